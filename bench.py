@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- refined patches/sec of the MI355X-native HPMVS refinement path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one expansion round: every rank runs the full optimize() (image selection, BOBYQA
@@ -18,6 +18,11 @@ N = 1 of that is exactly c2.  `--workload c2_50v_4k_1e6 --scaling weak` with N >
 its own 1e6 seeds instead.  The N > 1 line also carries per-rank kernel and exchange times
 (`per_rank`), so that a scaling curve can be read against the one-GPU shard timings of DESIGN section 7.
 
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR also writes what the last
+timed step computed (a fixed, seeded sample of the batch's result fields, float32 / float64 .npy files) so that two
+builds can be compared output for output.  The legs that take runs of their own (host_to_host, cpu_baseline, parity)
+run only with --full.
+
 Prints ONE JSON line (rank 0) with the contract fields plus
   roofline_issue : the compute-side view of the same kernel (it is instruction-issue / latency bound, not HBM
                  bound): VALU lane-cycles used / the machine's lane-cycles in the kernel's time, from the PMC
@@ -26,10 +31,10 @@ Prints ONE JSON line (rank 0) with the contract fields plus
   roofline     : algorithmic image bytes of the refinement kernel (588 B per sampleTexture that
                  passed its gates, counted by the kernel itself) / kernel time from HIP events on
                  the launch stream, against the 8 TB/s HBM peak;
-  cpu_baseline : the CPU oracle (restated photometric path around the reference's genuine NLopt
+  cpu_baseline : (--full) the CPU oracle (restated photometric path around the reference's genuine NLopt
                  BOBYQA when oracle/_ref travelled) on a bounded sample of the same seeds, all
                  host cores;
-  parity       : GPU vs that CPU run on the same sample (the metric's "mean NCC-score delta").
+  parity       : (--full) GPU vs that CPU run on the same sample (the metric's "mean NCC-score delta").
 """
 from __future__ import annotations
 
@@ -65,6 +70,28 @@ DEFAULT_WORKLOAD = "c2_50v_4k_1e6"              # N = 1
 DEFAULT_WORKLOAD_MULTI = "c3_50v_4k_1e6_sharded"  # N > 1: the same batch cut across the ranks (BASELINE configs[3])
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s (spec)
 RECORD_BYTES = dd.RECORD_BYTES  # all-gathered refined-patch record
+DUMP_ROWS = 65536  # --dump-outputs: rows of the seeded sample (~20 MB at 50 views) ...
+DUMP_BYTES = 48 << 20  # ... fewer where the image lists are wide, so that the files stay below 64 MB
+DUMP_SEED = 20240917
+
+
+def dump_outputs(outdir, work, n):
+    """The result fields of the last step (what a caller of hpmvs_optimize_batch receives) as DIR/<name>.npy: every row
+    when the batch is small, else a fixed seeded sample of rows (their indices in DIR/row_index.npy)."""
+    os.makedirs(outdir, exist_ok=True)
+    row_bytes = 4 * (18 + work["images"].shape[1]) + 8 * 5   # float32 fields + images, float64 fmin / x / row index
+    m = min(DUMP_ROWS, DUMP_BYTES // row_bytes)
+    if n <= m:
+        rows = np.arange(n, dtype=np.int64)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, m, replace=False))
+    idx = torch.from_numpy(rows).to(work["ok"].device)
+    np.save(os.path.join(outdir, "row_index.npy"), rows.astype(np.float64))
+    for k in ("center", "normal", "color", "ncc", "fmin", "x", "ok", "n_images", "images", "result", "nevals", "stage",
+              "ngrabs"):
+        a = work[k].index_select(0, idx).cpu().numpy()
+        a = a.astype(np.float64) if a.dtype == np.float64 else a.astype(np.float32)  # (the integer fields are < 2^24)
+        np.save(os.path.join(outdir, f"{k}.npy"), a)
 
 
 def device_batch(seeds, dev, max_images):
@@ -230,6 +257,11 @@ def main(argv=None, backend=None):
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--check-gather", action="store_true",
                     help="after the timed steps: compare the gathered records with the un-gathered results (tests)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write the last step's result fields (a seeded sample) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: host_to_host (staged and zero-copy), the CPU "
+                         "baseline and the parity sample (off: the plain run does only what the headline needs)")
     args = ap.parse_args(argv)
 
     rank = int(os.environ.get("RANK", "0"))
@@ -311,6 +343,8 @@ def main(argv=None, backend=None):
         step(timed=True)
     fence()
     elapsed_rank = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, work, n_seeds)
     # average launch duration of the refinement kernel over the timed region (and of pack + all-gather behind it)
     last_ms = float(np.mean([be.ms_between(a, b) for a, b, _ in marks]))
     exch_ms = float(np.mean([be.ms_between(b, c) for _, b, c in marks])) if use_dist else 0.0
@@ -346,7 +380,7 @@ def main(argv=None, backend=None):
     # seed arrays coming from pinned host memory and the refined fields copied back, timed separately (PCIe
     # inclusive; reported beside `value`, never as `value`: the bench contract times inputs resident in HBM)
     h2h = None
-    if not use_dist and backend is None:
+    if args.full and not use_dist and backend is None:
         in_keys = ("center", "normal", "scale", "n_images", "images")
         out_keys = ("center", "normal", "n_images", "images", "ok", "color", "fmin")
         host_in = {k: pristine[k].cpu().pin_memory() for k in in_keys}
@@ -484,7 +518,7 @@ def main(argv=None, backend=None):
             out["roofline"]["traffic_note"] = f"pmc_traffic.json unreadable: {e}"
 
     # ---- CPU baseline + parity on a bounded sample (rank 0, N = 1 only)
-    if rank == 0 and world == 1 and not args.no_cpu and backend is None:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and backend is None:
         try:
             cpu_leg(out, args, scene, seeds, n_seeds, work, ok, nevals, stage)
         except Exception as e:  # the GPU line must survive a box without the checker

@@ -570,7 +570,8 @@ def test_oracle_extend_round_bookkeeping():
     scene, seeds, _ = golden_scene()
     osc = orc.OracleScene(scene)
     P = orc.patches_from_seeds(seeds, list(range(40)))
-    orc.optimize_batch(osc, P, n_threads=4)
+    which = orc.best_optimizer(allow_port=True)   # (bookkeeping under test: the port stands in where oracle/_ref was not built)
+    orc.optimize_batch(osc, P, which=which, n_threads=4)
     good = [p for p in P if p.stage == 0][:12]
     assert len(good) >= 6
     parents = (orc.Patch * len(good))(*good)
@@ -583,7 +584,7 @@ def test_oracle_extend_round_bookkeeping():
             D.set_depths(p)
         before = [D.level(v, l).copy() for v in range(osc.n_views) for l in range(6)]
         occ = set(occ0)
-        out, counts = orc.extend_round(osc, D, parents, width, occ, frozen_gates=(mode == "frozen"))
+        out, counts = orc.extend_round(osc, D, parents, width, occ, frozen_gates=(mode == "frozen"), which=which)
         st = np.array([out[t].stage for t in range(6 * len(good))])
         assert set(st.tolist()) <= {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 20, 21, 22, 23, 24, 25, 26, 100}
         acc = np.nonzero(st == 0)[0]
@@ -608,7 +609,7 @@ def test_oracle_extend_round_bookkeeping():
             for dy in np.linspace(-1.5, 1.5, 7):
                 for dz in np.linspace(-1.5, 1.5, 7):
                     full.add(orc.cell_key([p.center[0] + dx * width, p.center[1] + dy * width, p.center[2] + dz * width], width))
-    out, counts = orc.extend_round(osc, D, parents, width, full)
+    out, counts = orc.extend_round(osc, D, parents, width, full, which=which)
     assert all(out[t].stage == 20 and out[t].nevals == 0 for t in range(6 * len(good)))
 
 

@@ -38,8 +38,8 @@ timeout 1000 bash profiles/collect.sh $TAG --steps 3 --warmup 1 --no-cpu > gpuru
 timeout 60 python profiles/make_pmc_record.py $O $TAG $O/pmc_traffic.json | tail -3 || { echo "make_pmc_record failed" | tee -a $O/FAILED.txt; FAILED=1; }
 keep 200 $O/phase_profile_c2.txt python tools/phase_profile.py tools/libhpmvs_prof.so 50 3840 2160 1000000
 keep 200 $O/phase_profile_c1.txt python tools/phase_profile.py tools/libhpmvs_prof.so
-keep 300 $O/bench_c1.json python bench.py --workload c1_12v_1080p_1e5 --steps 5 --warmup 1
-keep 400 $O/bench_c2.json python bench.py --steps 5 --warmup 1
-keep 600 $O/bench_c4_n1.json python bench.py --workload c4_200v_4k_1e7 --steps 2 --warmup 1 --cpu-sample 16384 --cpu-timing-sample 131072
+keep 300 $O/bench_c1.json python bench.py --workload c1_12v_1080p_1e5 --steps 5 --warmup 1 --full
+keep 400 $O/bench_c2.json python bench.py --steps 5 --warmup 1 --full
+keep 600 $O/bench_c4_n1.json python bench.py --workload c4_200v_4k_1e7 --steps 2 --warmup 1 --full --cpu-sample 16384 --cpu-timing-sample 131072
 [ -f $O/bench_c2.json ] && tail -c 400 $O/bench_c2.json; echo
 [ $FAILED = 0 ] && echo "collect_round: all files written" || { echo "collect_round: SOME FILES ARE MISSING (see $O/FAILED.txt)"; exit 1; }
