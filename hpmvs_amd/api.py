@@ -57,6 +57,7 @@ EXPORTS = [
     "hpmvs_scene_depth_reset", "hpmvs_scene_depth_set_level", "hpmvs_scene_depth_get_level",
     "hpmvs_set_depths_batch", "hpmvs_depth_gates_batch", "hpmvs_depth_footprints_batch", "hpmvs_depth_ops_batch", "hpmvs_level_support_batch",
     "hpmvs_host_alloc", "hpmvs_host_free", "hpmvs_last_staging",
+    "hpmvs_undistort", "hpmvs_undistort_map", "hpmvs_scene_set_view_distorted",
 ]
 
 _lib = None
@@ -85,6 +86,10 @@ def lib():
     L.hpmvs_scene_bytes.restype = C.c_size_t
     L.hpmvs_scene_bytes.argtypes = [C.c_void_p]
     L.hpmvs_build_pyramid.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    L.hpmvs_undistort.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int]
+    L.hpmvs_undistort_map.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]
+    L.hpmvs_scene_set_view_distorted.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                 C.POINTER(Camera), C.c_float, C.c_float]
     L.hpmvs_optimize_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(PatchBatch), C.c_int, C.c_void_p]
     L.hpmvs_init_patches_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.POINTER(PatchBatch), C.c_int, C.c_void_p]
@@ -155,6 +160,32 @@ def _ptr(a):
     return a.data_ptr()  # torch tensor
 
 
+def undistort(img, f: float, k1: float, device: int = 0):
+    """Image::undistort of the reference on the GPU: raw level 0 (uint8 [H, W, 3], numpy or a device tensor) -> the
+    undistorted level 0 of the same type and place.  Pixels the reference never writes are 0; k1 == 0 returns a copy."""
+    if isinstance(img, np.ndarray):
+        src = np.ascontiguousarray(img, dtype=np.uint8)
+        if src.ndim != 3 or src.shape[2] != 3:
+            raise HpmvsError("undistort: img must be uint8 [H, W, 3]")
+        out = np.empty_like(src)
+        _chk(lib().hpmvs_undistort(device, src.ctypes.data, src.shape[1], src.shape[0], float(f), float(k1),
+                                   out.ctypes.data, 0))
+        return out
+    src = img.contiguous()
+    if src.dim() != 3 or src.shape[2] != 3 or str(src.dtype) != "torch.uint8":
+        raise HpmvsError("undistort: img must be uint8 [H, W, 3]")
+    out = torch.empty_like(src)
+    _chk(lib().hpmvs_undistort(device, src.data_ptr(), src.shape[1], src.shape[0], float(f), float(k1), out.data_ptr(), 1))
+    return out
+
+
+def undistort_map(w: int, h: int, f: float, k1: float, device: int = 0) -> np.ndarray:
+    """float32 [h, w, 2]: the level-0 point (x, y) each output pixel of hpmvs_undistort samples (NaN included)."""
+    xy = np.empty((int(h), int(w), 2), dtype=np.float32)
+    _chk(lib().hpmvs_undistort_map(device, int(w), int(h), float(f), float(k1), xy.ctypes.data))
+    return xy
+
+
 class Scene:
     """HBM-resident scene: Scene::addCameras + extractCoVisiblilty state the path reads
     (reference include/hpmvs/Scene.h:69-71)."""
@@ -170,10 +201,16 @@ class Scene:
             rgb = v.rgb
             if isinstance(rgb, np.ndarray):
                 rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
-                _chk(L.hpmvs_scene_set_view(self.h, i, v.width, v.height, rgb.ctypes.data, 0, C.byref(cam)))
+                ptr, on_device = rgb.ctypes.data, 0
             else:  # torch tensor already in HBM
                 rgb = rgb.contiguous()
-                _chk(L.hpmvs_scene_set_view(self.h, i, v.width, v.height, rgb.data_ptr(), 1, C.byref(cam)))
+                ptr, on_device = rgb.data_ptr(), 1
+            k1 = float(getattr(v, "k1", 0.0))
+            if k1 != 0.0:  # raw pixels of a camera with radial distortion: undistorted on the GPU (Image::load)
+                _chk(L.hpmvs_scene_set_view_distorted(self.h, i, v.width, v.height, ptr, on_device, C.byref(cam),
+                                                      float(v.f), k1))
+            else:
+                _chk(L.hpmvs_scene_set_view(self.h, i, v.width, v.height, ptr, on_device, C.byref(cam)))
         for i, lst in enumerate(synth_scene.covis):
             arr = (C.c_int32 * max(1, len(lst)))(*lst)
             _chk(L.hpmvs_scene_set_covis(self.h, i, arr, len(lst)))

@@ -257,8 +257,12 @@ int hpmvs_scene_create(int n_views, int device, hpmvs_scene** out) {
     return HPMVS_OK;
 }
 
-int hpmvs_scene_set_view(hpmvs_scene* s, int view, int width, int height, const uint8_t* rgb_l0, int rgb_on_device,
-                         const hpmvs_camera* cam) {
+// Image::undistort's parameters (reference Image.h:80: float f_, k1_): k1 finite, f finite and positive
+static bool undistort_args_ok(float f, float k1) { return std::isfinite(k1) && std::isfinite(f) && f > 0.0f; }
+
+// hpmvs_scene_set_view and, for k1 != 0, hpmvs_scene_set_view_distorted: level 0 is the raw view undistorted on the GPU
+static int set_view(hpmvs_scene* s, int view, int width, int height, const uint8_t* rgb_l0, int rgb_on_device,
+                    const hpmvs_camera* cam, float f, float k1) {
     if (!s || !cam || !rgb_l0) return fail(HPMVS_ERR_ARG, "scene_set_view: null argument");
     if (s->committed) return fail(HPMVS_ERR_STATE, "scene_set_view: scene already committed");
     if (view < 0 || view >= s->n_views || width < 2 || height < 2) return fail(HPMVS_ERR_ARG, "scene_set_view: bad view/size");
@@ -280,6 +284,19 @@ int hpmvs_scene_set_view(hpmvs_scene* s, int view, int width, int height, const 
         }
         if (total > 0xffffffffull) return fail(HPMVS_ERR_ARG, "scene_set_view: image too large (a view's pyramid must stay below 4 GB)");
     }
+    // the raw view of a distorted one on the device: the caller's buffer, or a copy of the host pixels
+    const uint8_t* raw = nullptr;
+    uint8_t* raw_copy = nullptr;
+    struct FreeRaw { uint8_t*& p; ~FreeRaw() { if (p) hipFree(p); } } free_raw{raw_copy};
+    if (k1 != 0.0f) {
+        if (rgb_on_device) {
+            raw = rgb_l0;
+        } else {
+            HIPCHK(hipMalloc((void**)&raw_copy, (size_t)width * height * 3));
+            HIPCHK(hipMemcpy(raw_copy, rgb_l0, (size_t)width * height * 3, hipMemcpyHostToDevice));
+            raw = raw_copy;
+        }
+    }
     uint8_t* slab = nullptr;
     HIPCHK(hipMalloc((void**)&slab, total));
     if (s->view_set[view]) {  // set again: release the previous pyramid of this view
@@ -298,7 +315,10 @@ int hpmvs_scene_set_view(hpmvs_scene* s, int view, int width, int height, const 
     for (int l = 0; l < levels; l++) {
         uint8_t* d = slab + off[l];
         const size_t nb = (size_t)w * h * 3;
-        if (l == 0) {
+        if (l == 0 && raw) {
+            launch_undistort(raw, w, h, f, k1, d, nullptr);
+            HIPCHK(hipGetLastError());
+        } else if (l == 0) {
             HIPCHK(hipMemcpy(d, rgb_l0, nb, rgb_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
         } else {
             launch_half_resize(V.pix[l - 1], V.w[l - 1], V.h[l - 1], d, nullptr);
@@ -316,6 +336,17 @@ int hpmvs_scene_set_view(hpmvs_scene* s, int view, int width, int height, const 
     V.n_levels = levels;
     s->view_set[view] = 1;
     return HPMVS_OK;
+}
+
+int hpmvs_scene_set_view(hpmvs_scene* s, int view, int width, int height, const uint8_t* rgb_l0, int rgb_on_device,
+                         const hpmvs_camera* cam) {
+    return set_view(s, view, width, height, rgb_l0, rgb_on_device, cam, 1.0f, 0.0f);
+}
+
+int hpmvs_scene_set_view_distorted(hpmvs_scene* s, int view, int width, int height, const uint8_t* rgb_raw,
+                                   int rgb_on_device, const hpmvs_camera* cam, float f, float k1) {
+    if (!undistort_args_ok(f, k1)) return fail(HPMVS_ERR_ARG, "scene_set_view_distorted: f must be finite and > 0, k1 finite");
+    return set_view(s, view, width, height, rgb_raw, rgb_on_device, cam, f, k1);
 }
 
 int hpmvs_scene_set_covis(hpmvs_scene* s, int view, const int32_t* ids, int n) {
@@ -418,6 +449,53 @@ int hpmvs_build_pyramid(int device, const uint8_t* src, int w, int h, uint8_t* d
     launch_half_resize(ds, w, h, dd, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(dst, dd, nb2, hipMemcpyDeviceToHost));
+    return HPMVS_OK;
+}
+
+int hpmvs_undistort(int device, const uint8_t* src, int w, int h, float f, float k1, uint8_t* dst, int on_device) {
+    if (!src || !dst || w < 2 || h < 2) return fail(HPMVS_ERR_ARG, "undistort: bad argument");
+    if (!undistort_args_ok(f, k1)) return fail(HPMVS_ERR_ARG, "undistort: f must be finite and > 0, k1 finite");
+    const size_t nb = (size_t)w * h * 3;
+    if (src < dst + nb && dst < src + nb) return fail(HPMVS_ERR_ARG, "undistort: src and dst overlap");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(HPMVS_ERR_NODEVICE, "no HIP device visible");
+    if (device < 0 || device >= ndev) return fail(HPMVS_ERR_ARG, "undistort: bad device index");
+    HIPCHK(hipSetDevice(device));
+    if (k1 == 0.0f) {  // Image::load undistorts only for k1 != 0 (reference Image.cpp:50-53)
+        HIPCHK(hipMemcpy(dst, src, nb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToHost));
+        return HPMVS_OK;
+    }
+    if (on_device) {
+        launch_undistort(src, w, h, f, k1, dst, nullptr);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipDeviceSynchronize());
+        return HPMVS_OK;
+    }
+    uint8_t *ds = nullptr, *dd = nullptr;
+    struct Free { uint8_t*& a; uint8_t*& b; ~Free() { if (a) hipFree(a); if (b) hipFree(b); } } free_on_exit{ds, dd};
+    HIPCHK(hipMalloc((void**)&ds, nb));
+    HIPCHK(hipMalloc((void**)&dd, nb));
+    HIPCHK(hipMemcpy(ds, src, nb, hipMemcpyHostToDevice));
+    launch_undistort(ds, w, h, f, k1, dd, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(dst, dd, nb, hipMemcpyDeviceToHost));
+    return HPMVS_OK;
+}
+
+int hpmvs_undistort_map(int device, int w, int h, float f, float k1, float* xy) {
+    if (!xy || w < 2 || h < 2) return fail(HPMVS_ERR_ARG, "undistort_map: bad argument");
+    if (!undistort_args_ok(f, k1)) return fail(HPMVS_ERR_ARG, "undistort_map: f must be finite and > 0, k1 finite");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(HPMVS_ERR_NODEVICE, "no HIP device visible");
+    if (device < 0 || device >= ndev) return fail(HPMVS_ERR_ARG, "undistort_map: bad device index");
+    HIPCHK(hipSetDevice(device));
+    const size_t nf = (size_t)w * h * 2;
+    float* dxy = nullptr;
+    struct Free { float*& a; ~Free() { if (a) hipFree(a); } } free_on_exit{dxy};
+    HIPCHK(hipMalloc((void**)&dxy, nf * sizeof(float)));
+    launch_undistort_map(w, h, f, k1, dxy, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(xy, dxy, nf * sizeof(float), hipMemcpyDeviceToHost));
     return HPMVS_OK;
 }
 

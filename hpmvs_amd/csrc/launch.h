@@ -7,6 +7,9 @@
 namespace hpmvs {
 
 void launch_half_resize(const uint8_t* src, int w, int h, uint8_t* dst, hipStream_t st);
+// level-0 radial undistortion (kernel_undistort.hip): dst [h][w][3] u8, src read only; xy [h][w][2] source points
+void launch_undistort(const uint8_t* src, int w, int h, float f, float k1, uint8_t* dst, hipStream_t st);
+void launch_undistort_map(int w, int h, float f, float k1, float* xy, hipStream_t st);
 void launch_objective(const DevScene& sc, const DevOptions& o, const DevBatch& b, const double* xs, double* f_out,
                       int32_t* ngrabs_out, hipStream_t st);
 // the same values from the one-lane-per-grab kernel (kernel_objective_lane.hip)

@@ -215,10 +215,15 @@ void Image::init(const mo3d::NVM_Camera* cam, const int maxLevel) {
 void Image::setPixels(int width, int height, const uint8_t* rgb) {
     width_ = width; height_ = height;
     rgb_.assign(rgb, rgb + (size_t)width * height * 3);
+    raw_ = false;
+}
+void Image::setRawPixels(int width, int height, const uint8_t* rgb) {
+    setPixels(width, height, rgb);
+    raw_ = true;
 }
 bool Image::load() {
-    if (!rgb_.empty()) return true;  // pixels were handed over with setPixels
-    if (k1_ != 0) { std::cerr << "Image::load: radial undistortion (k1 != 0) is outside this path\n"; return false; }
+    if (!rgb_.empty()) return true;  // pixels were handed over with setPixels / setRawPixels
+    // raw pixels: the undistortion of Image.cpp:50-53 runs on the GPU when the scene is uploaded (Scene::deviceScene)
     std::ifstream in(path_.c_str(), std::ios::binary);
     std::string magic;
     int w = 0, h = 0, maxv = 0;
@@ -229,6 +234,7 @@ bool Image::load() {
     in.read((char*)rgb_.data(), rgb_.size());
     if (!in) return false;
     width_ = w; height_ = h;
+    raw_ = true;
     return true;
 }
 
@@ -519,8 +525,12 @@ hpmvs_scene* Scene::deviceScene() const {
         for (int k = 0; k < 3; k++) { hc.xaxis[k] = c.xAxis_[k]; hc.yaxis[k] = c.yAxis_[k]; hc.zaxis[k] = c.zAxis_[k]; }
         hc.fsum = c.kMat_[0](0, 0) + c.kMat_[0](1, 1);
         hc.n_levels = c.getLevels();
-        if (hpmvs_scene_set_view(s, (int)i, images_[i].getWidth(), images_[i].getHeight(), images_[i].pixels().data(), 0,
-                                 &hc) != HPMVS_OK ||
+        const Image& im = images_[i];
+        const int rc = im.isRaw() && im.getK1() != 0
+                           ? hpmvs_scene_set_view_distorted(s, (int)i, im.getWidth(), im.getHeight(), im.pixels().data(), 0, &hc,
+                                                            im.getFocal(), im.getK1())
+                           : hpmvs_scene_set_view(s, (int)i, im.getWidth(), im.getHeight(), im.pixels().data(), 0, &hc);
+        if (rc != HPMVS_OK ||
             hpmvs_scene_set_covis(s, (int)i, covis_[i].data(), (int)covis_[i].size()) != HPMVS_OK) {
             std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl;
             hpmvs_scene_destroy(s);

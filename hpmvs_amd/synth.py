@@ -82,6 +82,7 @@ class View:
     q: np.ndarray  # wxyz, world->camera
     c: np.ndarray  # centre (world)
     rgb: object = None  # uint8 [H, W, 3] (numpy, or a torch tensor when rendered on a device)
+    k1: float = 0.0  # NVM radial distortion r: != 0 means `rgb` is the raw image, undistorted when the scene is uploaded
 
 
 @dataclass

@@ -1,7 +1,8 @@
 // mo3d::Image -- the level-0 pixels of one view (reference include/hpmvs/Image.h:50-87).  The reference
-// loads a JPEG through CImg and builds the pyramid on the host (src/hpmvs/Image.cpp:41-66); here the
-// caller hands over interleaved u8 RGB (file decoding is I/O outside the path) and the pyramid is
-// built on the GPU when the scene is uploaded.
+// loads a JPEG through CImg, undistorts it when the camera's radial coefficient k1 (NVM field r) is not 0
+// and builds the pyramid on the host (src/hpmvs/Image.cpp:41-146); here the caller hands over interleaved
+// u8 RGB (file decoding is I/O outside the path) and both the undistortion and the pyramid run on the GPU
+// when the scene is uploaded (Scene::deviceScene: hpmvs_scene_set_view_distorted for raw pixels).
 #ifndef HPMVS_IMAGE_H_
 #define HPMVS_IMAGE_H_
 #include <cstdint>
@@ -11,11 +12,17 @@
 namespace mo3d {
 class Image {
 public:
-    Image() : f_(1.0f), k1_(0.0f), maxLevel_(0), width_(0), height_(0) {}
+    Image() : f_(1.0f), k1_(0.0f), maxLevel_(0), width_(0), height_(0), raw_(false) {}
     virtual ~Image() {}
     void init(const mo3d::NVM_Camera* cam, const int maxLevel = 1);
-    bool load();  // binary PPM (P6) only; k1 != 0 (undistortion) is not supported and fails
+    bool load();  // binary PPM (P6) only; the pixels are kept raw (as the camera recorded them)
+    // pixels taken as given: already undistorted (or k1 == 0); k1 is NOT applied to them
     void setPixels(int width, int height, const uint8_t* rgb_interleaved);
+    // pixels as the camera recorded them: undistorted with f and k1 on upload when k1 != 0
+    void setRawPixels(int width, int height, const uint8_t* rgb_interleaved);
+    bool isRaw() const { return raw_; }
+    float getFocal() const { return f_; }  // Image::f_ (float, NVM f)
+    float getK1() const { return k1_; }    // Image::k1_ (float, NVM r)
     inline int getWidth(int level = 0) const { return width_ >> level; }
     inline int getHeight(int level = 0) const { return height_ >> level; }
     int levels() const { return maxLevel_ + 1; }
@@ -25,6 +32,7 @@ private:
     std::string path_;
     float f_, k1_;
     int maxLevel_, width_, height_;
+    bool raw_;  // rgb_ still carries the radial distortion
 };
 }  // namespace mo3d
 #endif

@@ -24,6 +24,8 @@
  *   hpmvs_inccs_batch        <- PatchOptimizer::setINCCs, PatchOptimizer.cpp:448-474.
  *   hpmvs_build_pyramid      <- Image::load's pyramid, src/hpmvs/Image.cpp:55-63
  *                               (CImg get_resize_halfXY, thirdLibs/cimg/CImg.h:21189-21203).
+ *   hpmvs_undistort,         <- Image::undistort, src/hpmvs/Image.cpp:68-146 (run by Image::load for
+ *   hpmvs_scene_set_view_distorted  k1 != 0, :50-53), before the pyramid.
  *   hpmvs_init_patches_batch <- the seed loop of Scene::initPatches, src/hpmvs/Scene.cpp:112-178.
  *   hpmvs_expand_batch       <- the candidate loops of CellProcessor::extend / ::branch,
  *                               src/hpmvs/CellProcessor.cpp:84-142 and :210-262.
@@ -134,6 +136,23 @@ size_t hpmvs_scene_bytes(const hpmvs_scene *s);
 
 /* stand-alone pyramid kernel: src (w x h, device or host) -> dst (w/2 x h/2) */
 int hpmvs_build_pyramid(int device, const uint8_t *src, int w, int h, uint8_t *dst, int on_device);
+
+/* ---- radial undistortion (VisualSFM's one-parameter model: NVM camera field r) ------------- */
+/* Image::undistort of the reference: every output pixel samples the raw level 0 at the point m that satisfies
+ * m (1 + k1 |m|^2) = p in coordinates normalised by f around (w/2, h/2), bilinearly as CImg does, truncated to u8.
+ * `f` and `k1` are the float values the reference keeps (Image::f_, Image::k1_).  Pixels whose source point falls
+ * outside (1, w-1) x (1, h-1) -- the reference leaves them as uninitialised memory -- are 0 here.
+ * All three entries: HPMVS_ERR_ARG unless k1 is finite and f is finite and > 0; HPMVS_ERR_NODEVICE without a device. */
+/* src -> dst, both w x h interleaved u8 RGB (device pointers when on_device != 0, else host); the two buffers must not
+ * overlap.  k1 == 0 returns src byte for byte (the reference never resamples such a view). */
+int hpmvs_undistort(int device, const uint8_t *src, int w, int h, float f, float k1, uint8_t *dst, int on_device);
+/* diagnostics: xy [h][w][2] (host) = the float source point each output pixel samples, NaN included */
+int hpmvs_undistort_map(int device, int w, int h, float f, float k1, float *xy);
+/* hpmvs_scene_set_view for a raw view: level 0 is undistorted on the GPU, then the pyramid is built from it.  A host
+ * rgb_raw is copied to the device first; a device one (rgb_on_device != 0) is read in place.  k1 == 0 is exactly
+ * hpmvs_scene_set_view. */
+int hpmvs_scene_set_view_distorted(hpmvs_scene *s, int view, int width, int height, const uint8_t *rgb_raw,
+                                   int rgb_on_device, const hpmvs_camera *cam, float f, float k1);
 
 /* ---- the hot path ------------------------------------------------------------------------- */
 /* Full optimize() for every patch of the batch.  `stream` is a hipStream_t (NULL = default
