@@ -46,6 +46,11 @@ class PatchBatch(C.Structure):
                 ("result", C.c_void_p), ("nevals", C.c_void_p), ("stage", C.c_void_p), ("ngrabs", C.c_void_p)]
 
 
+class LeafTable(C.Structure):
+    _fields_ = [("n", C.c_int32), ("root_center", C.c_float * 3), ("root_width", C.c_float), ("cell_center", C.c_void_p),
+                ("cell_width", C.c_void_p), ("patch_center", C.c_void_p), ("born", C.c_void_p), ("died", C.c_void_p)]
+
+
 EXPORTS = [
     "hpmvs_last_error", "hpmvs_device_count", "hpmvs_build_id", "hpmvs_default_options", "hpmvs_camera_from_nvm",
     "hpmvs_scene_create", "hpmvs_scene_set_view", "hpmvs_scene_set_covis", "hpmvs_scene_commit",
@@ -58,6 +63,7 @@ EXPORTS = [
     "hpmvs_set_depths_batch", "hpmvs_depth_gates_batch", "hpmvs_depth_footprints_batch", "hpmvs_depth_ops_batch", "hpmvs_level_support_batch",
     "hpmvs_host_alloc", "hpmvs_host_free", "hpmvs_last_staging",
     "hpmvs_undistort", "hpmvs_undistort_map", "hpmvs_scene_set_view_distorted",
+    "hpmvs_regularize_batch",
 ]
 
 _lib = None
@@ -116,6 +122,8 @@ def lib():
     L.hpmvs_depth_gates_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_float, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int, C.c_void_p]
     L.hpmvs_depth_ops_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_void_p, C.c_int, C.c_void_p]
+    L.hpmvs_regularize_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LeafTable),
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.hpmvs_level_support_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     _lib = L
     return L
@@ -454,3 +462,40 @@ def build_pyramid(img: np.ndarray, device: int = 0) -> np.ndarray:
     out = np.zeros((h // 2, w // 2, 3), dtype=np.uint8)
     _chk(lib().hpmvs_build_pyramid(device, img.ctypes.data, w, h, out.ctypes.data, 0))
     return out
+
+
+INT32_MAX = 2**31 - 1
+REGULARIZE_PROBES = 24
+
+
+def regularize_batch(scene: Scene, cells: Batch, cell_width, position, expanded, root_center, root_width, leaf_center,
+                     leaf_width, leaf_patch, born=None, died=None, flatness=None, neighbours: bool = True):
+    """CellProcessor::regularize (reference CellProcessor.cpp:309-367) for every cell against a versioned table of the nonempty
+    leaves (include/hpmvs_amd.h: hpmvs_regularize_batch).  leaf_center / leaf_width: Leaf::c_ / width_, leaf_patch: the centre
+    of data[0]; born / died (default: -1 / INT32_MAX, the tree as it is) the queue positions between which a leaf exists.
+    flatness: the cells' flatness_ before the call (default -1), kept for unexpanded cells.
+    Returns (flatness [n] float32, n_neighbours [n] int32 (-1: not expanded), neighbour_leaf [n, 24] int32 or None)."""
+    n = cells.n
+    L = int(len(leaf_width))
+    cw = np.ascontiguousarray(cell_width, dtype=np.float32).reshape(n)
+    pos = np.ascontiguousarray(position, dtype=np.int32).reshape(n)
+    exp = np.ascontiguousarray(expanded).astype(np.uint8).reshape(n)
+    lc = np.ascontiguousarray(leaf_center, dtype=np.float32).reshape(L, 3)
+    lw = np.ascontiguousarray(leaf_width, dtype=np.float32).reshape(L)
+    lp = np.ascontiguousarray(np.asarray(leaf_patch, dtype=np.float32)[:, :3]).reshape(L, 3)
+    lb = np.full(L, -1, np.int32) if born is None else np.ascontiguousarray(born, dtype=np.int32).reshape(L)
+    ld = np.full(L, INT32_MAX, np.int32) if died is None else np.ascontiguousarray(died, dtype=np.int32).reshape(L)
+    t = LeafTable()
+    t.n = L
+    for k in range(3):
+        t.root_center[k] = float(np.float32(root_center[k]))
+    t.root_width = float(np.float32(root_width))
+    t.cell_center, t.cell_width, t.patch_center = lc.ctypes.data, lw.ctypes.data, lp.ctypes.data
+    t.born, t.died = lb.ctypes.data, ld.ctypes.data
+    fl = np.full(n, -1.0, np.float32) if flatness is None else np.ascontiguousarray(flatness, dtype=np.float32).reshape(n).copy()
+    nn = np.zeros(n, np.int32)
+    nb = np.zeros((n, REGULARIZE_PROBES), np.int32) if neighbours else None
+    b = cells.c_struct()
+    _chk(lib().hpmvs_regularize_batch(scene.h, C.byref(b), cw.ctypes.data, pos.ctypes.data, exp.ctypes.data, C.byref(t),
+                                      fl.ctypes.data, nn.ctypes.data, None if nb is None else nb.ctypes.data, 0, None))
+    return fl, nn, nb

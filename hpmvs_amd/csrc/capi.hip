@@ -1713,6 +1713,130 @@ int hpmvs_level_support_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, 
     HIPCHK(hipStreamSynchronize(st));
     return stage_out(support, dsup, (size_t)b->n);
 }
+// CellProcessor::regularize (src/hpmvs/CellProcessor.cpp:309-367) for a level of cells against a versioned leaf table
+// (kernel_regularize.hip).  Every device byte comes from a launch workspace: [1 KB counter block, untouched] [header] [hash keys]
+// [hash values] and, for host pointers, the leaf table and the cells in chunks that fit the rest.  The scene lock is held for the
+// whole call (the workspace is this call's until its last kernel has been enqueued).
+static size_t reg_align(size_t v) { return (v + 255) & ~(size_t)255; }
+int hpmvs_regularize_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, const float* cell_width, const int32_t* position,
+                           const uint8_t* expanded, const hpmvs_leaf_table* lt, float* flatness, int32_t* n_neighbours,
+                           int32_t* neighbour_leaf, int on_device, void* stream) {
+    if (hpmvs_device_count() <= 0) return fail(HPMVS_ERR_NODEVICE, "regularize_batch: no HIP device visible");
+    if (!s || !b || !lt) return fail(HPMVS_ERR_ARG, "regularize_batch: null scene / cells / leaf table");
+    if (!s->committed) return fail(HPMVS_ERR_STATE, "regularize_batch: scene not committed");
+    if (b->n < 0 || lt->n < 0) return fail(HPMVS_ERR_ARG, "regularize_batch: negative count");
+    if (b->n > 0 && (b->max_images < 1 || !b->center || !b->normal || !b->n_images || !b->images || !cell_width || !position ||
+                     !expanded || !flatness || !n_neighbours))
+        return fail(HPMVS_ERR_ARG, "regularize_batch: cell arrays missing");
+    if (lt->n > 0 && (!lt->cell_center || !lt->cell_width || !lt->patch_center || !lt->born || !lt->died))
+        return fail(HPMVS_ERR_ARG, "regularize_batch: leaf table arrays missing");
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(lt->root_center[k])) return fail(HPMVS_ERR_ARG, "regularize_batch: root centre not finite");
+    if (!(lt->root_width > 0.0f) || !std::isfinite(lt->root_width)) return fail(HPMVS_ERR_ARG, "regularize_batch: root width must be finite and > 0");
+    if (b->n == 0) return HPMVS_OK;
+    const size_t n = (size_t)b->n, L = (size_t)lt->n;
+    std::vector<int32_t> href;
+    if (!on_device) {   // the reference image of an expanded cell must be a view of the scene (host arrays: checked here)
+        href.resize(n);
+        for (size_t i = 0; i < n; i++) {
+            href[i] = b->images[i * (size_t)b->max_images];
+            if (expanded[i] && (b->n_images[i] < 1 || href[i] < 0 || href[i] >= s->n_views))
+                return fail(HPMVS_ERR_ARG, "regularize_batch: an expanded cell's reference image is not a view of the scene");
+        }
+    }
+    size_t slots = 2;
+    while (slots < 2 * L) slots <<= 1;
+    const size_t o_hdr = kQueueSlotBytes, o_keys = reg_align(o_hdr + 16), o_vals = reg_align(o_keys + 8 * slots);
+    size_t o_end = reg_align(o_vals + 4 * slots);
+    size_t o_lcc = 0, o_lcw = 0, o_lpc = 0, o_lb = 0, o_ld = 0;
+    if (!on_device) {
+        o_lcc = o_end; o_lcw = reg_align(o_lcc + 12 * L); o_lpc = reg_align(o_lcw + 4 * L); o_lb = reg_align(o_lpc + 12 * L);
+        o_ld = reg_align(o_lb + 4 * L); o_end = reg_align(o_ld + 4 * L);
+    }
+    // host cells: 16 + 16 (centre, normal) + 4 x 4 (ref, width, position, flatness) + 1 (expanded) + 4 + 96 (outputs) bytes, 8 arrays
+    const size_t per_cell = 149, chunk_min = 1024;
+    if (slots > ((size_t)1 << 30) || o_end + (on_device ? 0 : chunk_min * per_cell + 8 * 256) > s->ws_bytes)
+        return fail(HPMVS_ERR_ARG, "regularize_batch: the leaf table does not fit the launch workspace");
+    int rc;
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::recursive_mutex> lk(s->mu);
+    if ((rc = service_quiesce(s))) return rc;
+    int32_t* q;
+    int slot;
+    if ((rc = acquire_workspace(s, &q, &slot, st))) return rc;
+    struct Release { const hpmvs_scene* s; int slot; hipStream_t st; ~Release() { hipEventRecord(s->slot_done[slot], st); s->slot_used[slot] = true; } } rel{s, slot, st};
+    char* w = (char*)q;
+    int32_t* hdr = (int32_t*)(w + o_hdr);
+    RegTree t;
+    t.root[0] = lt->root_center[0]; t.root[1] = lt->root_center[1]; t.root[2] = lt->root_center[2]; t.root[3] = lt->root_width;
+    t.n = lt->n; t.slots = (int32_t)slots;
+    t.keys = (unsigned long long*)(w + o_keys); t.vals = (int32_t*)(w + o_vals);
+    if (on_device) {
+        t.cell_center = lt->cell_center; t.cell_width = lt->cell_width; t.patch_center = lt->patch_center; t.born = lt->born; t.died = lt->died;
+    } else {
+        t.cell_center = (const float*)(w + o_lcc); t.cell_width = (const float*)(w + o_lcw); t.patch_center = (const float*)(w + o_lpc);
+        t.born = (const int32_t*)(w + o_lb); t.died = (const int32_t*)(w + o_ld);
+        if (L) {
+            HIPCHK(hipMemcpyAsync((void*)t.cell_center, lt->cell_center, 12 * L, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync((void*)t.cell_width, lt->cell_width, 4 * L, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync((void*)t.patch_center, lt->patch_center, 12 * L, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync((void*)t.born, lt->born, 4 * L, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync((void*)t.died, lt->died, 4 * L, hipMemcpyHostToDevice, st));
+        }
+    }
+    HIPCHK(hipMemsetAsync(hdr, 0, 16, st));
+    HIPCHK(hipMemsetAsync(t.keys, 0, 8 * slots, st));
+    launch_regularize_leaves(t, on_device ? b->n : 0, s->n_views, b->images, b->max_images, b->n_images, expanded, hdr, st);
+    HIPCHK(hipGetLastError());
+    int32_t h[3] = {0, 0, 0};
+    HIPCHK(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (h[0] & 1) return fail(HPMVS_ERR_ARG, "regularize_batch: a leaf's centre is not the one the root's subdivision gives for its width, or it lies deeper than 21 levels");
+    if (h[0] & 2) return fail(HPMVS_ERR_ARG, "regularize_batch: an expanded cell's reference image is not a view of the scene");
+    const int max_depth = h[1], min_depth = kRegMaxDepth + 1 - h[2];
+    const DevScene sc = dev_scene(s);
+    RegCells cl;
+    if (on_device) {
+        cl.n = b->n; cl.ref_stride = b->max_images;
+        cl.center = b->center; cl.normal = b->normal; cl.ref = b->images; cl.width = cell_width; cl.position = position; cl.expanded = expanded;
+        cl.flatness = flatness; cl.n_neighbours = n_neighbours; cl.neighbour = neighbour_leaf;
+        launch_regularize(sc, t, cl, min_depth, max_depth, st);
+        HIPCHK(hipGetLastError());
+        return HPMVS_OK;
+    }
+    const size_t chunk = std::min(n, (s->ws_bytes - o_end - 8 * 256) / per_cell);
+    char* c0 = w + o_end;
+    float* dcen = (float*)c0;
+    float* dnor = (float*)(c0 + reg_align(16 * chunk));
+    int32_t* dref = (int32_t*)((char*)dnor + reg_align(16 * chunk));
+    float* dwid = (float*)((char*)dref + reg_align(4 * chunk));
+    int32_t* dpos = (int32_t*)((char*)dwid + reg_align(4 * chunk));
+    float* dfl = (float*)((char*)dpos + reg_align(4 * chunk));
+    int32_t* dnn = (int32_t*)((char*)dfl + reg_align(4 * chunk));
+    int32_t* dnb = (int32_t*)((char*)dnn + reg_align(4 * chunk));
+    uint8_t* dexp = (uint8_t*)((char*)dnb + reg_align(96 * chunk));
+    for (size_t i0 = 0; i0 < n; i0 += chunk) {
+        const size_t m = std::min(chunk, n - i0);
+        HIPCHK(hipMemcpyAsync(dcen, b->center + 4 * i0, 16 * m, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(dnor, b->normal + 4 * i0, 16 * m, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(dref, href.data() + i0, 4 * m, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(dwid, cell_width + i0, 4 * m, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(dpos, position + i0, 4 * m, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(dfl, flatness + i0, 4 * m, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(dexp, expanded + i0, m, hipMemcpyHostToDevice, st));
+        cl.n = (int32_t)m; cl.ref_stride = 1;
+        cl.center = dcen; cl.normal = dnor; cl.ref = dref; cl.width = dwid; cl.position = dpos; cl.expanded = dexp;
+        cl.flatness = dfl; cl.n_neighbours = dnn; cl.neighbour = neighbour_leaf ? dnb : nullptr;
+        launch_regularize(sc, t, cl, min_depth, max_depth, st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(flatness + i0, dfl, 4 * m, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(n_neighbours + i0, dnn, 4 * m, hipMemcpyDeviceToHost, st));
+        if (neighbour_leaf) HIPCHK(hipMemcpyAsync(neighbour_leaf + 24 * i0, dnb, 96 * m, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    return HPMVS_OK;
+}
 int hpmvs_depth_gates_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, float margin, int abs_int,
                             int32_t* n_visible, int32_t* n_blocking, int32_t* n_free, int on_device, void* stream) {
     int rc = check_depth_batch(s, b, "depth_gates_batch");

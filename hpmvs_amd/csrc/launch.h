@@ -6,6 +6,34 @@
 
 namespace hpmvs {
 
+// CellProcessor::regularize over a versioned leaf table (kernel_regularize.hip, include/hpmvs_amd.h: hpmvs_regularize_batch).
+// Kept out of dev_types.h, whose hash is part of the refinement kernel's build id.
+constexpr int kRegMaxDepth = 21;   // 3 bits per level below the sentinel bit of a 64-bit path key
+struct RegTree {
+    float root[4];                     // c_ (3), width_ of the Branch the probes descend from
+    int32_t n;                         // nonempty leaves
+    int32_t slots;                     // hash slots (power of two, >= 2 n)
+    const float* cell_center;          // [n][3] Leaf::c_
+    const float* cell_width;           // [n]
+    const float* patch_center;         // [n][3] data[0]->center_
+    const int32_t* born;               // [n] the leaf exists at queue positions born < q < died
+    const int32_t* died;
+    unsigned long long* keys;          // [slots] path keys, 0 = free
+    int32_t* vals;                     // [slots] leaf index
+};
+struct RegCells {
+    int32_t n, ref_stride;
+    const float* center; const float* normal;   // [n][4]
+    const int32_t* ref;                          // images_[0] at ref[i * ref_stride]
+    const float* width;                          // [n] leaf width_
+    const int32_t* position;                     // [n] queue position
+    const uint8_t* expanded;                     // [n]
+    float* flatness;                             // [n] written for expanded cells only
+    int32_t* n_neighbours;                       // [n] -1: not expanded
+    int32_t* neighbour;                          // [n][24] or null
+};
+
+
 void launch_half_resize(const uint8_t* src, int w, int h, uint8_t* dst, hipStream_t st);
 // level-0 radial undistortion (kernel_undistort.hip): dst [h][w][3] u8, src read only; xy [h][w][2] source points
 void launch_undistort(const uint8_t* src, int w, int h, float f, float k1, uint8_t* dst, hipStream_t st);
@@ -56,6 +84,12 @@ void launch_depth_ops_apply(const DevScene& sc, const DevDepthView* depths, floa
 // the cells a batch's gates read and setDepths would write (the scheduler's conflict test; layouts at the kernel)
 void launch_depth_footprints(const DevScene& sc, const DevDepthView* depths, const DevBatch& b, int32_t* wr, int32_t* fr, int32_t* at,
                              int32_t* vb, hipStream_t st);
+
+// CellProcessor::regularize (kernel_regularize.hip): leaf keys + checks + hash table (hdr[0]: error bits, hdr[1]: deepest leaf, hdr[2]: 22 - shallowest), then
+// one launch over the cells
+void launch_regularize_leaves(const RegTree& t, int n_cells, int n_views, const int32_t* ref, int ref_stride, const int32_t* n_images,
+                              const uint8_t* expanded, int32_t* hdr, hipStream_t st);
+void launch_regularize(const DevScene& sc, const RegTree& t, const RegCells& cl, int min_depth, int max_depth, hipStream_t st);
 
 // refined-patch records of the multi-GPU exchange (include/hpmvs_amd.h: hpmvs_record, 192 bytes)
 void launch_pack_records(const DevBatch& b, void* records, hipStream_t st);

@@ -211,25 +211,69 @@ def branch_level(scene: api.Scene, parents: api.Batch, cell_center, cell_width, 
     commute with the minimum, so the order is part of the result.  `final_level[i]`: nodeLevel(leaf i) >= PATCH_FINAL_MINLEVEL
     (the scheduler's knowledge): such a leaf keeps its patch when no child survived (:265-266).  The tree operations (split,
     the children's leaves, the queue) stay with the caller; the result names what to do.  Equals the sequential loop's
-    (`orc_branch_round`): children, split decisions, every depth map (tests/test_gpu_branch_level.py)."""
+    (`orc_branch_round`): children, split decisions, every depth map (tests/test_gpu_branch_level.py).
+    settle_level with no leaf above the removal threshold."""
+    r = settle_level(scene, parents, cell_center, cell_width, np.zeros(parents.n, np.float32), final_level, options)
+    return BranchResult(r.candidates, r.support, r.split, r.children)
+
+
+REMOVE_FLATNESS = 2.4   # processCell (CellProcessor.cpp:409): flatness_ > 2.4 removes the patch
+
+
+def child_cell(center, width, idx):
+    """Cell(parent, idx) (doctree.cpp:30-36): width_ = parent width / 2.0, c_[k] = parent c_[k] +- width_ / 2.0, computed in
+    double and stored as float."""
+    w = np.float32(float(width) / 2.0)
+    c = np.array([float(center[k]) + (1.0 if (idx >> k) & 1 else -1.0) * float(w) / 2.0 for k in range(3)], dtype=np.float32)
+    return c, w
+
+
+def octant(center, p) -> int:
+    """Branch::at's child index (doctree.h:250-255): bit k set where p[k] > c_[k]."""
+    return (int(np.float32(p[2]) > np.float32(center[2])) << 2) | (int(np.float32(p[1]) > np.float32(center[1])) << 1) | \
+        int(np.float32(p[0]) > np.float32(center[0]))
+
+
+@dataclass
+class SettleResult:
+    candidates: api.Batch          # the 4 n branch children (stage 20: not built / not refined, removed leaves included)
+    support: np.ndarray            # Scene::getLevelSupport of every leaf's patch
+    removed: np.ndarray            # [n] 1: flatness_ > 2.4, the patch was removed (its depths taken back, the leaf emptied)
+    split: np.ndarray              # [n] 1: the leaf was split (its patch's depths taken back, the children's entered)
+    children: np.ndarray           # [n, 4] bool: the children that go into the new leaves
+    child_octant: np.ndarray       # [n, 4] the octant of the split leaf each child goes into (-1: not a child)
+    octant_center: np.ndarray      # [n, 8, 3] Cell::c_ of the split leaf's eight children
+
+
+def settle_level(scene: api.Scene, parents: api.Batch, cell_center, cell_width, flatness, final_level, options=None) -> SettleResult:
+    """processCell's decision for expanded leaves with flatness_ >= 0 (reference CellProcessor.cpp:409-419), in the scheduler's
+    order: flatness_ > 2.4 removes the patch (Scene::setDepths(p, true), the leaf emptied), anything else goes to
+    CellProcessor::branch.  ONE hpmvs_level_support_batch and ONE hpmvs_expand_batch (the removed leaves' children are skipped),
+    then ONE hpmvs_depth_ops_batch in queue order that interleaves the removals' subtractions with the branches' subtractions
+    and additions: subtracting a depth does not commute with other depth updates.  The tree operations stay with the caller:
+    the result says per leaf removed / split and which child goes into which child leaf."""
     o = options or api.default_options()
     n = parents.n
     cc = np.ascontiguousarray(cell_center, dtype=np.float32).reshape(n, 3)
     cw = np.ascontiguousarray(cell_width, dtype=np.float32).reshape(n)
     final = np.ascontiguousarray(final_level).astype(bool).reshape(n)
+    fl = np.ascontiguousarray(flatness, dtype=np.float32).reshape(n)
+    removed = fl.astype(np.float64) > REMOVE_FLATNESS    # float > double, as the reference compares
     support = api.level_support_batch(scene, parents, int(o.MINLEVEL))
-    skip = np.repeat(support < 1, 4).astype(np.uint8)   # an exhausted leaf builds nothing
+    skip = np.repeat((support < 1) | removed, 4).astype(np.uint8)   # an exhausted or removed leaf builds nothing
     out = api.expand_batch(scene, api.EXPAND_BRANCH, parents, cc, cw, skip, options=o)
     children = ((out.stage == 0) & (skip == 0)).reshape(n, 4)
-    split = (support >= 1) & ~(final & (children.sum(axis=1) == 0))
-    # the map updates in the reference's order: leaf by leaf, the old patch out, the children in
+    split = ~removed & (support >= 1) & ~(final & (children.sum(axis=1) == 0))
+    # the map updates in the reference's order: leaf by leaf, a removed patch out, or the old patch out and the children in
     M = max(parents.max_images, out.max_images)
     widen = lambda a: np.pad(a, ((0, 0), (0, M - a.shape[1])), constant_values=-1)
     rows_c, rows_n, rows_s, rows_m, rows_i, sub = [], [], [], [], [], []
     pimg, cimg = widen(parents.images), widen(out.images)
-    for i in np.nonzero(split)[0]:
+    for i in np.nonzero(split | removed)[0]:
         rows_c.append(parents.center[i]); rows_n.append(parents.normal[i]); rows_s.append(parents.scale[i])
         rows_m.append(parents.n_images[i]); rows_i.append(pimg[i]); sub.append(1)
+        if removed[i]:
+            continue
         for k in np.nonzero(children[i])[0]:
             t = 4 * i + k
             rows_c.append(out.center[t]); rows_n.append(out.normal[t]); rows_s.append(out.scale[t])
@@ -238,4 +282,114 @@ def branch_level(scene: api.Scene, parents: api.Batch, cell_center, cell_width, 
         ops = api.Batch(np.array(rows_c), np.array(rows_n), np.array(rows_s), np.array(rows_m), np.array(rows_i))
         ops.ok[:] = 1
         api.depth_ops_batch(scene, ops, np.array(sub, np.uint8))
-    return BranchResult(out, support, split.astype(np.uint8), children)
+    child_octant = np.full((n, 4), -1, np.int32)
+    octant_center = np.zeros((n, 8, 3), np.float32)
+    for i in np.nonzero(split)[0]:
+        for idx in range(8):
+            octant_center[i, idx] = child_cell(cc[i], cw[i], idx)[0]
+        for k in np.nonzero(children[i])[0]:
+            child_octant[i, k] = octant(cc[i], out.center[4 * i + k])
+    return SettleResult(out, support, removed.astype(np.uint8), split.astype(np.uint8), children, child_octant, octant_center)
+
+
+@dataclass
+class OctreeSnapshot:
+    """The scheduler's octree as hpmvs_regularize_batch reads it: the root Branch and the nonempty leaves, each valid at queue
+    positions born < q < died (include/hpmvs_amd.h: hpmvs_leaf_table)."""
+    root_center: np.ndarray        # [3] Cell::c_ of the root Branch (a subtree's root when the model is split)
+    root_width: float
+    cell_center: np.ndarray        # [L, 3] Leaf::c_
+    cell_width: np.ndarray         # [L]
+    patch_center: np.ndarray       # [L, 3] data[0]->center_
+    born: np.ndarray = None        # [L] (default -1)
+    died: np.ndarray = None        # [L] (default INT32_MAX)
+
+    def __post_init__(self):
+        self.cell_center = np.ascontiguousarray(self.cell_center, dtype=np.float32).reshape(-1, 3)
+        L = len(self.cell_center)
+        self.cell_width = np.ascontiguousarray(self.cell_width, dtype=np.float32).reshape(L)
+        self.patch_center = np.ascontiguousarray(np.asarray(self.patch_center, dtype=np.float32)[:, :3]).reshape(L, 3)
+        self.born = np.full(L, -1, np.int32) if self.born is None else np.ascontiguousarray(self.born, dtype=np.int32).reshape(L)
+        self.died = np.full(L, api.INT32_MAX, np.int32) if self.died is None else np.ascontiguousarray(self.died, dtype=np.int32).reshape(L)
+
+    @property
+    def n(self):
+        return len(self.cell_width)
+
+
+def regularize_level(scene: api.Scene, cells: api.Batch, cell_width, position, expanded, snapshot: OctreeSnapshot, flatness=None,
+                     neighbours: bool = False):
+    """CellProcessor::regularize (reference CellProcessor.cpp:309-367) for the cells of a level as ONE hpmvs_regularize_batch:
+    cell i sees the tree as it stands at its queue position position[i].  Returns (flatness, n_neighbours, neighbour_leaf)."""
+    t = snapshot
+    return api.regularize_batch(scene, cells, cell_width, position, expanded, t.root_center, t.root_width, t.cell_center,
+                                t.cell_width, t.patch_center, t.born, t.died, flatness=flatness, neighbours=neighbours)
+
+
+@dataclass
+class ProcessResult:
+    flatness: np.ndarray           # [n] flatness_ after the sweep (regularized cells updated, the others as given)
+    n_neighbours: np.ndarray       # [n] neighbour leaves of the regularized cells (-1: not expanded, -2: settled)
+    neighbour_leaf: np.ndarray     # [n, 24] their snapshot indices (None unless asked for)
+    settled: np.ndarray            # indices of the cells settle_level decided (flatness_ >= 0)
+    settle: SettleResult           # its result, row j for cell settled[j]
+    snapshot: OctreeSnapshot       # the versioned tree of the sweep: the split children's leaves appended, died / born set
+    child_leaf: np.ndarray         # [len(settled), 4] snapshot index of the leaf each child went into (-1: none)
+
+
+def process_level(scene: api.Scene, cells: api.Batch, cell_leaf, flatness, expanded, snapshot: OctreeSnapshot, final_level,
+                  options=None, neighbours: bool = False) -> ProcessResult:
+    """One sweep of processCell over cells of mixed flatness (priority L*10 + 1 / + 2, CellProcessor.cpp:390-419), in the
+    scheduler's order (queue position = index): cell_leaf[i] is the snapshot index of cell i's leaf.  (1) settle_level on the
+    cells with flatness_ >= 0, (2) their removals and splits become died / born entries of the versioned tree, (3)
+    regularize_level on the cells with flatness_ < 0 against it.  regularize only reads the tree and settle does not read
+    flatness, so one pass of each gives the sequential loop's result."""
+    n = cells.n
+    fl = np.ascontiguousarray(flatness, dtype=np.float32).reshape(n).copy()
+    leaf = np.ascontiguousarray(cell_leaf, dtype=np.int64).reshape(n)
+    final = np.ascontiguousarray(final_level).astype(bool).reshape(n)
+    exp = np.ascontiguousarray(expanded).astype(np.uint8).reshape(n)
+    # processCell extends an unexpanded cell instead (:386-392), and one leaf changes at most once per sweep (died / born)
+    if not exp.all():
+        raise ValueError("process_level: every cell must be expanded (an unexpanded one goes to extend_level)")
+    if len(np.unique(leaf)) != n or (n and (leaf.min() < 0 or leaf.max() >= snapshot.n)):
+        raise ValueError("process_level: every cell must own a distinct leaf of the snapshot")
+    reg = fl < 0
+    settled = np.nonzero(~reg)[0]                   # (NaN is not < 0: processCell settles it)
+    sub = lambda b, idx: api.Batch(b.center[idx], b.normal[idx], b.scale[idx], b.n_images[idx], b.images[idx])
+    t = snapshot
+    S = settle_level(scene, sub(cells, settled), t.cell_center[leaf[settled]], t.cell_width[leaf[settled]], fl[settled],
+                     final[settled], options)
+    cc, cw, pc = [t.cell_center], [t.cell_width], [t.patch_center]
+    born, died = [t.born], [t.died.copy()]
+    child_leaf = np.full((len(settled), 4), -1, np.int64)
+    L = t.n
+    for j, i in enumerate(settled):
+        if S.removed[j] or S.split[j]:
+            died[0][leaf[i]] = i
+        if not S.split[j]:
+            continue
+        w = np.float32(float(t.cell_width[leaf[i]]) / 2.0)
+        new = {}
+        for k in range(4):                          # data[0] of a child leaf: its first child (branch pushes in k order)
+            o_ = int(S.child_octant[j, k])
+            if o_ < 0:
+                continue
+            if o_ not in new:
+                new[o_] = L
+                cc.append(S.octant_center[j, o_][None]); cw.append(np.array([w], np.float32))
+                pc.append(S.candidates.center[4 * j + k, :3][None])
+                born.append(np.array([i], np.int32)); died.append(np.array([api.INT32_MAX], np.int32))
+                L += 1
+            child_leaf[j, k] = new[o_]
+    snap = OctreeSnapshot(t.root_center, t.root_width, np.concatenate(cc), np.concatenate(cw), np.concatenate(pc),
+                          np.concatenate(born), np.concatenate(died))
+    nn = np.full(n, -2, np.int32)
+    nb = np.full((n, api.REGULARIZE_PROBES), -1, np.int32) if neighbours else None
+    ri = np.nonzero(reg)[0]
+    if len(ri):
+        f_, n_, b_ = regularize_level(scene, sub(cells, ri), snap.cell_width[leaf[ri]], ri, exp[ri], snap, fl[ri], neighbours)
+        fl[ri] = f_; nn[ri] = n_
+        if neighbours:
+            nb[ri] = b_
+    return ProcessResult(fl, nn, nb, settled, S, snap, child_leaf)

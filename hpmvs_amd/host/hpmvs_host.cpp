@@ -1214,6 +1214,147 @@ bool PatchOptimizer::branchLevel(const mo3d::Patch3d* const* parents, const Cell
     return ops.empty() || scene_p->setDepths(ops.data(), ops.size(), sub.data());
 }
 
+bool PatchOptimizer::regularizeLevel(mo3d::Patch3d* const* cells, size_t n, const float* cellWidth, const int32_t* position,
+                                     const LeafTable& t, std::vector<int>* nNeighbours) {
+    if (nNeighbours) nNeighbours->assign(n, -1);
+    if (n == 0) return true;
+    hpmvs_scene* dev = scene_p->deviceScene();
+    if (!dev) return false;
+    const size_t L = t.size();
+    if (t.center.size() != 3 * L || t.patch.size() != 3 * L || t.born.size() != L || t.died.size() != L) {
+        std::cerr << "hpmvs: regularizeLevel: inconsistent leaf table" << std::endl;
+        return false;
+    }
+    HostBatch hb(reinterpret_cast<const Patch3d* const*>(cells), n);
+    std::vector<float> cw(cellWidth, cellWidth + n), fl(n);
+    std::vector<int32_t> pos(position, position + n), nn(n);
+    std::vector<uint8_t> exp(n);
+    for (size_t i = 0; i < n; i++) { fl[i] = cells[i]->flatness_; exp[i] = cells[i]->expanded_ ? 1 : 0; }
+    hpmvs_leaf_table lt;
+    lt.n = (int32_t)L;
+    for (int k = 0; k < 3; k++) lt.root_center[k] = t.rootCenter[k];
+    lt.root_width = t.rootWidth;
+    lt.cell_center = t.center.data(); lt.cell_width = t.width.data(); lt.patch_center = t.patch.data();
+    lt.born = t.born.data(); lt.died = t.died.data();
+    if (hpmvs_regularize_batch(dev, &hb.b, cw.data(), pos.data(), exp.data(), &lt, fl.data(), nn.data(), nullptr, 0, nullptr) != HPMVS_OK) {
+        std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl;
+        return false;
+    }
+    for (size_t i = 0; i < n; i++) {
+        cells[i]->flatness_ = fl[i];
+        cells[i]->priorityReduction_ = 0;   // processCell, CellProcessor.cpp:399
+    }
+    if (nNeighbours) nNeighbours->assign(nn.begin(), nn.end());
+    return true;
+}
+
+// Cell(parent, idx) (doctree.cpp:30-36): double arithmetic, float storage; Branch::at's octant (doctree.h:250-255)
+static int octant_of(const Eigen::Vector3f& c, const Eigen::Vector4f& p) {
+    return ((p[2] > c[2]) << 2) | ((p[1] > c[1]) << 1) | (p[0] > c[0]);
+}
+static Eigen::Vector3f child_center(const Eigen::Vector3f& c, float w, int idx) {
+    const float cw = (float)(w / 2.0);
+    Eigen::Vector3f r;
+    for (int k = 0; k < 3; k++) r[k] = (float)(c[k] + ((idx >> k) & 1 ? 1.0 : -1.0) * cw / 2.0);
+    return r;
+}
+
+bool PatchOptimizer::settleLevel(const mo3d::Patch3d* const* parents, const CellRef* cells, size_t n, const uint8_t* finalLevel,
+                                 SettleResult& R) {
+    R = SettleResult();
+    if (n == 0) return true;
+    R.removed.assign(n, 0);
+    for (size_t i = 0; i < n; i++) R.removed[i] = parents[i]->flatness_ > 2.4 ? 1 : 0;   // CellProcessor.cpp:409 (float > double)
+    if (!scene_p->levelSupport(parents, n, options_p->MINLEVEL, R.support)) return false;
+    std::vector<uint8_t> skip(4 * n, 0), acc;
+    for (size_t i = 0; i < n; i++) if (R.support[i] < 1 || R.removed[i]) for (int k = 0; k < 4; k++) skip[4 * i + k] = 1;
+    expandBatch(BRANCH, parents, cells, n, skip.data(), R.candidates, acc);
+    if (R.candidates.size() != 4 * n) return false;
+    R.child.assign(4 * n, 0);
+    R.childOctant.assign(4 * n, -1);
+    R.split.assign(n, 0);
+    std::vector<const Patch3d*> ops;
+    std::vector<uint8_t> sub;
+    for (size_t i = 0; i < n; i++) {
+        int children = 0;
+        for (int k = 0; k < 4; k++) { R.child[4 * i + k] = (acc[4 * i + k] && !skip[4 * i + k]) ? 1 : 0; children += R.child[4 * i + k]; }
+        if (R.removed[i]) { ops.push_back(parents[i]); sub.push_back(1); continue; }   // setDepths(p, true) (:410)
+        if (R.support[i] < 1 || (finalLevel && finalLevel[i] && children == 0)) continue;
+        R.split[i] = 1;
+        ops.push_back(parents[i]); sub.push_back(1);
+        for (int k = 0; k < 4; k++)
+            if (R.child[4 * i + k]) {
+                ops.push_back(&R.candidates[4 * i + k]); sub.push_back(0);
+                R.childOctant[4 * i + k] = octant_of(cells[i].c, R.candidates[4 * i + k].center_);
+            }
+    }
+    return ops.empty() || scene_p->setDepths(ops.data(), ops.size(), sub.data());
+}
+
+bool PatchOptimizer::processLevel(mo3d::Patch3d* const* cells, const int32_t* cellLeaf, size_t n, const uint8_t* finalLevel,
+                                  const LeafTable& table, ProcessResult& R) {
+    R = ProcessResult();
+    R.table = table;
+    R.nNeighbours.assign(n, -2);
+    if (n == 0) return true;
+    std::vector<uint8_t> seen(table.size(), 0);
+    for (size_t i = 0; i < n; i++) {
+        const int32_t l = cellLeaf[i];
+        if (l < 0 || (size_t)l >= table.size() || seen[l] || !cells[i]->expanded_) {
+            std::cerr << "hpmvs: processLevel: every cell must be expanded and own a distinct leaf of the table" << std::endl;
+            return false;
+        }
+        seen[l] = 1;
+    }
+    std::vector<const Patch3d*> sp;
+    std::vector<CellRef> sc;
+    std::vector<uint8_t> sf;
+    std::vector<size_t> reg;
+    for (size_t i = 0; i < n; i++) {
+        if (cells[i]->flatness_ < 0) { reg.push_back(i); continue; }   // (NaN is not < 0: processCell settles it)
+        const int32_t l = cellLeaf[i];
+        R.settled.push_back(i);
+        sp.push_back(cells[i]);
+        sc.push_back(CellRef{Eigen::Vector3f(table.center[3 * l], table.center[3 * l + 1], table.center[3 * l + 2]), table.width[l]});
+        sf.push_back(finalLevel ? finalLevel[i] : 0);
+    }
+    if (!settleLevel(sp.data(), sc.data(), sp.size(), sf.data(), R.settle)) return false;
+    LeafTable& T = R.table;
+    R.childLeaf.assign(4 * R.settled.size(), -1);
+    for (size_t j = 0; j < R.settled.size(); j++) {
+        const size_t i = R.settled[j];
+        const int32_t l = cellLeaf[i];
+        if (R.settle.removed[j] || R.settle.split[j]) T.died[l] = (int32_t)i;
+        if (!R.settle.split[j]) continue;
+        const float w = (float)(table.width[l] / 2.0);
+        int made[8];
+        for (int o = 0; o < 8; o++) made[o] = -1;
+        for (int k = 0; k < 4; k++) {   // data[0] of a child leaf: its first child (branch pushes in k order)
+            const int o = R.settle.childOctant[4 * j + k];
+            if (o < 0) continue;
+            if (made[o] < 0) {
+                made[o] = (int)T.size();
+                const Eigen::Vector3f c = child_center(sc[j].c, sc[j].width, o);
+                const Patch3d& ch = R.settle.candidates[4 * j + k];
+                for (int d = 0; d < 3; d++) { T.center.push_back(c[d]); T.patch.push_back(ch.center_[d]); }
+                T.width.push_back(w);
+                T.born.push_back((int32_t)i);
+                T.died.push_back(INT32_MAX);
+            }
+            R.childLeaf[4 * j + k] = made[o];
+        }
+    }
+    if (reg.empty()) return true;
+    std::vector<Patch3d*> rp;
+    std::vector<float> rw;
+    std::vector<int32_t> rq;
+    for (size_t i : reg) { rp.push_back(cells[i]); rw.push_back(table.width[cellLeaf[i]]); rq.push_back((int32_t)i); }
+    std::vector<int> nn;
+    if (!regularizeLevel(rp.data(), rp.size(), rw.data(), rq.data(), T, &nn)) return false;
+    for (size_t j = 0; j < reg.size(); j++) R.nNeighbours[reg[j]] = nn[j];
+    return true;
+}
+
 // The centres of a level's candidates BEFORE optimize (CellProcessor.cpp:103-116: the leaf look-up of :118-122 uses them): the device's
 // own construction with every candidate skipped, read back without building 6 n Patch3d objects, in rows just wide enough for the
 // parents' lists (nothing is refined, no list grows).  centers: 3 floats per candidate.

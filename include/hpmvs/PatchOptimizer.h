@@ -67,6 +67,45 @@ public:
         std::vector<uint8_t> split;              // per leaf: split (its patch's depths are out of the maps, the children's in)
     };
     bool branchLevel(const mo3d::Patch3d* const* parents, const CellRef* cells, size_t n, const uint8_t* finalLevel, BranchResult& out);
+    // Priorities L*10+1 / +2 of CellProcessor::processCell (reference src/hpmvs/CellProcessor.cpp:369-420) as batched device calls, the
+    // C++ form of hpmvs_amd.frontier.regularize_level / settle_level / process_level (same calls, same results).  The octree stays the
+    // scheduler's: it passes a versioned snapshot of its nonempty leaves (include/hpmvs_amd.h, hpmvs_leaf_table): leaf j exists at queue
+    // positions born[j] < q < died[j].
+    struct LeafTable {
+        Eigen::Vector3f rootCenter;          // Cell::c_ of the Branch the CellProcessor walks (a subtree's root when the model is split)
+        float rootWidth = 0.0f;
+        std::vector<float> center, width, patch;   // 3 / 1 / 3 floats per leaf: Leaf::c_, width_, data[0]->center_
+        std::vector<int32_t> born, died;           // 1 per leaf (-1 / INT32_MAX: present for the whole sweep)
+        size_t size() const { return width.size(); }
+    };
+    // CellProcessor::regularize (:309-367) for cells[i] at queue position position[i] against `table`: writes flatness_ (an unexpanded
+    // cell keeps it) and sets priorityReduction_ = 0 (:399).  cellWidth[i]: its leaf's width_.  nNeighbours (optional): the distinct
+    // nonempty leaves found, -1 for an unexpanded cell.
+    bool regularizeLevel(mo3d::Patch3d* const* cells, size_t n, const float* cellWidth, const int32_t* position, const LeafTable& table,
+                         std::vector<int>* nNeighbours = nullptr);
+    // processCell's decision for expanded leaves with flatness_ >= 0 (:409-419), in the scheduler's order: flatness_ > 2.4 removes the
+    // patch (its depths taken back), anything else branches the leaf (branchLevel's rule).  Removals and branches share ONE ordered
+    // Scene::setDepths call.  childOctant[4 i + k]: the octant (Branch::at's index) of leaf i that child k goes into, -1 if none.
+    struct SettleResult {
+        std::vector<mo3d::Patch3d> candidates;   // 4 per leaf
+        std::vector<uint8_t> child;              // 4 per leaf
+        std::vector<int> childOctant;            // 4 per leaf
+        std::vector<int> support;
+        std::vector<uint8_t> removed, split;
+    };
+    bool settleLevel(const mo3d::Patch3d* const* parents, const CellRef* cells, size_t n, const uint8_t* finalLevel, SettleResult& out);
+    // One sweep of mixed cells in queue order (position = index): settleLevel on the cells with flatness_ >= 0, their removals and splits
+    // as died / born entries of the table, then regularizeLevel on the cells with flatness_ < 0 against it.  Every cell must be expanded
+    // and own its leaf (cellLeaf[i]: index into `table`, distinct).  out.table: the sweep's versioned table (split children appended).
+    struct ProcessResult {
+        std::vector<size_t> settled;             // the cells settleLevel decided, in order
+        SettleResult settle;                     // row j for cell settled[j]
+        LeafTable table;
+        std::vector<int> childLeaf;              // 4 per settled cell: the table index of the child's leaf (-1: none)
+        std::vector<int> nNeighbours;            // per cell; -2 for settled cells
+    };
+    bool processLevel(mo3d::Patch3d* const* cells, const int32_t* cellLeaf, size_t n, const uint8_t* finalLevel, const LeafTable& table,
+                      ProcessResult& out);
     // diagnostics of the last optimize()/optimizeBatch() call that the reference computes and drops
     // (final mean robust INCC f*, PatchOptimizer.cpp:365,376): one entry per patch
     const std::vector<double>& lastObjective() const { return lastF_; }

@@ -29,6 +29,7 @@
  *   hpmvs_init_patches_batch <- the seed loop of Scene::initPatches, src/hpmvs/Scene.cpp:112-178.
  *   hpmvs_expand_batch       <- the candidate loops of CellProcessor::extend / ::branch,
  *                               src/hpmvs/CellProcessor.cpp:84-142 and :210-262.
+ *   hpmvs_regularize_batch   <- CellProcessor::regularize, src/hpmvs/CellProcessor.cpp:309-367.
  *   hpmvs_camera_from_nvm    <- Camera::init, src/hpmvs/Camera.cpp:34-81.
  */
 #ifndef HPMVS_AMD_H
@@ -259,6 +260,40 @@ int hpmvs_level_support_batch(const hpmvs_scene *s, const hpmvs_patch_batch *b, 
  *   view_block [n][n_views][3]     every view v: 1 if viewBlockTest examines it, ix0, iy0 of its 3x3 block (read the same way) */
 int hpmvs_depth_footprints_batch(const hpmvs_scene *s, const hpmvs_patch_batch *b, int32_t *writes, int32_t *frees,
                                  int32_t *attached, int32_t *view_block, int on_device, void *stream);
+
+/* ---- CellProcessor::regularize for a priority level (src/hpmvs/CellProcessor.cpp:309-367, processCell :369-420) ----------------
+ * The octree stays the scheduler's.  For each call it passes a VERSIONED snapshot of the nonempty leaves: a leaf is part of the
+ * tree at queue positions born < q < died (leaves present when the sweep starts: born = -1, died = INT32_MAX; a leaf the sweep
+ * removes or splits at position s: died = s; a leaf that split creates: born = s).  root_* is the Branch the CellProcessor walks
+ * (a subtree's root when the model is split).  Every leaf's path is re-derived from the root with the reference's recurrences
+ * (Cell(parent, idx), doctree.cpp:30-36; Branch::at, doctree.h:250-255); a leaf whose recomputed centre is not bit-equal to
+ * cell_center, or that lies deeper than HPMVS_MAX_TREE_DEPTH levels, makes the call fail with HPMVS_ERR_ARG before any output
+ * is written. */
+#define HPMVS_MAX_TREE_DEPTH 21
+#define HPMVS_REGULARIZE_PROBES 24
+typedef struct {
+    int32_t n;                  /* nonempty leaves */
+    float root_center[3];       /* Cell::c_ of the root Branch */
+    float root_width;           /* its width_ */
+    const float *cell_center;   /* [n][3] Leaf::c_ */
+    const float *cell_width;    /* [n]    Leaf::width_ */
+    const float *patch_center;  /* [n][3] data[0]->center_ (x, y, z) */
+    const int32_t *born;        /* [n] */
+    const int32_t *died;        /* [n] */
+} hpmvs_leaf_table;
+/* regularize(cell) for every cell of `cells` (center, normal, n_images, images[.][0] are read): cell_width[n] = its leaf's width_,
+ * position[n] = its queue position q, expanded[n] = expanded_.  flatness[n] is in/out: an unexpanded cell keeps its value
+ * (regularize returns at once) and gets n_neighbours = -1; otherwise flatness = 2.6 (no neighbour leaf), 2.5 (fewer than 4) or
+ * the RMS plane distance / width, and n_neighbours = the distinct nonempty leaves the 24 probes found at q (the cell's own leaf
+ * counts when a probe lands in it).  neighbour_leaf (nullable): [n][24] those leaves' table indices in first-probe order
+ * (yy outer, xx inner), -1 padded.  The RMS sum runs in that order; the reference sums in std::set<Leaf*> (heap-address)
+ * order, so flatness may differ from a given reference run by the rounding of at most 23 float additions.
+ * HPMVS_ERR_ARG also for an expanded cell whose reference image is not a view of the scene.  Host or device pointers (leaf
+ * table included) as for hpmvs_optimize_batch; the call is host-synchronous once (leaf checks) and then only enqueues when
+ * on_device != 0. */
+int hpmvs_regularize_batch(const hpmvs_scene *s, const hpmvs_patch_batch *cells, const float *cell_width, const int32_t *position,
+                           const uint8_t *expanded, const hpmvs_leaf_table *leaves, float *flatness, int32_t *n_neighbours,
+                           int32_t *neighbour_leaf, int on_device, void *stream);
 
 /* Host-pointer calls and pinned memory.  An array of a host-pointer call (on_device = 0) that lies in pinned host memory
  * mapped into the GPU's address space -- hipHostMalloc / hipHostRegister, torch's pin_memory(), hpmvs_host_alloc below --

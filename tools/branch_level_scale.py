@@ -3,6 +3,13 @@ batched refinement of the 4 n children, one ordered depth-ops call) against the 
 reference CellProcessor.cpp:210-307), every child, split decision and map cell compared.
 
     python tools/branch_level_scale.py [views w h seeds leaves [start_level]]      (default: 12 1920 1080 100000 16384 3)
+
+The `regularize` leg times CellProcessor::regularize (CellProcessor.cpp:309-367) for one level: hpmvs_regularize_batch (host
+pointers, wall time of the call and of the kernels by HIP events via torch) against the host restatement in tools/regularize_host.cpp
+on 1 and 16 threads, on the same cells and leaf table; the kernel's own time comes from a rocprofv3 --kernel-trace --stats run of
+this leg.  Prints one JSON line.
+
+    python tools/branch_level_scale.py regularize [views w h seeds]                (default: 50 3840 2160 200000)
 """
 import json
 import os
@@ -16,6 +23,85 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from hpmvs_amd import api, frontier, synth  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
+
+
+
+def regularize_leg(argv):
+    import ctypes as C
+    import subprocess
+    import tempfile
+    V, W_, H_, NS = (int(a) for a in argv[:4]) if len(argv) >= 4 else (50, 3840, 2160, 200000)
+    dev = torch.device("cuda", 0)
+    scene = synth.make_scene(V, W_, H_, n_waves=24, device=dev)
+    g = api.Scene(scene)
+    seeds = synth.make_seeds(scene, NS, start_level=4, max_images=min(V, api.MAX_IMAGES))
+    b0 = api.Batch.from_seeds(seeds)
+    api.optimize_batch(g, b0)
+    ok = np.nonzero(b0.ok)[0]
+    P = b0.center[ok, :3].astype(np.float32)
+    lo, hi = P.min(axis=0), P.max(axis=0)
+    rc = ((lo + hi) / 2).astype(np.float32)
+    rw = np.float32(2.0 ** np.ceil(np.log2(float((hi - lo).max()) * 1.1)))
+    # leaves on one level of the tree: descend every patch with Cell(parent, idx) / Branch::at until most patches own a leaf
+    c = np.repeat(rc[None], len(ok), axis=0)
+    w = np.float32(rw)
+    key = np.ones(len(ok), np.uint64)
+    depth = 0
+    while depth < 21 and (depth < 2 or len(np.unique(key)) < 0.8 * len(ok)):
+        bit = P > c
+        cw = np.float32(float(w) / 2.0)
+        c = (c.astype(np.float64) + np.where(bit, 1.0, -1.0) * float(cw) / 2.0).astype(np.float32)
+        w = cw
+        key = (key << np.uint64(3)) | (bit[:, 0] | (bit[:, 1].astype(np.uint64) << np.uint64(1)) | (bit[:, 2].astype(np.uint64) << np.uint64(2))).astype(np.uint64)
+        depth += 1
+    _, first = np.unique(key, return_index=True)          # data[0] of a leaf: its first patch
+    first.sort()
+    L = len(first)
+    lc, lw, lp = c[first], np.full(L, w, np.float32), P[first]
+    sel = ok[first]
+    cells_all = api.Batch(b0.center[sel], b0.normal[sel], b0.scale[sel], b0.n_images[sel], b0.images[sel])
+    xax = np.array([api.camera_from_nvm(v.f, v.q, v.c, v.width, v.height, 5).xaxis[:] for v in scene.views], np.float32)
+    src = os.path.join(ROOT, "tools", "regularize_host.cpp")
+    so = os.path.join(tempfile.mkdtemp(), "libregularize_host.so")
+    subprocess.run(["g++", "-O2", "-std=c++14", "-fopenmp", "-ffp-contract=off", "-shared", "-fPIC", src, "-o", so], check=True)
+    H = C.CDLL(so)
+    H.regularize_host.restype = C.c_double
+    H.regularize_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    root = np.array([*rc, rw], np.float32)
+    out = {"scene": f"{V} x {W_}x{H_}", "build": api.lib().hpmvs_build_id().decode(), "leaves": int(L), "leaf_depth": depth, "runs": []}
+    for n in (16384, L):
+        cells = api.Batch(cells_all.center[:n], cells_all.normal[:n], cells_all.scale[:n], cells_all.n_images[:n], cells_all.images[:n])
+        ones, zeros = np.ones(n, np.uint8), np.zeros(n, np.int32)
+        api.regularize_batch(g, cells, lw[:n], zeros, ones, rc, rw, lc, lw, lp)          # warm-up
+        walls, evs = [], []
+        for _ in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter(); e0.record()
+            fl, nn, _ = api.regularize_batch(g, cells, lw[:n], zeros, ones, rc, rw, lc, lw, lp, neighbours=False)
+            e1.record(); torch.cuda.synchronize()
+            walls.append(time.perf_counter() - t0); evs.append(e0.elapsed_time(e1) / 1e3)
+        xa = np.ascontiguousarray(xax[cells.images[:, 0]])
+        host = {}
+        for T in (1, 16):
+            hf, hn = np.zeros(n, np.float32), np.zeros(n, np.int32)
+            secs = H.regularize_host(root.ctypes.data, L, lc.ctypes.data, lw.ctypes.data, lp.ctypes.data, n, cells.center.ctypes.data,
+                                     cells.normal.ctypes.data, xa.ctypes.data, lw[:n].ctypes.data, T, hf.ctypes.data, hn.ctypes.data)
+            host[T] = secs
+        rel = np.abs(hf.astype(np.float64) - fl) / np.maximum(np.abs(fl.astype(np.float64)), 1e-30)
+        out["runs"].append({"cells": n, "gpu_call_s_median": float(np.median(walls)), "gpu_call_event_s_median": float(np.median(evs)),
+                            "host_1_thread_s": host[1], "host_16_threads_s": host[16],
+                            "speedup_vs_16_threads": host[16] / float(np.median(walls)),
+                            "neighbour_counts_equal": bool(np.array_equal(hn, nn)), "flatness_bit_equal": int((hf.view(np.int32) == fl.view(np.int32)).sum()),
+                            "flatness_max_rel_diff": float(rel.max())})
+    g.close()
+    print(json.dumps(out))
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "regularize":
+    regularize_leg(sys.argv[2:])
+    raise SystemExit(0)
 
 V, W_, H_, NSEEDS, NLEAVES = (int(a) for a in sys.argv[1:6]) if len(sys.argv) > 5 else (12, 1920, 1080, 100000, 16384)
 SL = int(sys.argv[6]) if len(sys.argv) > 6 else 3
