@@ -63,7 +63,7 @@ EXPORTS = [
     "hpmvs_set_depths_batch", "hpmvs_depth_gates_batch", "hpmvs_depth_footprints_batch", "hpmvs_depth_ops_batch", "hpmvs_level_support_batch",
     "hpmvs_host_alloc", "hpmvs_host_free", "hpmvs_last_staging",
     "hpmvs_undistort", "hpmvs_undistort_map", "hpmvs_scene_set_view_distorted",
-    "hpmvs_regularize_batch",
+    "hpmvs_regularize_batch", "hpmvs_filter_batch",
 ]
 
 _lib = None
@@ -125,6 +125,7 @@ def lib():
     L.hpmvs_regularize_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LeafTable),
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.hpmvs_level_support_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.hpmvs_filter_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     _lib = L
     return L
 
@@ -203,9 +204,11 @@ class Scene:
         self.h = C.c_void_p()
         self.device = device
         self.n_views = synth_scene.n_views
+        self.view_levels = []   # pyramid levels per view (Camera::getLevels)
         _chk(L.hpmvs_scene_create(self.n_views, device, C.byref(self.h)))
         for i, v in enumerate(synth_scene.views):
             cam = camera_from_nvm(v.f, v.q, v.c, v.width, v.height, synth_scene.max_level)
+            self.view_levels.append(int(cam.n_levels))
             rgb = v.rgb
             if isinstance(rgb, np.ndarray):
                 rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
@@ -499,3 +502,17 @@ def regularize_batch(scene: Scene, cells: Batch, cell_width, position, expanded,
     _chk(lib().hpmvs_regularize_batch(scene.h, C.byref(b), cw.ctypes.data, pos.ctypes.data, exp.ctypes.data, C.byref(t),
                                       fl.ctypes.data, nn.ctypes.data, None if nb is None else nb.ctypes.data, 0, None))
     return fl, nn, nb
+
+
+def filter_batch(scene: Scene, patches: Batch, cell_start):
+    """CellProcessor::filter (reference CellProcessor.cpp:43-82) for every cell (include/hpmvs_amd.h: hpmvs_filter_batch): cell c
+    holds the rows cell_start[c] .. cell_start[c + 1] - 1 of `patches`, in data order.  Returns (dist [n] float32, keep [n_cells]
+    int32: the kept row, -1 for an empty cell, -2 for a cell with no winner)."""
+    cs = np.ascontiguousarray(cell_start, dtype=np.int32).reshape(-1)
+    if len(cs) < 1:
+        raise ValueError("filter_batch: cell_start needs n_cells + 1 entries")
+    dist = np.zeros(patches.n, np.float32)
+    keep = np.zeros(len(cs) - 1, np.int32)
+    b = patches.c_struct()
+    _chk(lib().hpmvs_filter_batch(scene.h, C.byref(b), cs.ctypes.data, len(cs) - 1, dist.ctypes.data, keep.ctypes.data, 0, None))
+    return dist, keep

@@ -1837,6 +1837,70 @@ int hpmvs_regularize_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, con
     }
     return HPMVS_OK;
 }
+// CellProcessor::filter (src/hpmvs/CellProcessor.cpp:43-82) for every cell of a level (kernel_filter.hip).  The offsets are
+// validated before any output is written: on the host for host pointers, by filter_check_kernel (verdict read back) for device
+// pointers.
+int hpmvs_filter_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, const int32_t* cell_start, int n_cells, float* dist,
+                       int32_t* keep, int on_device, void* stream) {
+    if (hpmvs_device_count() <= 0) return fail(HPMVS_ERR_NODEVICE, "filter_batch: no HIP device visible");
+    if (!s || !b) return fail(HPMVS_ERR_ARG, "filter_batch: null scene / batch");
+    if (!s->committed) return fail(HPMVS_ERR_STATE, "filter_batch: scene not committed");
+    if (b->n < 0 || n_cells < 0) return fail(HPMVS_ERR_ARG, "filter_batch: negative count");
+    if (!cell_start) return fail(HPMVS_ERR_ARG, "filter_batch: cell_start missing");
+    if (b->n > 0 && (!b->center || !b->normal || !dist)) return fail(HPMVS_ERR_ARG, "filter_batch: batch arrays missing");
+    if (n_cells > 0 && !keep) return fail(HPMVS_ERR_ARG, "filter_batch: keep missing");
+    static const char* kBadOffsets = "filter_batch: cell_start must start at 0, not decrease and end at the batch's row count";
+    if (!on_device) {
+        if (cell_start[0] != 0 || cell_start[n_cells] != b->n) return fail(HPMVS_ERR_ARG, kBadOffsets);
+        for (int c = 0; c < n_cells; c++)
+            if (cell_start[c + 1] < cell_start[c]) return fail(HPMVS_ERR_ARG, kBadOffsets);
+    }
+    if (b->n == 0 && n_cells == 0 && !on_device) return HPMVS_OK;
+    int rc;
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)b->n, nc = (size_t)n_cells;
+    Staged sg;
+    sg.scene = s;
+    const float *dcen = nullptr, *dnor = nullptr;
+    const int32_t* dcs = nullptr;
+    float* ddist = nullptr;
+    int32_t* dkeep = nullptr;
+    int32_t* bad = nullptr;
+    {
+        Exclusive ex(s);  // the allocations of this call (see Exclusive)
+        if (on_device) {
+            dcen = b->center; dnor = b->normal; dcs = cell_start; ddist = dist; dkeep = keep;
+            void* p = nullptr;
+            HIPCHK(hipMalloc(&p, sizeof(int32_t))); sg.tmp.push_back(p); bad = (int32_t*)p;
+        } else {
+            float *c = nullptr, *nm = nullptr;
+            int32_t* cs = nullptr;
+            if ((rc = stage_in(sg, c, b->center, 4 * n, true))) return rc;
+            if ((rc = stage_in(sg, nm, b->normal, 4 * n, true))) return rc;
+            if ((rc = stage_in(sg, cs, cell_start, nc + 1, true))) return rc;
+            if ((rc = stage_in(sg, ddist, dist, n, false, /*need_zero=*/false))) return rc;
+            if ((rc = stage_in(sg, dkeep, keep, nc, false, /*need_zero=*/false))) return rc;
+            dcen = c; dnor = nm; dcs = cs;
+        }
+    }
+    if ((rc = stage_flush(sg, st))) return rc;
+    if (on_device) {
+        int32_t h = 0;
+        HIPCHK(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
+        launch_filter_check(dcs, n_cells, b->n, bad, st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&h, bad, sizeof(h), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (h) return fail(HPMVS_ERR_ARG, kBadOffsets);
+    }
+    launch_filter(dcen, dnor, dcs, n_cells, b->n, ddist, dkeep, st);
+    HIPCHK(hipGetLastError());
+    if (on_device) return HPMVS_OK;
+    HIPCHK(hipStreamSynchronize(st));
+    if ((rc = stage_out(dist, (const float*)ddist, n))) return rc;
+    return stage_out(keep, (const int32_t*)dkeep, nc);
+}
 int hpmvs_depth_gates_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, float margin, int abs_int,
                             int32_t* n_visible, int32_t* n_blocking, int32_t* n_free, int on_device, void* stream) {
     int rc = check_depth_batch(s, b, "depth_gates_batch");

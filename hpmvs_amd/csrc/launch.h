@@ -91,6 +91,12 @@ void launch_regularize_leaves(const RegTree& t, int n_cells, int n_views, const 
                               const uint8_t* expanded, int32_t* hdr, hipStream_t st);
 void launch_regularize(const DevScene& sc, const RegTree& t, const RegCells& cl, int min_depth, int max_depth, hipStream_t st);
 
+// CellProcessor::filter (kernel_filter.hip): bad[0] |= 1 unless cell_start[0] == 0, non-decreasing, cell_start[n_cells] == n; then
+// dist[n] per row and keep[n_cells] per cell (row of the kept patch, -1: empty cell, -2: no winner)
+void launch_filter_check(const int32_t* cell_start, int n_cells, int n, int32_t* bad, hipStream_t st);
+void launch_filter(const float* center, const float* normal, const int32_t* cell_start, int n_cells, int n, float* dist, int32_t* keep,
+                   hipStream_t st);
+
 // refined-patch records of the multi-GPU exchange (include/hpmvs_amd.h: hpmvs_record, 192 bytes)
 void launch_pack_records(const DevBatch& b, void* records, hipStream_t st);
 void launch_unpack_records(const void* records, int n, const DevBatch& b, hipStream_t st);

@@ -393,3 +393,229 @@ def process_level(scene: api.Scene, cells: api.Batch, cell_leaf, flatness, expan
         if neighbours:
             nb[ri] = b_
     return ProcessResult(fl, nn, nb, settled, S, snap, child_leaf)
+
+
+@dataclass
+class FilterResult:
+    keep: np.ndarray               # [n_cells] row of the kept patch (-1: empty cell, -2: no winner)
+    dist: np.ndarray               # [n] the reference's mean signed plane distance per row (0 in single-patch cells)
+    removed: np.ndarray            # [n] 1: a loser (its depths taken back, its images_ cleared by the caller)
+
+
+MAX_LEVELS = 8                     # HPMVS_MAX_LEVELS
+
+
+def _cell_offsets(patches: api.Batch, cell_start) -> np.ndarray:
+    cs = np.ascontiguousarray(cell_start, dtype=np.int64).reshape(-1)
+    if len(cs) < 1 or cs[0] != 0 or cs[-1] != patches.n or (np.diff(cs) < 0).any():
+        raise ValueError("cell_start must start at 0, not decrease and end at the number of patches")
+    return cs.astype(np.int32)
+
+
+def _filter(scene: api.Scene, patches: api.Batch, cell_start) -> FilterResult:
+    cs = _cell_offsets(patches, cell_start)
+    dist, keep = api.filter_batch(scene, patches, cs)
+    if (keep == -2).any():
+        raise ValueError(f"filter: cell {int(np.nonzero(keep == -2)[0][0])} has no patch whose distance is below FLT_MAX "
+                         "(the reference would keep a null pointer)")
+    removed = np.ones(patches.n, np.uint8)
+    removed[keep[keep >= 0]] = 0
+    return FilterResult(keep, dist, removed)
+
+
+def _rows(b: api.Batch, idx, width=None) -> api.Batch:
+    idx = np.asarray(idx, dtype=np.int64)
+    img = b.images[idx]
+    if width is not None and width > img.shape[1]:
+        img = np.pad(img, ((0, 0), (0, width - img.shape[1])), constant_values=-1)
+    return api.Batch(b.center[idx], b.normal[idx], b.scale[idx], b.n_images[idx], img)
+
+
+def filter_level(scene: api.Scene, patches: api.Batch, cell_start, options=None) -> FilterResult:
+    """CellProcessor::filter (reference CellProcessor.cpp:43-82) for the cells of a level, in the scheduler's order: cell c holds
+    the rows cell_start[c] .. cell_start[c + 1] - 1 of `patches` in data order.  ONE hpmvs_filter_batch, then ONE
+    hpmvs_depth_ops_batch that takes the losers' depths back in queue order (Scene::setDepths(p, true)).  The result is the
+    sequential loop's when nothing else runs between the filters; processCell's first visit, which extends each kept patch right
+    after its filter, is filter_extend_level.  Raises ValueError before the maps are touched when a cell has no winner.
+    (`options`: the signature of the other level calls; filter reads none.)"""
+    r = _filter(scene, patches, cell_start)
+    losers = np.nonzero(r.removed)[0]
+    if len(losers):
+        ops = _rows(patches, losers)
+        ops.ok[:] = 1
+        api.depth_ops_batch(scene, ops, np.ones(len(losers), np.uint8))
+    return r
+
+
+def filter_extend_level(scene: api.Scene, patches: api.Batch, cell_start, width: float, occupied: set, expanded=None,
+                        margin: float = 1.0, abs_int: int = 0, options=None, key=cell_key):
+    """processCell's first visit of a level's unexpanded leaves (reference CellProcessor.cpp:369-392), in queue order: filter
+    cell i (:377-378), then CellProcessor::extend on its kept patch.  Returns (FilterResult, LevelResult); the LevelResult is laid
+    out as extend_level's, the kept patches being the parents.
+
+    ONE hpmvs_filter_batch decides every cell (filter reads only the cell's own patches).  Then extend_level's candidate steps
+    over the kept patches -- the candidates' leaves, ONE hpmvs_expand_batch, ONE hpmvs_depth_footprints_batch over the refined
+    candidates and the losers -- and extend_level's wave walk with SUBTRACTION EVENTS: each loser is an event at its queue
+    position (after the candidates of the cells before it, before its own cell's candidates).  An event always passes and
+    occupies no leaf; its cells are those its setDepths(p, true) would write.  It is deferred when one of them is written by an
+    earlier candidate accepted or deferred in this wave, or read by an earlier deferred candidate; events never block each other
+    (subtractions commute).  Applied or deferred, its cells join `dirty` (a later candidate of the wave read its counts before
+    the subtraction); deferred, they also join `guard` (a later addition must follow the subtraction).  Each wave's accepted
+    additions and applied subtractions are ONE hpmvs_depth_ops_batch in queue order.  The result equals the sequential loop's
+    (DESIGN.md §3.9); on a level of single-patch cells it is extend_level's.
+
+    `expanded`: expanded_ per row (default 0).  ValueError before any map update for a cell with no winner, an empty cell or a
+    kept patch that is already expanded (processCell does not extend it, :380)."""
+    o = options or api.default_options()
+    MIN = int(o.MIN_IMAGES_PER_PATCH)
+    n_levels = max(scene.view_levels) if scene.view_levels else 1
+    if n_levels > MAX_LEVELS:
+        raise ValueError(f"filter_extend_level: the scene's cameras have {n_levels} pyramid levels, more than HPMVS_MAX_LEVELS")
+    cs = _cell_offsets(patches, cell_start)
+    exp = np.zeros(patches.n, np.uint8) if expanded is None else np.ascontiguousarray(expanded).astype(np.uint8).reshape(patches.n)
+    if (np.diff(cs) == 0).any():
+        raise ValueError(f"filter_extend_level: cell {int(np.nonzero(np.diff(cs) == 0)[0][0])} is empty")
+    F = _filter(scene, patches, cs)
+    if exp[F.keep].any():
+        raise ValueError(f"filter_extend_level: the kept patch of cell {int(np.nonzero(exp[F.keep])[0][0])} is already expanded")
+    parents = _rows(patches, F.keep)
+    n = parents.n
+    N = 6 * n
+    cc = np.zeros((n, 3), np.float32)
+    widths = np.full(n, width, np.float32)
+    pre = api.expand_batch(scene, api.EXPAND_EXTEND, parents, cc, widths, np.ones(N, np.uint8), options=o)
+    pre_key = [key(pre.center[t], width) for t in range(N)]
+    skip = np.array([k in occupied for k in pre_key], np.uint8)   # level-start occupancy: those are never refined
+    out = api.expand_batch(scene, api.EXPAND_EXTEND, parents, cc, widths, skip, options=o)
+    refined = (out.stage == 0) & (skip == 0)
+    post_key = [key(out.center[t], width) if refined[t] else None for t in range(N)]
+    # ONE footprint call: the refined candidates, then the losers
+    rc = np.nonzero(refined)[0]
+    losers = np.nonzero(F.removed)[0]
+    M = max(out.max_images, patches.max_images)
+    fp_rows = [_rows(out, rc, M), _rows(patches, losers, M)]
+    fp = api.Batch(*[np.concatenate([getattr(b, f) for b in fp_rows]) for f in ("center", "normal", "scale", "n_images", "images")])
+    wr, fr, at, vb = api.depth_footprints_batch(scene, fp)
+    fpi = {int(t): i for i, t in enumerate(rc)}
+    pad = lambda a: np.pad(a, ((0, 0), (0, M - a.shape[1])), constant_values=-1)
+    pimg, oimg = pad(patches.images), pad(out.images)
+    V = scene.n_views
+    reads_cache, writes_cache = {}, {}
+
+    def reads(t):
+        r = reads_cache.get(t)
+        if r is None:
+            i = fpi[t]
+            r = set()
+            for k in range(int(fp.n_images[i])):
+                if at[i, k, 0] >= 0:
+                    _full_depth_cells(at[i, k, 0], int(at[i, k, 1]), int(at[i, k, 2]), n_levels, r)
+                if fr[i, k, 0] >= 0:
+                    r.add(_cell(*fr[i, k]))
+            for v in range(V):
+                if vb[i, v, 0]:
+                    _full_depth_cells(v, int(vb[i, v, 1]), int(vb[i, v, 2]), n_levels, r)
+            reads_cache[t] = r
+        return r
+
+    def writes_row(i):
+        return {_cell(*wr[i, k]) for k in range(int(fp.n_images[i])) if wr[i, k, 0] >= 0}
+
+    def writes(t):
+        w = writes_cache.get(t)
+        if w is None:
+            w = writes_cache[t] = writes_row(fpi[t])
+        return w
+
+    ev_cells = {int(r): writes_row(len(rc) + j) for j, r in enumerate(losers)}
+    # the queue: per cell its losers (events, ("e", row)), then its six candidates (("c", t))
+    cell_of = np.repeat(np.arange(len(cs) - 1), np.diff(cs))
+    queue = []
+    li = 0
+    for i in range(n):
+        while li < len(losers) and cell_of[losers[li]] == i:
+            queue.append(("e", int(losers[li])))
+            li += 1
+        queue.extend(("c", t) for t in range(6 * i, 6 * i + 6) if not skip[t])
+    stage = np.where(skip != 0, 20, out.stage).astype(np.int32)
+    counts = np.full((N, 3), -1, np.int32)
+    accepted = []
+    pending = queue
+    waves = 0
+    deferred_log = []
+    while pending:
+        waves += 1
+        todo = [t for kind, t in pending if kind == "c" and refined[t]]
+        cnt = {}
+        if todo:
+            v, b, f = api.depth_gates_batch(scene, _rows(out, todo), margin, abs_int)
+            cnt = {t: (int(v[i]), int(b[i]), int(f[i])) for i, t in enumerate(todo)}
+        dirty, guard, maybe_occ, occ_guard = set(), set(), set(), set()
+        cand_dirty, cand_guard = set(), set()     # the candidates' share of dirty / guard: what an event checks
+        deferred, ops = [], []
+
+        def defer(t):
+            deferred.append(("c", t))
+            occ_guard.add(pre_key[t])
+            if refined[t]:
+                dirty.update(writes(t)); cand_dirty.update(writes(t))
+                guard.update(reads(t)); cand_guard.update(reads(t))
+                maybe_occ.add(post_key[t]); occ_guard.add(post_key[t])
+
+        for kind, t in pending:
+            if kind == "e":
+                c = ev_cells[t]
+                dirty.update(c)
+                if not c.isdisjoint(cand_dirty) or not c.isdisjoint(cand_guard):
+                    deferred.append(("e", t))
+                    guard.update(c)
+                else:
+                    ops.append(("e", t))
+                continue
+            pk = pre_key[t]
+            if pk in occupied:
+                stage[t] = 20                       # its leaf was taken (by an earlier candidate: occupancy only grows in order)
+                continue
+            if pk in maybe_occ:
+                defer(t)
+                continue
+            if not refined[t]:
+                stage[t] = out.stage[t]             # failed in optimize or at the scale / drift gates: reads no map
+                continue
+            if not reads(t).isdisjoint(dirty):
+                defer(t)
+                continue
+            v_, b_, f_ = cnt[t]
+            counts[t] = (v_, b_, f_)
+            if not v_ >= MIN:
+                stage[t] = 23
+            elif not b_ < MIN:
+                stage[t] = 24
+            elif not (f_ >= MIN - 1 and f_ * 1.0 / int(out.n_images[t]) > 0.75):
+                stage[t] = 25
+            else:
+                k_ = post_key[t]
+                if k_ in occupied:
+                    stage[t] = 26
+                elif k_ in maybe_occ or k_ in occ_guard or not writes(t).isdisjoint(guard):
+                    counts[t] = (-1, -1, -1)
+                    defer(t)
+                else:
+                    occupied.add(k_)
+                    stage[t] = 0
+                    accepted.append(t); ops.append(("c", t))
+                    dirty.update(writes(t)); cand_dirty.update(writes(t))
+        if ops:
+            src = [(patches, pimg) if kind == "e" else (out, oimg) for kind, _ in ops]
+            sub = np.array([kind == "e" for kind, _ in ops], np.uint8)
+            batch = api.Batch(*[np.array([getattr(b, f)[t] for (b, _), (_, t) in zip(src, ops)]) for f in ("center", "normal", "scale", "n_images")],
+                              np.array([im[t] for (_, im), (_, t) in zip(src, ops)]))
+            batch.ok[:] = 1
+            if sub.any():
+                api.depth_ops_batch(scene, batch, sub)
+            else:
+                api.set_depths_batch(scene, batch)
+        deferred_log.append(len(deferred))
+        pending = deferred
+    accepted.sort()
+    return F, LevelResult(out, stage, counts, accepted, waves, deferred_log)

@@ -920,6 +920,142 @@ extern "C" int hpmvs_host_selftest_conflict_graph(unsigned seed, int n, int n_vi
     return bad;
 }
 
+namespace {
+// The subtraction events of filterExtendLevel in the conflict graph: an event is a node with write cells and no
+// reads (its footprint's read entries are cleared before build_conflict_graph, which then gives the candidate -> event read edges:
+// flow[t] holds the events u < t that write a cell candidate t reads, anti[e] the candidates d < e that read a cell event e
+// writes).  add_event_edges adds the write-write edges between an event and a candidate: the candidates u < e that write one of
+// e's cells go into flow[e] (e waits while such a u is accepted or deferred in this wave), the events e < t that write one of
+// candidate t's cells into anti[t] (t must not be entered while such an e is deferred).  No edges between events: subtractions
+// commute.  Neither list gets a duplicate: build_conflict_graph puts no candidate into flow[e] and no event into anti[t].
+void clear_event_reads(RawFootprints& F, const std::vector<uint8_t>& isEvent) {
+    for (size_t i = 0; i < F.n; i++) {
+        if (!isEvent[i]) continue;
+        for (size_t k = 0; k < F.M; k++) {
+            F.fr[(i * F.M + k) * 4] = -1;
+            F.at[(i * F.M + k) * 3] = -1;
+        }
+        for (size_t v = 0; v < F.V; v++) F.vb[(i * F.V + v) * 3] = 0;
+    }
+}
+void add_event_edges(const RawFootprints& F, const std::vector<uint8_t>& isEvent, ConflictGraph& G) {
+    const size_t n = F.n;
+    std::unordered_map<uint64_t, std::vector<uint32_t> > evCells;   // cell key -> the events that write it
+    for (size_t i = 0; i < n; i++)
+        if (isEvent[i]) for_write_cells(F, i, [&](uint64_t k) { auto& v = evCells[k]; if (v.empty() || v.back() != (uint32_t)i) v.push_back((uint32_t)i); return false; });
+    std::vector<std::pair<uint32_t, uint32_t> > eFlow, eAnti;   // (node, neighbour)
+    if (!evCells.empty()) {
+        std::vector<uint32_t> seen(n, 0xFFFFFFFFu);
+        for (size_t t = 0; t < n; t++) {
+            if (isEvent[t]) continue;
+            for_write_cells(F, t, [&](uint64_t k) {
+                auto it = evCells.find(k);
+                if (it == evCells.end()) return false;
+                for (uint32_t e : it->second) {
+                    if (seen[e] == (uint32_t)t) continue;
+                    seen[e] = (uint32_t)t;
+                    if (e > t) eFlow.emplace_back(e, (uint32_t)t); else eAnti.emplace_back((uint32_t)t, e);
+                }
+                return false;
+            });
+        }
+    }
+    auto merge = [&](std::vector<std::pair<uint32_t, uint32_t> >& e, std::vector<uint32_t>& off, std::vector<uint32_t>& adj) {
+        if (e.empty()) return;
+        std::vector<uint32_t> cnt(n + 1, 0);
+        for (auto& p : e) cnt[p.first + 1]++;
+        std::vector<uint32_t> noff(n + 1, 0), nadj(adj.size() + e.size());
+        for (size_t i = 0; i < n; i++) noff[i + 1] = noff[i] + (off[i + 1] - off[i]) + cnt[i + 1];
+        std::vector<uint32_t> fill(n);
+        for (size_t i = 0; i < n; i++) {
+            fill[i] = noff[i];
+            for (uint32_t q = off[i]; q < off[i + 1]; q++) nadj[fill[i]++] = adj[q];
+        }
+        for (auto& p : e) nadj[fill[p.first]++] = p.second;
+        off.swap(noff); adj.swap(nadj);
+    };
+    merge(eFlow, G.flow_off, G.flow_adj);
+    merge(eAnti, G.anti_off, G.anti_adj);
+}
+}  // namespace
+
+// Test hook (tests/test_cpu_filter.py; no device needed): random footprints as in hpmvs_host_selftest_conflict_graph, every node an
+// event with probability 1 / event_every (its reads cleared), and the graph of build_conflict_graph + add_event_edges against the
+// definition of DESIGN.md §3.9 by brute-force set intersection:
+//   flow[i], candidate i: nodes j < i (either kind) that write a cell i reads;  event i: candidates j < i that write a cell i writes;
+//   anti[i], candidate i: candidates j < i that read a cell i writes, and events j < i that write a cell i writes;
+//            event i: candidates j < i that read a cell i writes.
+// Returns the number of nodes whose lists differ from the definition (0; a duplicate counts), or -1 for bad arguments.
+extern "C" int hpmvs_host_selftest_event_graph(unsigned seed, int n, int n_views, int max_w, int max_h, int n_levels, int max_images,
+                                               int event_every, int* n_edges, int* n_events) {
+    if (n < 1 || n_views < 1 || max_w < 8 || max_h < 8 || n_levels < 1 || n_levels > 7 || max_images < 1 || event_every < 1) return -1;
+    RawFootprints F;
+    F.n = (size_t)n; F.V = (size_t)n_views; F.M = (size_t)max_images;
+    F.nimg.assign(F.n, 0);
+    F.wr.assign(F.n * F.M * 4, -1); F.fr.assign(F.n * F.M * 4, -1); F.at.assign(F.n * F.M * 3, -1); F.vb.assign(F.n * F.V * 3, 0);
+    unsigned long long st = 0x9E3779B97F4A7C15ull ^ ((unsigned long long)seed * 0xD1B54A32D192ED03ull);
+    auto rnd = [&](int m) { st = st * 6364136223846793005ull + 1442695040888963407ull; return (int)((st >> 33) % (unsigned long long)m); };
+    const int wx = max_w / 4 < 24 ? max_w / 4 : 24, wy = max_h / 4 < 24 ? max_h / 4 : 24;
+    std::vector<uint8_t> isEvent(F.n, 0);
+    int events = 0;
+    for (size_t i = 0; i < F.n; i++) {
+        isEvent[i] = rnd(event_every) == 0 ? 1 : 0;
+        events += isEvent[i];
+        const int m = 1 + rnd(max_images);
+        F.nimg[i] = m;
+        const int corner = rnd(4);
+        const int bx = (corner & 1) ? max_w - wx - 1 : -2, by = (corner & 2) ? max_h - wy - 1 : -2;
+        for (int k = 0; k < m; k++) {
+            const int view = rnd(n_views), px = bx + rnd(wx + 3), py = by + rnd(wy + 3);
+            int32_t* a = &F.at[(i * F.M + k) * 3];
+            if (rnd(8)) { a[0] = view; a[1] = px - 1; a[2] = py - 1; }
+            const int l = rnd(n_levels);
+            const int cx = (px < 0 ? 0 : px) >> (1 + l), cy = (py < 0 ? 0 : py) >> (1 + l);
+            int32_t* w = &F.wr[(i * F.M + k) * 4];
+            if (rnd(6)) { w[0] = view; w[1] = l; w[2] = cx + rnd(2); w[3] = cy + rnd(2); }
+            const int lf = rnd(n_levels);
+            int32_t* f = &F.fr[(i * F.M + k) * 4];
+            if (rnd(6)) { f[0] = view; f[1] = lf; f[2] = ((px < 0 ? 0 : px) >> (1 + lf)) + rnd(2); f[3] = ((py < 0 ? 0 : py) >> (1 + lf)) + rnd(2); }
+        }
+        for (int v = 0; v < n_views; v++)
+            if (rnd(3) == 0) { int32_t* b = &F.vb[(i * F.V + (size_t)v) * 3]; b[0] = 1; b[1] = bx + rnd(wx + 3) - 1; b[2] = by + rnd(wy + 3) - 1; }
+    }
+    clear_event_reads(F, isEvent);
+    ConflictGraph G;
+    build_conflict_graph(F, n_levels, max_w, max_h, G);
+    add_event_edges(F, isEvent, G);
+    std::vector<std::unordered_set<uint64_t> > R(F.n), W(F.n);
+    for (size_t i = 0; i < F.n; i++) {
+        for_read_cells(F, i, n_levels, [&](uint64_t k) { R[i].insert(k); return false; });
+        for_write_cells(F, i, [&](uint64_t k) { W[i].insert(k); return false; });
+    }
+    auto meets = [](const std::unordered_set<uint64_t>& a, const std::unordered_set<uint64_t>& b) {
+        for (uint64_t k : a) if (b.count(k)) return true;
+        return false;
+    };
+    int bad = 0;
+    for (size_t i = 0; i < F.n; i++) {
+        std::unordered_set<uint32_t> wantFlow, wantAnti;
+        for (size_t j = 0; j < i; j++) {
+            if (isEvent[i]) {
+                if (!isEvent[j] && meets(W[j], W[i])) wantFlow.insert((uint32_t)j);
+                if (!isEvent[j] && meets(R[j], W[i])) wantAnti.insert((uint32_t)j);
+            } else {
+                if (meets(W[j], R[i])) wantFlow.insert((uint32_t)j);
+                if (isEvent[j] ? meets(W[j], W[i]) : meets(R[j], W[i])) wantAnti.insert((uint32_t)j);
+            }
+        }
+        const std::unordered_set<uint32_t> gotFlow(G.flow_adj.begin() + G.flow_off[i], G.flow_adj.begin() + G.flow_off[i + 1]);
+        const std::unordered_set<uint32_t> gotAnti(G.anti_adj.begin() + G.anti_off[i], G.anti_adj.begin() + G.anti_off[i + 1]);
+        if (gotFlow != wantFlow || gotFlow.size() != (size_t)(G.flow_off[i + 1] - G.flow_off[i]) || gotAnti != wantAnti ||
+            gotAnti.size() != (size_t)(G.anti_off[i + 1] - G.anti_off[i]))
+            bad++;
+    }
+    if (n_edges) *n_edges = (int)(G.flow_adj.size() + G.anti_adj.size());
+    if (n_events) *n_events = events;
+    return bad;
+}
+
 bool Scene::depthFootprints(const Patch3d* const* patches, size_t n, std::vector<std::vector<uint64_t> >& reads,
                             std::vector<std::vector<uint64_t> >& writes, int nLevels) const {
     reads.assign(n, std::vector<uint64_t>());
@@ -1535,6 +1671,186 @@ bool PatchOptimizer::extendLevel(const mo3d::Patch3d* const* parents, size_t n, 
                      1e3 * (t_pre - t_begin), 1e3 * (t_ref - t_pre), 1e3 * (t_fp - t_ref), 1e3 * (t_graph - t_fp), G.flow_adj.size(), G.anti_adj.size(),
                      1e3 * t_gates, 1e3 * t_walk, 1e3 * t_set);
     std::sort(R.accepted.begin(), R.accepted.end());
+    return true;
+}
+
+// ---------------------------------------------------------------- filter
+// ONE hpmvs_filter_batch over the cells: keep / dist / removed.  false for malformed offsets or a cell with no winner.
+static bool run_filter(const Scene* scene, mo3d::Patch3d* const* patches, const size_t* cellStart, size_t nCells, PatchOptimizer::FilterResult& R,
+                       const char* who) {
+    R = PatchOptimizer::FilterResult();
+    if (!cellStart || cellStart[0] != 0 || nCells > (size_t)INT32_MAX - 1) {
+        std::cerr << "hpmvs: " << who << ": cellStart must start at 0" << std::endl;
+        return false;
+    }
+    for (size_t c = 0; c < nCells; c++)
+        if (cellStart[c + 1] < cellStart[c]) { std::cerr << "hpmvs: " << who << ": cellStart decreases" << std::endl; return false; }
+    const size_t n = cellStart[nCells];
+    if (n > (size_t)INT32_MAX) { std::cerr << "hpmvs: " << who << ": too many patches" << std::endl; return false; }
+    hpmvs_scene* dev = scene->deviceScene();
+    if (!dev) return false;
+    std::vector<int32_t> cs(nCells + 1), keep(nCells);
+    for (size_t c = 0; c <= nCells; c++) cs[c] = (int32_t)cellStart[c];
+    R.dist.assign(n, 0.0f);
+    HostBatch hb(reinterpret_cast<const Patch3d* const*>(patches), n);
+    if (hpmvs_filter_batch(dev, &hb.b, cs.data(), (int)nCells, R.dist.data(), keep.data(), 0, nullptr) != HPMVS_OK) {
+        std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl;
+        return false;
+    }
+    for (size_t c = 0; c < nCells; c++)
+        if (keep[c] == -2) { std::cerr << "hpmvs: " << who << ": cell " << c << " has no patch whose distance is below FLT_MAX" << std::endl; return false; }
+    R.keep.assign(keep.begin(), keep.end());
+    R.removed.assign(n, 1);
+    for (size_t c = 0; c < nCells; c++) if (keep[c] >= 0) R.removed[(size_t)keep[c]] = 0;
+    return true;
+}
+
+bool PatchOptimizer::filterLevel(mo3d::Patch3d* const* patches, const size_t* cellStart, size_t nCells, FilterResult& R) {
+    if (!run_filter(scene_p, patches, cellStart, nCells, R, "filterLevel")) return false;
+    std::vector<const Patch3d*> losers;
+    for (size_t i = 0; i < R.removed.size(); i++) if (R.removed[i]) losers.push_back(patches[i]);
+    const std::vector<uint8_t> sub(losers.size(), 1);
+    if (!losers.empty() && !scene_p->setDepths(losers.data(), losers.size(), sub.data())) return false;   // setDepths(*p, true) (:71)
+    for (size_t i = 0; i < R.removed.size(); i++) if (R.removed[i]) patches[i]->images_.clear();            // images_.clear() (:72)
+    return true;
+}
+
+bool PatchOptimizer::filterExtendLevel(mo3d::Patch3d* const* patches, const size_t* cellStart, size_t nCells, float width,
+                                       std::unordered_set<uint64_t>& occupied, float margin, bool absInt, FilterResult& FR, LevelResult& R,
+                                       LeafKeyFn leafKey, void* user) {
+    if (!leafKey) leafKey = grid_leaf_key;
+    R = LevelResult();
+    int nLevels = 1;
+    for (const Camera& c : scene_p->cameras_) nLevels = std::max(nLevels, c.getLevels());
+    if (nLevels > HPMVS_MAX_LEVELS) { std::cerr << "hpmvs: filterExtendLevel: more than HPMVS_MAX_LEVELS pyramid levels" << std::endl; return false; }
+    if (cellStart)
+        for (size_t c = 0; c < nCells; c++)
+            if (cellStart[c + 1] == cellStart[c]) { std::cerr << "hpmvs: filterExtendLevel: cell " << c << " is empty" << std::endl; return false; }
+    if (!run_filter(scene_p, patches, cellStart, nCells, FR, "filterExtendLevel")) return false;
+    const size_t n = nCells, N = 6, T = n * N;
+    std::vector<const Patch3d*> parents(n);
+    for (size_t i = 0; i < n; i++) {
+        parents[i] = patches[(size_t)FR.keep[i]];
+        if (parents[i]->expanded_) { std::cerr << "hpmvs: filterExtendLevel: the kept patch of cell " << i << " is already expanded" << std::endl; return false; }
+    }
+    if (n == 0) return true;
+    // extendLevel's candidate steps over the kept patches
+    std::vector<CellRef> cells(n);
+    for (size_t i = 0; i < n; i++) { cells[i].c = Eigen::Vector3f(0.0f, 0.0f, 0.0f); cells[i].width = width; }
+    std::vector<uint8_t> skip(T, 0), refined;
+    std::vector<float> pre, widths(n, width);
+    if (!candidate_centers(scene_p, options_p, (int)EXTEND, parents.data(), widths.data(), n, pre)) return false;
+    std::vector<uint64_t> preKey(T), postKey(T, 0);
+    for (size_t t = 0; t < T; t++) {
+        preKey[t] = leafKey(Eigen::Vector3f(pre[3 * t], pre[3 * t + 1], pre[3 * t + 2]), width, user);
+        skip[t] = occupied.count(preKey[t]) ? 1 : 0;
+    }
+    expandBatch(EXTEND, parents.data(), cells.data(), n, skip.data(), R.candidates, refined);
+    if (R.candidates.size() != T) return false;
+    for (size_t t = 0; t < T; t++) {
+        if (skip[t]) refined[t] = 0;
+        if (refined[t]) postKey[t] = leafKey(Eigen::Vector3f(R.candidates[t].center_[0], R.candidates[t].center_[1], R.candidates[t].center_[2]), width, user);
+    }
+    // the footprinted nodes in queue order: per cell its losers (events), then its refined candidates; ONE footprint call
+    std::vector<const Patch3d*> nodes;
+    std::vector<uint8_t> isEvent;
+    std::vector<int> fpi(T, -1);
+    std::vector<size_t> queue;   // pending items: t < T a candidate, T + node an event
+    for (size_t i = 0; i < n; i++) {
+        for (size_t r = cellStart[i]; r < cellStart[i + 1]; r++)
+            if (FR.removed[r]) { queue.push_back(T + nodes.size()); nodes.push_back(patches[r]); isEvent.push_back(1); }
+        for (size_t t = N * i; t < N * (i + 1); t++) {
+            if (refined[t]) { fpi[t] = (int)nodes.size(); nodes.push_back(&R.candidates[t]); isEvent.push_back(0); }
+            if (!skip[t]) queue.push_back(t);
+        }
+    }
+    RawFootprints F;
+    if (!raw_footprints(*scene_p, nodes.data(), nodes.size(), F)) return false;
+    clear_event_reads(F, isEvent);
+    ConflictGraph G;
+    {
+        int maxW = 1, maxH = 1;
+        for (const Image& im : scene_p->images_) { maxW = std::max(maxW, im.getWidth()); maxH = std::max(maxH, im.getHeight()); }
+        if (F.n > 0) { build_conflict_graph(F, nLevels, maxW, maxH, G); add_event_edges(F, isEvent, G); }
+    }
+    R.stage.assign(T, 1);
+    R.counts.assign(3 * T, -1);
+    for (size_t t = 0; t < T; t++) if (skip[t]) R.stage[t] = 20;
+    const int MIN = options_p->MIN_IMAGES_PER_PATCH;
+    // open[i] == w: node i was accepted, applied or deferred in wave w (`dirty`); defer_w[i] == w: deferred in wave w (`guard`).  For an
+    // event, flow lists only candidates, so its tests are those of §3.9: an earlier candidate accepted or deferred that writes its cells,
+    // an earlier deferred candidate that reads them.
+    std::vector<int> open(nodes.size(), 0), defer_w(nodes.size(), 0);
+    FlatSet maybeOcc, occGuard;
+    auto reads_hit_dirty = [&](size_t i, int wave) {
+        for (uint32_t q = G.flow_off[i]; q < G.flow_off[i + 1]; q++) if (open[G.flow_adj[q]] == wave) return true;
+        return false;
+    };
+    auto writes_hit_guard = [&](size_t i, int wave) {
+        for (uint32_t q = G.anti_off[i]; q < G.anti_off[i + 1]; q++) if (defer_w[G.anti_adj[q]] == wave) return true;
+        return false;
+    };
+    std::vector<size_t> pending = queue;
+    while (!pending.empty()) {
+        R.waves++;
+        std::vector<size_t> todo;
+        for (size_t t : pending) if (t < T && refined[t]) todo.push_back(t);
+        std::vector<int> v, b, f;
+        std::vector<const Patch3d*> sub(todo.size());
+        for (size_t k = 0; k < todo.size(); k++) sub[k] = &R.candidates[todo[k]];
+        if (!todo.empty() && !scene_p->depthGates(sub.data(), sub.size(), margin, v, b, f, absInt)) return false;
+        std::vector<int> slot(T, -1);
+        for (size_t k = 0; k < todo.size(); k++) slot[todo[k]] = (int)k;
+        maybeOcc.clear(); occGuard.clear();
+        const int wave = R.waves;
+        std::vector<size_t> deferred;
+        std::vector<const Patch3d*> ops;
+        std::vector<uint8_t> opSub;
+        auto defer = [&](size_t t) {
+            deferred.push_back(t);
+            occGuard.add(preKey[t]);
+            if (refined[t]) {
+                open[(size_t)fpi[t]] = wave; defer_w[(size_t)fpi[t]] = wave;
+                maybeOcc.add(postKey[t]); occGuard.add(postKey[t]);
+            }
+        };
+        for (size_t t : pending) {
+            if (t >= T) {   // a subtraction event: always passes, occupies no leaf
+                const size_t e = t - T;
+                open[e] = wave;
+                if (reads_hit_dirty(e, wave) || writes_hit_guard(e, wave)) { defer_w[e] = wave; deferred.push_back(t); }
+                else { ops.push_back(nodes[e]); opSub.push_back(1); }
+                continue;
+            }
+            if (occupied.count(preKey[t])) { R.stage[t] = 20; continue; }
+            if (maybeOcc.has(preKey[t])) { defer(t); continue; }
+            if (!refined[t]) { R.stage[t] = 1; continue; }
+            if (reads_hit_dirty((size_t)fpi[t], wave)) { defer(t); continue; }
+            const int k = slot[t];
+            const int cv = v[k], cb = b[k], cf = f[k];
+            R.counts[3 * t] = cv; R.counts[3 * t + 1] = cb; R.counts[3 * t + 2] = cf;
+            if (!(cv >= MIN)) R.stage[t] = 23;
+            else if (!(cb < MIN)) R.stage[t] = 24;
+            else if (!(cf >= MIN - 1 && cf * 1.0 / (double)R.candidates[t].images_.size() > 0.75)) R.stage[t] = 25;
+            else if (occupied.count(postKey[t])) R.stage[t] = 26;
+            else if (maybeOcc.has(postKey[t]) || occGuard.has(postKey[t]) || writes_hit_guard((size_t)fpi[t], wave)) {
+                R.counts[3 * t] = R.counts[3 * t + 1] = R.counts[3 * t + 2] = -1;
+                defer(t);
+            } else {
+                occupied.insert(postKey[t]);
+                R.stage[t] = 0;
+                R.accepted.push_back(t);
+                ops.push_back(&R.candidates[t]); opSub.push_back(0);
+                open[(size_t)fpi[t]] = wave;
+            }
+        }
+        // the wave's accepted additions and applied subtractions, in queue order
+        const bool anySub = std::find(opSub.begin(), opSub.end(), (uint8_t)1) != opSub.end();   // (additions only: setDepths' plain batch)
+        if (!ops.empty() && !scene_p->setDepths(ops.data(), ops.size(), anySub ? opSub.data() : nullptr)) return false;
+        pending.swap(deferred);
+    }
+    std::sort(R.accepted.begin(), R.accepted.end());
+    for (size_t i = 0; i < FR.removed.size(); i++) if (FR.removed[i]) patches[i]->images_.clear();   // images_.clear() (:72)
     return true;
 }
 

@@ -106,6 +106,26 @@ public:
     };
     bool processLevel(mo3d::Patch3d* const* cells, const int32_t* cellLeaf, size_t n, const uint8_t* finalLevel, const LeafTable& table,
                       ProcessResult& out);
+    // Priority L*10 of processCell for cells holding several patches (reference src/hpmvs/CellProcessor.cpp:369-392, filter :43-82), the
+    // C++ form of hpmvs_amd.frontier.filter_level / filter_extend_level (same calls, same results).  patches: the cells' patches in data
+    // order, the cells in the scheduler's order; cell c holds patches[cellStart[c]] .. patches[cellStart[c + 1] - 1] (cellStart has
+    // nCells + 1 entries, starts at 0 and does not decrease).  keep[c]: the index of the patch filter keeps (-1: empty cell); removed[i]:
+    // patch i lost (its depths are out of the maps and its images_ cleared, as the reference does; the tree stays the caller's).
+    struct FilterResult {
+        std::vector<int> keep;
+        std::vector<float> dist;                 // per patch: the reference's mean signed plane distance (0 in single-patch cells)
+        std::vector<uint8_t> removed;
+    };
+    // filter for every cell as ONE hpmvs_filter_batch, then the losers' depths taken back in ONE ordered Scene::setDepths(..., subtract).
+    // false (nothing changed) for malformed offsets or a cell with no winner (the reference would keep a null pointer).
+    bool filterLevel(mo3d::Patch3d* const* patches, const size_t* cellStart, size_t nCells, FilterResult& out);
+    // filter cell i, then CellProcessor::extend on its kept patch, for every cell in queue order: ONE filter call, extendLevel's candidate
+    // steps over the kept patches, and extendLevel's wave walk over a conflict graph that also holds the losers as subtraction events
+    // (DESIGN.md §3.9).  `level` is laid out as extendLevel's, the kept patches being the parents.  false before any map update for
+    // malformed offsets, an empty cell, a cell with no winner or a kept patch that is already expanded (processCell does not extend it).
+    bool filterExtendLevel(mo3d::Patch3d* const* patches, const size_t* cellStart, size_t nCells, float width,
+                           std::unordered_set<uint64_t>& occupied, float margin, bool absInt, FilterResult& filter, LevelResult& level,
+                           LeafKeyFn leafKey = nullptr, void* user = nullptr);
     // diagnostics of the last optimize()/optimizeBatch() call that the reference computes and drops
     // (final mean robust INCC f*, PatchOptimizer.cpp:365,376): one entry per patch
     const std::vector<double>& lastObjective() const { return lastF_; }

@@ -30,6 +30,7 @@
  *   hpmvs_expand_batch       <- the candidate loops of CellProcessor::extend / ::branch,
  *                               src/hpmvs/CellProcessor.cpp:84-142 and :210-262.
  *   hpmvs_regularize_batch   <- CellProcessor::regularize, src/hpmvs/CellProcessor.cpp:309-367.
+ *   hpmvs_filter_batch       <- CellProcessor::filter, src/hpmvs/CellProcessor.cpp:43-82.
  *   hpmvs_camera_from_nvm    <- Camera::init, src/hpmvs/Camera.cpp:34-81.
  */
 #ifndef HPMVS_AMD_H
@@ -294,6 +295,21 @@ typedef struct {
 int hpmvs_regularize_batch(const hpmvs_scene *s, const hpmvs_patch_batch *cells, const float *cell_width, const int32_t *position,
                            const uint8_t *expanded, const hpmvs_leaf_table *leaves, float *flatness, int32_t *n_neighbours,
                            int32_t *neighbour_leaf, int on_device, void *stream);
+
+/* ---- CellProcessor::filter for a priority level (src/hpmvs/CellProcessor.cpp:43-82, processCell :377-378) ------------------------
+ * The rows of `patches` (center and normal are read) are the cells' patches in data order, the cells in the scheduler's order:
+ * cell c holds rows cell_start[c] .. cell_start[c + 1] - 1.  For a cell of k >= 2 patches, dist[r] is the reference's float for
+ * row r: (sum over the other rows jj, in order, of normalized(normal_r) . (center_jj - center_r)) / (float)(k - 1), signed; 0
+ * for the rows of single-patch cells.  keep[c] is the row of the patch filter keeps -- the lowest row reaching the minimum among
+ * the cell's distances < FLT_MAX (NaN and +inf never win) --, the cell's row for a single patch, -1 for an empty cell and -2
+ * for a cell with no distance below FLT_MAX (the reference would keep a null pointer there).  The other rows of a cell are
+ * its losers: the caller takes their depths back (hpmvs_depth_ops_batch, subtract = 1, in queue order) and clears their image
+ * lists.  HPMVS_ERR_ARG before any output is written when a count is negative, cell_start[0] != 0, the offsets decrease or
+ * cell_start[n_cells] != patches->n (with device pointers the offsets are checked by a small kernel whose verdict the call
+ * reads back first).  Host or device pointers as for hpmvs_optimize_batch; host-synchronous once, then only enqueues when
+ * on_device != 0. */
+int hpmvs_filter_batch(const hpmvs_scene *s, const hpmvs_patch_batch *patches, const int32_t *cell_start, int n_cells, float *dist,
+                       int32_t *keep, int on_device, void *stream);
 
 /* Host-pointer calls and pinned memory.  An array of a host-pointer call (on_device = 0) that lies in pinned host memory
  * mapped into the GPU's address space -- hipHostMalloc / hipHostRegister, torch's pin_memory(), hpmvs_host_alloc below --
