@@ -6,21 +6,35 @@ the three depth-map counts (:130-139, Scene.cpp:518-644) -> DynOctTree::addCondi
 Scene::setDepths (Scene.cpp:351-381).  Candidate i's counts are read from maps that the candidates accepted BEFORE it in the
 same level have already written, and its octree cell may have been taken by one of them.
 
-`extend_level` keeps that meaning and the batching:
+`extend_level` keeps that meaning and the batching.  There is ONE walk in this module (`_candidates`, `_level`, `_walk`); the
+level's queue holds the candidates in the reference's order and, for `filter_extend_level`, SUBTRACTION EVENTS between them
+(the patches CellProcessor::filter removed from a cell, right before that cell's candidates).  `extend_level` is the walk
+without events.
   * ONE hpmvs_expand_batch refines every candidate of the level (the refinement reads neither the maps nor the octree);
-  * ONE hpmvs_depth_footprints_batch names, per candidate, the map cells its gates read and the cells setDepths would write;
-  * the candidates are then decided in WAVES.  A wave = one hpmvs_depth_gates_batch over the still undecided candidates
-    against the maps as they are, a walk over them in the reference's order, one hpmvs_set_depths_batch for the accepted.
+  * ONE hpmvs_depth_footprints_batch names, per refined candidate, the map cells its gates read and the cells setDepths would
+    write, and per event the cells its setDepths(p, true) would write (a candidate that was not refined reads and writes none);
+  * the queue is then decided in WAVES.  A wave = one hpmvs_depth_gates_batch over the still undecided candidates against the
+    maps as they are, a walk over the pending items in the reference's order, one ordered depth update for what was accepted
+    (hpmvs_set_depths_batch when the wave holds additions only, else ONE hpmvs_depth_ops_batch in queue order: subtracting a
+    depth does not commute with adding one).
     In the walk a candidate is DECIDED (accepted or rejected for good) unless something it depends on is still open:
-      - a map cell it reads may be written by an earlier candidate of this walk that was accepted or deferred (`dirty`),
-      - a cell it would write is read by an earlier deferred candidate (`guard`: that one must not see this write later),
+      - a map cell it reads may be written by an earlier item of this walk: a candidate that was accepted or deferred, an event
+        applied or deferred (`dirty`: its counts were read before that write),
+      - a cell it would write is read by an earlier deferred candidate (that one must not see this write later) or written by
+        an earlier deferred event (the addition must follow the subtraction) (`guard`),
       - its octree cell (before or after refinement) is the possible cell of an earlier deferred candidate (`maybe_occ`),
         or an earlier deferred candidate looks at the cell it would occupy (`occ_guard`);
-    then it is DEFERRED to the next wave, and leaves its own possible effects in those sets.  The first undecided candidate
-    of a wave always gets decided, so the waves end; their number is the depth of the dependency chains, not the number of
-    candidates (tests/test_gpu_expand_round.py records it: a handful).
+    then it is DEFERRED to the next wave, and leaves its own possible effects in those sets.
+    An EVENT always passes and occupies no leaf.  It is deferred when one of its cells is written by an earlier candidate
+    accepted or deferred in this wave (`cand_dirty`), or read by an earlier deferred candidate (`cand_guard`); events never
+    block each other (subtractions commute).  Applied or deferred, its cells join `dirty`; deferred, they also join `guard`.
+    The first undecided item of a wave always gets decided (the sets are empty when it is reached), so the waves end; their
+    number is the depth of the dependency chains, not the number of candidates (tests/test_gpu_expand_round.py records it: a
+    handful).
   The result -- stage codes, counts, accepted set, occupancy, every depth map -- equals the sequential loop's, candidate by
-  candidate (asserted against the oracle's `orc_extend_round` on BASELINE configs[0] and on a 12-view scene).
+  candidate (asserted against the oracle's `orc_extend_round` on BASELINE configs[0] and on a 12-view scene; with events
+  against the sequential filter / extend loop, tests/test_gpu_filter_level.py).  tests/test_cpu_frontier_walk.py
+  drives `_walk` without a device against the sequential loop of a toy model.
 
 The octree itself stays with the scheduler (out of scope): `occupied` is the caller's set of cell keys,
 `cell_key` the caller's map from a point to its leaf (default: the uniform grid of leaf width `width`).
@@ -78,14 +92,32 @@ class LevelResult:
     deferred_per_wave: list = field(default_factory=list)
 
 
-def extend_level(scene: api.Scene, parents: api.Batch, width: float, occupied: set, margin: float = 1.0, abs_int: int = 0,
-                 options=None, n_levels: int = 6, key=cell_key, sequential: bool = True) -> LevelResult:
-    """CellProcessor::extend over `parents` (the leaves of one priority level, in the scheduler's order).  `occupied` is
-    updated in place; the scene's depth maps receive the accepted candidates.  sequential = False gives round 3's plain
-    frontier round (every count read from the maps as they are when the level starts): one wave, not the reference's
-    result when candidates of a level interact through the maps."""
-    o = options or api.default_options()
-    MIN = int(o.MIN_IMAGES_PER_PATCH)
+MAX_LEVELS = 8                     # HPMVS_MAX_LEVELS
+
+
+def _rows(b: api.Batch, idx, width=None) -> api.Batch:
+    idx = np.asarray(idx, dtype=np.int64)
+    img = b.images[idx]
+    if width is not None and width > img.shape[1]:
+        img = np.pad(img, ((0, 0), (0, width - img.shape[1])), constant_values=-1)
+    return api.Batch(b.center[idx], b.normal[idx], b.scale[idx], b.n_images[idx], img)
+
+
+def _concat(batches) -> api.Batch:
+    return api.Batch(*[np.concatenate([getattr(b, f) for b in batches]) for f in ("center", "normal", "scale", "n_images", "images")])
+
+
+def _pyramid_levels(scene: api.Scene, who: str) -> int:
+    """The deepest pyramid of the scene's cameras: the levels getFullDepth walks, so the levels a read can be on."""
+    n_levels = max(scene.view_levels) if scene.view_levels else 1
+    if n_levels > MAX_LEVELS:
+        raise ValueError(f"{who}: the scene's cameras have {n_levels} pyramid levels, more than HPMVS_MAX_LEVELS")
+    return n_levels
+
+
+def _candidates(scene, parents, width, occupied, o, key):
+    """The candidate steps of a level: the six candidates of every parent before optimize and their leaves (`pre_key`), ONE
+    hpmvs_expand_batch over those whose leaf is free when the level starts, the refined ones' leaves (`post_key`)."""
     n = parents.n
     N = 6 * n
     cc = np.zeros((n, 3), np.float32)
@@ -97,59 +129,47 @@ def extend_level(scene: api.Scene, parents: api.Batch, width: float, occupied: s
     out = api.expand_batch(scene, api.EXPAND_EXTEND, parents, cc, widths, skip, options=o)
     refined = (out.stage == 0) & (skip == 0)
     post_key = [key(out.center[t], width) if refined[t] else None for t in range(N)]
-    wr, fr, at, vb = api.depth_footprints_batch(scene, out)
-    V = scene.n_views
+    return out, pre_key, post_key, skip, refined
 
-    reads_cache, writes_cache = {}, {}
 
-    def reads(t):
-        r = reads_cache.get(t)
-        if r is None:
-            r = set()
-            for k in range(int(out.n_images[t])):
-                if at[t, k, 0] >= 0:
-                    _full_depth_cells(at[t, k, 0], int(at[t, k, 1]), int(at[t, k, 2]), n_levels, r)
-                if fr[t, k, 0] >= 0:
-                    r.add(_cell(*fr[t, k]))
-            for v in range(V):
-                if vb[t, v, 0]:
-                    _full_depth_cells(v, int(vb[t, v, 1]), int(vb[t, v, 2]), n_levels, r)
-            reads_cache[t] = r
-        return r
-
-    def writes(t):
-        w = writes_cache.get(t)
-        if w is None:
-            w = {_cell(*wr[t, k]) for k in range(int(out.n_images[t])) if wr[t, k, 0] >= 0}
-            writes_cache[t] = w
-        return w
-
-    stage = np.where(skip != 0, 20, out.stage).astype(np.int32)
-    counts = np.full((N, 3), -1, np.int32)
-    accepted = []
-    pending = [t for t in range(N) if not skip[t]]
-    waves = 0
-    deferred_log = []
+def _walk(queue, pre_key, post_key, refined, n_images, reads, writes, ev_cells, occupied, min_images, stage, counts, gates, apply,
+          sequential=True):
+    """The wave walk of the module docstring over `queue`: items ("c", t) (candidate t) and ("e", j) (subtraction event j) in the
+    reference's order.  reads(t) / writes(t): the map cells refined candidate t's gates read / its setDepths would write (sets);
+    ev_cells[j]: the cells event j writes.  The device is reached through two callables only: gates(list of candidates) -> their
+    (depthTests, viewBlockTest, pixelFreeTests) counts from the maps as they are, apply(ops) enters a wave's accepted candidates
+    and applied events, given as queue items in queue order.  `stage` (preset to each candidate's refinement result) and `counts`
+    are filled in place, `occupied` grows.  Returns (accepted in queue order, waves, deferred per wave).  sequential = False
+    drops every deferral of a candidate (one wave; meaningful without events only)."""
+    MIN = min_images
+    accepted, waves, deferred_log = [], 0, []
+    pending = list(queue)
     while pending:
         waves += 1
-        todo = [t for t in pending if refined[t]]
-        cnt = {}
-        if todo:
-            a = np.array(todo)
-            sub = api.Batch(out.center[a], out.normal[a], out.scale[a], out.n_images[a], out.images[a])
-            v, b, f = api.depth_gates_batch(scene, sub, margin, abs_int)
-            cnt = {t: (int(v[i]), int(b[i]), int(f[i])) for i, t in enumerate(todo)}
+        todo = [t for kind, t in pending if kind == "c" and refined[t]]
+        cnt = dict(zip(todo, gates(todo))) if todo else {}
         dirty, guard, maybe_occ, occ_guard = set(), set(), set(), set()
-        deferred, acc_now = [], []
+        cand_dirty, cand_guard = set(), set()     # the candidates' share of dirty / guard: what an event checks
+        deferred, ops = [], []
 
         def defer(t):
-            deferred.append(t)
+            deferred.append(("c", t))
             occ_guard.add(pre_key[t])
             if refined[t]:
-                dirty.update(writes(t)); guard.update(reads(t))
+                dirty.update(writes(t)); cand_dirty.update(writes(t))
+                guard.update(reads(t)); cand_guard.update(reads(t))
                 maybe_occ.add(post_key[t]); occ_guard.add(post_key[t])
 
-        for t in pending:
+        for kind, t in pending:
+            if kind == "e":
+                c = ev_cells[t]
+                dirty.update(c)
+                if not c.isdisjoint(cand_dirty) or not c.isdisjoint(cand_guard):
+                    deferred.append(("e", t))
+                    guard.update(c)
+                else:
+                    ops.append(("e", t))
+                continue
             pk = pre_key[t]
             if pk in occupied:
                 stage[t] = 20                       # its leaf was taken (by an earlier candidate: occupancy only grows in order)
@@ -158,8 +178,7 @@ def extend_level(scene: api.Scene, parents: api.Batch, width: float, occupied: s
                 defer(t)
                 continue
             if not refined[t]:
-                stage[t] = out.stage[t]             # failed in optimize or at the scale / drift gates: reads no map
-                continue
+                continue                            # failed in optimize or at the scale / drift gates (its preset stage): reads no map
             if sequential and not reads(t).isdisjoint(dirty):
                 defer(t)
                 continue
@@ -169,7 +188,7 @@ def extend_level(scene: api.Scene, parents: api.Batch, width: float, occupied: s
                 stage[t] = 23
             elif not b_ < MIN:
                 stage[t] = 24
-            elif not (f_ >= MIN - 1 and f_ * 1.0 / int(out.n_images[t]) > 0.75):
+            elif not (f_ >= MIN - 1 and f_ * 1.0 / n_images[t] > 0.75):
                 stage[t] = 25
             else:
                 k_ = post_key[t]
@@ -181,17 +200,99 @@ def extend_level(scene: api.Scene, parents: api.Batch, width: float, occupied: s
                 else:
                     occupied.add(k_)
                     stage[t] = 0
-                    accepted.append(t); acc_now.append(t)
-                    dirty.update(writes(t))
-        if acc_now:
-            a = np.array(acc_now)
-            acc = api.Batch(out.center[a], out.normal[a], out.scale[a], out.n_images[a], out.images[a])
-            acc.ok[:] = 1
-            api.set_depths_batch(scene, acc)
+                    accepted.append(t); ops.append(("c", t))
+                    dirty.update(writes(t)); cand_dirty.update(writes(t))
+        if ops:
+            apply(ops)
         deferred_log.append(len(deferred))
         pending = deferred
-    accepted.sort()
-    return LevelResult(out, stage, counts, accepted, waves, deferred_log)
+    return accepted, waves, deferred_log
+
+
+def _level(scene, parents, width, occupied, margin, abs_int, o, key, n_levels, sequential=True, events=None, event_cell=()):
+    """CellProcessor::extend over `parents` with the subtraction events `events` (a Batch, or None): event j comes before the
+    candidates of parent event_cell[j] (non-decreasing).  The candidate steps, ONE hpmvs_depth_footprints_batch over the refined
+    candidates followed by the events, the queue, and the walk with the device behind its two callables."""
+    out, pre_key, post_key, skip, refined = _candidates(scene, parents, width, occupied, o, key)
+    N = 6 * parents.n
+    rc = np.nonzero(refined)[0]
+    n_ev = events.n if events is not None else 0
+    M = max(out.max_images, events.max_images) if n_ev else out.max_images
+    fp = _concat([_rows(out, rc, M)] + ([_rows(events, np.arange(n_ev), M)] if n_ev else []))
+    wr, fr, at, vb = api.depth_footprints_batch(scene, fp) if fp.n else (None,) * 4
+    fpi = {int(t): i for i, t in enumerate(rc)}
+    V = scene.n_views
+    reads_cache, writes_cache = {}, {}
+
+    def reads(t):
+        r = reads_cache.get(t)
+        if r is None:
+            i = fpi[t]
+            r = set()
+            for k in range(int(fp.n_images[i])):
+                if at[i, k, 0] >= 0:
+                    _full_depth_cells(at[i, k, 0], int(at[i, k, 1]), int(at[i, k, 2]), n_levels, r)
+                if fr[i, k, 0] >= 0:
+                    r.add(_cell(*fr[i, k]))
+            for v in range(V):
+                if vb[i, v, 0]:
+                    _full_depth_cells(v, int(vb[i, v, 1]), int(vb[i, v, 2]), n_levels, r)
+            reads_cache[t] = r
+        return r
+
+    def writes_row(i):
+        return {_cell(*wr[i, k]) for k in range(int(fp.n_images[i])) if wr[i, k, 0] >= 0}
+
+    def writes(t):
+        w = writes_cache.get(t)
+        if w is None:
+            w = writes_cache[t] = writes_row(fpi[t])
+        return w
+
+    ev_cells = [writes_row(len(rc) + j) for j in range(n_ev)]
+    # the queue: per parent its events, then its six candidates
+    queue = []
+    j = 0
+    for i in range(parents.n):
+        while j < n_ev and event_cell[j] == i:
+            queue.append(("e", j))
+            j += 1
+        queue.extend(("c", t) for t in range(6 * i, 6 * i + 6) if not skip[t])
+
+    def gates(todo):
+        v, b, f = api.depth_gates_batch(scene, _rows(out, todo), margin, abs_int)
+        return [(int(v[i]), int(b[i]), int(f[i])) for i in range(len(todo))]
+
+    def apply(ops):
+        # additions only: hpmvs_set_depths_batch; with a subtraction ONE hpmvs_depth_ops_batch in queue order
+        sub = np.array([kind == "e" for kind, _ in ops], np.uint8)
+        batch = _rows(out, [t for kind, t in ops if kind == "c"], M)
+        if sub.any():
+            both = _concat([batch, _rows(events, [t for kind, t in ops if kind == "e"], M)])
+            batch = _rows(both, np.argsort(np.argsort(sub, kind="stable")))   # back from (additions, subtractions) to queue order
+        batch.ok[:] = 1
+        if sub.any():
+            api.depth_ops_batch(scene, batch, sub)
+        else:
+            api.set_depths_batch(scene, batch)
+
+    stage = np.where(skip != 0, 20, out.stage).astype(np.int32)
+    counts = np.full((N, 3), -1, np.int32)
+    accepted, waves, deferred_log = _walk(queue, pre_key, post_key, refined, out.n_images, reads, writes, ev_cells, occupied,
+                                          int(o.MIN_IMAGES_PER_PATCH), stage, counts, gates, apply, sequential)
+    return LevelResult(out, stage, counts, sorted(accepted), waves, deferred_log)
+
+
+def extend_level(scene: api.Scene, parents: api.Batch, width: float, occupied: set, margin: float = 1.0, abs_int: int = 0,
+                 options=None, n_levels: int = 6, key=cell_key, sequential: bool = True) -> LevelResult:
+    """CellProcessor::extend over `parents` (the leaves of one priority level, in the scheduler's order): the walk of the module
+    docstring without events.  `occupied` is updated in place; the scene's depth maps receive the accepted candidates.
+    sequential = False gives round 3's plain frontier round (every count read from the maps as they are when the level starts):
+    one wave, not the reference's result when candidates of a level interact through the maps.
+    `n_levels` is kept for existing callers and ignored: the pyramid levels a read can be on are the scene's cameras' (at most
+    HPMVS_MAX_LEVELS, ValueError beyond), so no value given here can hide a read from the walk."""
+    return _level(scene, parents, width, occupied, margin, abs_int, options or api.default_options(), key,
+                  _pyramid_levels(scene, "extend_level"), sequential)
 
 
 @dataclass
@@ -356,9 +457,8 @@ def process_level(scene: api.Scene, cells: api.Batch, cell_leaf, flatness, expan
         raise ValueError("process_level: every cell must own a distinct leaf of the snapshot")
     reg = fl < 0
     settled = np.nonzero(~reg)[0]                   # (NaN is not < 0: processCell settles it)
-    sub = lambda b, idx: api.Batch(b.center[idx], b.normal[idx], b.scale[idx], b.n_images[idx], b.images[idx])
     t = snapshot
-    S = settle_level(scene, sub(cells, settled), t.cell_center[leaf[settled]], t.cell_width[leaf[settled]], fl[settled],
+    S = settle_level(scene, _rows(cells, settled), t.cell_center[leaf[settled]], t.cell_width[leaf[settled]], fl[settled],
                      final[settled], options)
     cc, cw, pc = [t.cell_center], [t.cell_width], [t.patch_center]
     born, died = [t.born], [t.died.copy()]
@@ -388,7 +488,7 @@ def process_level(scene: api.Scene, cells: api.Batch, cell_leaf, flatness, expan
     nb = np.full((n, api.REGULARIZE_PROBES), -1, np.int32) if neighbours else None
     ri = np.nonzero(reg)[0]
     if len(ri):
-        f_, n_, b_ = regularize_level(scene, sub(cells, ri), snap.cell_width[leaf[ri]], ri, exp[ri], snap, fl[ri], neighbours)
+        f_, n_, b_ = regularize_level(scene, _rows(cells, ri), snap.cell_width[leaf[ri]], ri, exp[ri], snap, fl[ri], neighbours)
         fl[ri] = f_; nn[ri] = n_
         if neighbours:
             nb[ri] = b_
@@ -400,9 +500,6 @@ class FilterResult:
     keep: np.ndarray               # [n_cells] row of the kept patch (-1: empty cell, -2: no winner)
     dist: np.ndarray               # [n] the reference's mean signed plane distance per row (0 in single-patch cells)
     removed: np.ndarray            # [n] 1: a loser (its depths taken back, its images_ cleared by the caller)
-
-
-MAX_LEVELS = 8                     # HPMVS_MAX_LEVELS
 
 
 def _cell_offsets(patches: api.Batch, cell_start) -> np.ndarray:
@@ -421,14 +518,6 @@ def _filter(scene: api.Scene, patches: api.Batch, cell_start) -> FilterResult:
     removed = np.ones(patches.n, np.uint8)
     removed[keep[keep >= 0]] = 0
     return FilterResult(keep, dist, removed)
-
-
-def _rows(b: api.Batch, idx, width=None) -> api.Batch:
-    idx = np.asarray(idx, dtype=np.int64)
-    img = b.images[idx]
-    if width is not None and width > img.shape[1]:
-        img = np.pad(img, ((0, 0), (0, width - img.shape[1])), constant_values=-1)
-    return api.Batch(b.center[idx], b.normal[idx], b.scale[idx], b.n_images[idx], img)
 
 
 def filter_level(scene: api.Scene, patches: api.Batch, cell_start, options=None) -> FilterResult:
@@ -453,24 +542,14 @@ def filter_extend_level(scene: api.Scene, patches: api.Batch, cell_start, width:
     cell i (:377-378), then CellProcessor::extend on its kept patch.  Returns (FilterResult, LevelResult); the LevelResult is laid
     out as extend_level's, the kept patches being the parents.
 
-    ONE hpmvs_filter_batch decides every cell (filter reads only the cell's own patches).  Then extend_level's candidate steps
-    over the kept patches -- the candidates' leaves, ONE hpmvs_expand_batch, ONE hpmvs_depth_footprints_batch over the refined
-    candidates and the losers -- and extend_level's wave walk with SUBTRACTION EVENTS: each loser is an event at its queue
-    position (after the candidates of the cells before it, before its own cell's candidates).  An event always passes and
-    occupies no leaf; its cells are those its setDepths(p, true) would write.  It is deferred when one of them is written by an
-    earlier candidate accepted or deferred in this wave, or read by an earlier deferred candidate; events never block each other
-    (subtractions commute).  Applied or deferred, its cells join `dirty` (a later candidate of the wave read its counts before
-    the subtraction); deferred, they also join `guard` (a later addition must follow the subtraction).  Each wave's accepted
-    additions and applied subtractions are ONE hpmvs_depth_ops_batch in queue order.  The result equals the sequential loop's
-    (DESIGN.md §3.9); on a level of single-patch cells it is extend_level's.
+    ONE hpmvs_filter_batch decides every cell (filter reads only the cell's own patches).  Then the walk of the module docstring
+    over the kept patches, each loser a subtraction event at its queue position (after the candidates of the cells before it,
+    before its own cell's candidates); always sequential.  The result equals the sequential loop's; on a level
+    of single-patch cells there are no events and it is extend_level's, wave for wave.
 
     `expanded`: expanded_ per row (default 0).  ValueError before any map update for a cell with no winner, an empty cell or a
     kept patch that is already expanded (processCell does not extend it, :380)."""
-    o = options or api.default_options()
-    MIN = int(o.MIN_IMAGES_PER_PATCH)
-    n_levels = max(scene.view_levels) if scene.view_levels else 1
-    if n_levels > MAX_LEVELS:
-        raise ValueError(f"filter_extend_level: the scene's cameras have {n_levels} pyramid levels, more than HPMVS_MAX_LEVELS")
+    n_levels = _pyramid_levels(scene, "filter_extend_level")
     cs = _cell_offsets(patches, cell_start)
     exp = np.zeros(patches.n, np.uint8) if expanded is None else np.ascontiguousarray(expanded).astype(np.uint8).reshape(patches.n)
     if (np.diff(cs) == 0).any():
@@ -478,144 +557,8 @@ def filter_extend_level(scene: api.Scene, patches: api.Batch, cell_start, width:
     F = _filter(scene, patches, cs)
     if exp[F.keep].any():
         raise ValueError(f"filter_extend_level: the kept patch of cell {int(np.nonzero(exp[F.keep])[0][0])} is already expanded")
-    parents = _rows(patches, F.keep)
-    n = parents.n
-    N = 6 * n
-    cc = np.zeros((n, 3), np.float32)
-    widths = np.full(n, width, np.float32)
-    pre = api.expand_batch(scene, api.EXPAND_EXTEND, parents, cc, widths, np.ones(N, np.uint8), options=o)
-    pre_key = [key(pre.center[t], width) for t in range(N)]
-    skip = np.array([k in occupied for k in pre_key], np.uint8)   # level-start occupancy: those are never refined
-    out = api.expand_batch(scene, api.EXPAND_EXTEND, parents, cc, widths, skip, options=o)
-    refined = (out.stage == 0) & (skip == 0)
-    post_key = [key(out.center[t], width) if refined[t] else None for t in range(N)]
-    # ONE footprint call: the refined candidates, then the losers
-    rc = np.nonzero(refined)[0]
     losers = np.nonzero(F.removed)[0]
-    M = max(out.max_images, patches.max_images)
-    fp_rows = [_rows(out, rc, M), _rows(patches, losers, M)]
-    fp = api.Batch(*[np.concatenate([getattr(b, f) for b in fp_rows]) for f in ("center", "normal", "scale", "n_images", "images")])
-    wr, fr, at, vb = api.depth_footprints_batch(scene, fp)
-    fpi = {int(t): i for i, t in enumerate(rc)}
-    pad = lambda a: np.pad(a, ((0, 0), (0, M - a.shape[1])), constant_values=-1)
-    pimg, oimg = pad(patches.images), pad(out.images)
-    V = scene.n_views
-    reads_cache, writes_cache = {}, {}
-
-    def reads(t):
-        r = reads_cache.get(t)
-        if r is None:
-            i = fpi[t]
-            r = set()
-            for k in range(int(fp.n_images[i])):
-                if at[i, k, 0] >= 0:
-                    _full_depth_cells(at[i, k, 0], int(at[i, k, 1]), int(at[i, k, 2]), n_levels, r)
-                if fr[i, k, 0] >= 0:
-                    r.add(_cell(*fr[i, k]))
-            for v in range(V):
-                if vb[i, v, 0]:
-                    _full_depth_cells(v, int(vb[i, v, 1]), int(vb[i, v, 2]), n_levels, r)
-            reads_cache[t] = r
-        return r
-
-    def writes_row(i):
-        return {_cell(*wr[i, k]) for k in range(int(fp.n_images[i])) if wr[i, k, 0] >= 0}
-
-    def writes(t):
-        w = writes_cache.get(t)
-        if w is None:
-            w = writes_cache[t] = writes_row(fpi[t])
-        return w
-
-    ev_cells = {int(r): writes_row(len(rc) + j) for j, r in enumerate(losers)}
-    # the queue: per cell its losers (events, ("e", row)), then its six candidates (("c", t))
     cell_of = np.repeat(np.arange(len(cs) - 1), np.diff(cs))
-    queue = []
-    li = 0
-    for i in range(n):
-        while li < len(losers) and cell_of[losers[li]] == i:
-            queue.append(("e", int(losers[li])))
-            li += 1
-        queue.extend(("c", t) for t in range(6 * i, 6 * i + 6) if not skip[t])
-    stage = np.where(skip != 0, 20, out.stage).astype(np.int32)
-    counts = np.full((N, 3), -1, np.int32)
-    accepted = []
-    pending = queue
-    waves = 0
-    deferred_log = []
-    while pending:
-        waves += 1
-        todo = [t for kind, t in pending if kind == "c" and refined[t]]
-        cnt = {}
-        if todo:
-            v, b, f = api.depth_gates_batch(scene, _rows(out, todo), margin, abs_int)
-            cnt = {t: (int(v[i]), int(b[i]), int(f[i])) for i, t in enumerate(todo)}
-        dirty, guard, maybe_occ, occ_guard = set(), set(), set(), set()
-        cand_dirty, cand_guard = set(), set()     # the candidates' share of dirty / guard: what an event checks
-        deferred, ops = [], []
-
-        def defer(t):
-            deferred.append(("c", t))
-            occ_guard.add(pre_key[t])
-            if refined[t]:
-                dirty.update(writes(t)); cand_dirty.update(writes(t))
-                guard.update(reads(t)); cand_guard.update(reads(t))
-                maybe_occ.add(post_key[t]); occ_guard.add(post_key[t])
-
-        for kind, t in pending:
-            if kind == "e":
-                c = ev_cells[t]
-                dirty.update(c)
-                if not c.isdisjoint(cand_dirty) or not c.isdisjoint(cand_guard):
-                    deferred.append(("e", t))
-                    guard.update(c)
-                else:
-                    ops.append(("e", t))
-                continue
-            pk = pre_key[t]
-            if pk in occupied:
-                stage[t] = 20                       # its leaf was taken (by an earlier candidate: occupancy only grows in order)
-                continue
-            if pk in maybe_occ:
-                defer(t)
-                continue
-            if not refined[t]:
-                stage[t] = out.stage[t]             # failed in optimize or at the scale / drift gates: reads no map
-                continue
-            if not reads(t).isdisjoint(dirty):
-                defer(t)
-                continue
-            v_, b_, f_ = cnt[t]
-            counts[t] = (v_, b_, f_)
-            if not v_ >= MIN:
-                stage[t] = 23
-            elif not b_ < MIN:
-                stage[t] = 24
-            elif not (f_ >= MIN - 1 and f_ * 1.0 / int(out.n_images[t]) > 0.75):
-                stage[t] = 25
-            else:
-                k_ = post_key[t]
-                if k_ in occupied:
-                    stage[t] = 26
-                elif k_ in maybe_occ or k_ in occ_guard or not writes(t).isdisjoint(guard):
-                    counts[t] = (-1, -1, -1)
-                    defer(t)
-                else:
-                    occupied.add(k_)
-                    stage[t] = 0
-                    accepted.append(t); ops.append(("c", t))
-                    dirty.update(writes(t)); cand_dirty.update(writes(t))
-        if ops:
-            src = [(patches, pimg) if kind == "e" else (out, oimg) for kind, _ in ops]
-            sub = np.array([kind == "e" for kind, _ in ops], np.uint8)
-            batch = api.Batch(*[np.array([getattr(b, f)[t] for (b, _), (_, t) in zip(src, ops)]) for f in ("center", "normal", "scale", "n_images")],
-                              np.array([im[t] for (_, im), (_, t) in zip(src, ops)]))
-            batch.ok[:] = 1
-            if sub.any():
-                api.depth_ops_batch(scene, batch, sub)
-            else:
-                api.set_depths_batch(scene, batch)
-        deferred_log.append(len(deferred))
-        pending = deferred
-    accepted.sort()
-    return F, LevelResult(out, stage, counts, accepted, waves, deferred_log)
+    L = _level(scene, _rows(patches, F.keep), width, occupied, margin, abs_int, options or api.default_options(), key, n_levels,
+               events=_rows(patches, losers), event_cell=cell_of[losers])
+    return F, L

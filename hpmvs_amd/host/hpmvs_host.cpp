@@ -847,23 +847,20 @@ void build_conflict_graph(const RawFootprints& F, int nLevels, int maxW, int max
     csr(e_flow, G.flow_off, G.flow_adj);
     csr(e_anti, G.anti_off, G.anti_adj);
 }
-}  // namespace
-
-// Test hook (tests/test_cpu_host_logic.py; no device needed): random footprints -- blocks at the image border and beyond it,
-// writes on every pyramid level, cells that collide -- and the conflict graph of build_conflict_graph against the definition
-// itself: candidate j is a neighbour of i iff a cell key j would write is among the cell keys i reads (the vectors of
-// Scene::depthFootprints).  Returns the number of (i, j) pairs on which the two disagree (0), or -1 for bad arguments.
-extern "C" int hpmvs_host_selftest_conflict_graph(unsigned seed, int n, int n_views, int max_w, int max_h, int n_levels, int max_images, int* n_edges) {
-    if (n < 1 || n_views < 1 || max_w < 8 || max_h < 8 || n_levels < 1 || n_levels > 7 || max_images < 1) return -1;
-    RawFootprints F;
+// The random footprints of the two graph selftests below: blocks at the image border and beyond it, writes on every pyramid level,
+// cells that collide.  With isEvent, node i is an event with probability 1 / event_every (drawn first per node); without, nothing is drawn there.
+void random_footprints(unsigned seed, int n, int n_views, int max_w, int max_h, int n_levels, int max_images, int event_every,
+                       RawFootprints& F, std::vector<uint8_t>* isEvent) {
     F.n = (size_t)n; F.V = (size_t)n_views; F.M = (size_t)max_images;
     F.nimg.assign(F.n, 0);
     F.wr.assign(F.n * F.M * 4, -1); F.fr.assign(F.n * F.M * 4, -1); F.at.assign(F.n * F.M * 3, -1); F.vb.assign(F.n * F.V * 3, 0);
+    if (isEvent) isEvent->assign(F.n, 0);
     unsigned long long st = 0x9E3779B97F4A7C15ull ^ ((unsigned long long)seed * 0xD1B54A32D192ED03ull);
     auto rnd = [&](int m) { st = st * 6364136223846793005ull + 1442695040888963407ull; return (int)((st >> 33) % (unsigned long long)m); };
     // everything happens in a few small windows of the images, so that candidates really meet
     const int wx = max_w / 4 < 24 ? max_w / 4 : 24, wy = max_h / 4 < 24 ? max_h / 4 : 24;
     for (size_t i = 0; i < F.n; i++) {
+        if (isEvent) (*isEvent)[i] = rnd(event_every) == 0 ? 1 : 0;
         const int m = 1 + rnd(max_images);
         F.nimg[i] = m;
         const int corner = rnd(4);   // windows at the four corners: blocks reach outside the image there
@@ -883,6 +880,16 @@ extern "C" int hpmvs_host_selftest_conflict_graph(unsigned seed, int n, int n_vi
         for (int v = 0; v < n_views; v++)
             if (rnd(3) == 0) { int32_t* b = &F.vb[(i * F.V + (size_t)v) * 3]; b[0] = 1; b[1] = bx + rnd(wx + 3) - 1; b[2] = by + rnd(wy + 3) - 1; }
     }
+}
+}  // namespace
+
+// Test hook (tests/test_cpu_host_logic.py; no device needed): random_footprints and the conflict graph of build_conflict_graph against the definition
+// itself: candidate j is a neighbour of i iff a cell key j would write is among the cell keys i reads (the vectors of
+// Scene::depthFootprints).  Returns the number of (i, j) pairs on which the two disagree (0), or -1 for bad arguments.
+extern "C" int hpmvs_host_selftest_conflict_graph(unsigned seed, int n, int n_views, int max_w, int max_h, int n_levels, int max_images, int* n_edges) {
+    if (n < 1 || n_views < 1 || max_w < 8 || max_h < 8 || n_levels < 1 || n_levels > 7 || max_images < 1) return -1;
+    RawFootprints F;
+    random_footprints(seed, n, n_views, max_w, max_h, n_levels, max_images, 0, F, nullptr);
     ConflictGraph G;
     build_conflict_graph(F, n_levels, max_w, max_h, G);
     // the definition: cell key -> the candidates that would write it
@@ -990,36 +997,9 @@ extern "C" int hpmvs_host_selftest_event_graph(unsigned seed, int n, int n_views
                                                int event_every, int* n_edges, int* n_events) {
     if (n < 1 || n_views < 1 || max_w < 8 || max_h < 8 || n_levels < 1 || n_levels > 7 || max_images < 1 || event_every < 1) return -1;
     RawFootprints F;
-    F.n = (size_t)n; F.V = (size_t)n_views; F.M = (size_t)max_images;
-    F.nimg.assign(F.n, 0);
-    F.wr.assign(F.n * F.M * 4, -1); F.fr.assign(F.n * F.M * 4, -1); F.at.assign(F.n * F.M * 3, -1); F.vb.assign(F.n * F.V * 3, 0);
-    unsigned long long st = 0x9E3779B97F4A7C15ull ^ ((unsigned long long)seed * 0xD1B54A32D192ED03ull);
-    auto rnd = [&](int m) { st = st * 6364136223846793005ull + 1442695040888963407ull; return (int)((st >> 33) % (unsigned long long)m); };
-    const int wx = max_w / 4 < 24 ? max_w / 4 : 24, wy = max_h / 4 < 24 ? max_h / 4 : 24;
-    std::vector<uint8_t> isEvent(F.n, 0);
-    int events = 0;
-    for (size_t i = 0; i < F.n; i++) {
-        isEvent[i] = rnd(event_every) == 0 ? 1 : 0;
-        events += isEvent[i];
-        const int m = 1 + rnd(max_images);
-        F.nimg[i] = m;
-        const int corner = rnd(4);
-        const int bx = (corner & 1) ? max_w - wx - 1 : -2, by = (corner & 2) ? max_h - wy - 1 : -2;
-        for (int k = 0; k < m; k++) {
-            const int view = rnd(n_views), px = bx + rnd(wx + 3), py = by + rnd(wy + 3);
-            int32_t* a = &F.at[(i * F.M + k) * 3];
-            if (rnd(8)) { a[0] = view; a[1] = px - 1; a[2] = py - 1; }
-            const int l = rnd(n_levels);
-            const int cx = (px < 0 ? 0 : px) >> (1 + l), cy = (py < 0 ? 0 : py) >> (1 + l);
-            int32_t* w = &F.wr[(i * F.M + k) * 4];
-            if (rnd(6)) { w[0] = view; w[1] = l; w[2] = cx + rnd(2); w[3] = cy + rnd(2); }
-            const int lf = rnd(n_levels);
-            int32_t* f = &F.fr[(i * F.M + k) * 4];
-            if (rnd(6)) { f[0] = view; f[1] = lf; f[2] = ((px < 0 ? 0 : px) >> (1 + lf)) + rnd(2); f[3] = ((py < 0 ? 0 : py) >> (1 + lf)) + rnd(2); }
-        }
-        for (int v = 0; v < n_views; v++)
-            if (rnd(3) == 0) { int32_t* b = &F.vb[(i * F.V + (size_t)v) * 3]; b[0] = 1; b[1] = bx + rnd(wx + 3) - 1; b[2] = by + rnd(wy + 3) - 1; }
-    }
+    std::vector<uint8_t> isEvent;
+    random_footprints(seed, n, n_views, max_w, max_h, n_levels, max_images, event_every, F, &isEvent);
+    const int events = (int)std::count(isEvent.begin(), isEvent.end(), (uint8_t)1);
     clear_event_reads(F, isEvent);
     ConflictGraph G;
     build_conflict_graph(F, n_levels, max_w, max_h, G);
@@ -1536,7 +1516,7 @@ static bool candidate_centers(const Scene* scene, const HpmvsOptions* opt, int m
     return true;
 }
 
-// HPMVS_LEVEL_TIMES=1: extendLevel prints where its time went (stderr)
+// HPMVS_LEVEL_TIMES=1: extendLevel / filterExtendLevel print where their time went (stderr, lines that start with the method's name)
 static bool level_times() { static const bool on = [] { const char* e = getenv("HPMVS_LEVEL_TIMES"); return e && e[0] == '1'; }(); return on; }
 static double level_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -1545,58 +1525,83 @@ static uint64_t grid_leaf_key(const Eigen::Vector3f& p, float width, void*) {
     return (uint64_t)(((ix + (1 << 20)) << 42) | ((iy + (1 << 20)) << 21) | (iz + (1 << 20)));
 }
 
-bool PatchOptimizer::extendLevel(const mo3d::Patch3d* const* parents, size_t n, float width, std::unordered_set<uint64_t>& occupied,
-                                 float margin, bool absInt, LevelResult& R, bool sequential, LeafKeyFn leafKey, void* user) {
+// The deepest pyramid of the scene's cameras: the levels getFullDepth walks, so the levels a read can be on (-1: more than the gates support)
+static int pyramid_levels(const Scene* scene, const char* who) {
+    int nLevels = 1;
+    for (const Camera& c : scene->cameras_) nLevels = std::max(nLevels, c.getLevels());
+    if (nLevels > HPMVS_MAX_LEVELS) { std::cerr << "hpmvs: " << who << ": more than HPMVS_MAX_LEVELS pyramid levels" << std::endl; return -1; }
+    return nLevels;
+}
+
+// THE wave walk of the host layer (hpmvs_amd/frontier.py states the same rule over sets of cell keys): one
+// priority level of CellProcessor::extend over `parents`, with the subtraction events `events` in its queue -- event j comes right
+// before the candidates of parent eventCell[j] (non-decreasing).  extendLevel is the case without events.  The candidates' leaves, ONE
+// expandBatch, ONE footprint call over the nodes in queue order (a parent's events, then its refined candidates), the level's conflict
+// graph, then the waves: depthGates over the undecided candidates, the walk in queue order, ONE ordered setDepths.  Events need
+// sequential == true.  `who` names the calling method in the HPMVS_LEVEL_TIMES lines.
+static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, const HpmvsOptions* options, int nLevels,
+                       const Patch3d* const* parents, size_t n, const Patch3d* const* events, const size_t* eventCell, size_t nEvents,
+                       float width, std::unordered_set<uint64_t>& occupied, float margin, bool absInt, bool sequential,
+                       PatchOptimizer::LeafKeyFn leafKey, void* user, PatchOptimizer::LevelResult& R) {
     if (!leafKey) leafKey = grid_leaf_key;
     const size_t N = 6, T = n * N;
-    R = LevelResult();
+    R = PatchOptimizer::LevelResult();
     if (n == 0) return true;
+    if (nEvents && !sequential) return false;
     const double t_begin = level_now();
-    std::vector<CellRef> cells(n);
+    std::vector<PatchOptimizer::CellRef> cells(n);
     for (size_t i = 0; i < n; i++) { cells[i].c = Eigen::Vector3f(0.0f, 0.0f, 0.0f); cells[i].width = width; }
     // the candidates before optimize (everything skipped: constructed only) -> their leaves
     std::vector<uint8_t> skip(T, 0), refined;
     std::vector<float> pre, widths(n, width);
-    if (!candidate_centers(scene_p, options_p, (int)EXTEND, parents, widths.data(), n, pre)) return false;
+    if (!candidate_centers(scene, options, (int)PatchOptimizer::EXTEND, parents, widths.data(), n, pre)) return false;
     std::vector<uint64_t> preKey(T), postKey(T, 0);
     for (size_t t = 0; t < T; t++) {
         preKey[t] = leafKey(Eigen::Vector3f(pre[3 * t], pre[3 * t + 1], pre[3 * t + 2]), width, user);
         skip[t] = occupied.count(preKey[t]) ? 1 : 0;   // level-start occupancy: those are never refined
     }
     const double t_pre = level_now();
-    expandBatch(EXTEND, parents, cells.data(), n, skip.data(), R.candidates, refined);
+    po.expandBatch(PatchOptimizer::EXTEND, parents, cells.data(), n, skip.data(), R.candidates, refined);
     if (R.candidates.size() != T) return false;
     const double t_ref = level_now();
-    std::vector<const Patch3d*> ptr(T);
-    for (size_t t = 0; t < T; t++) {
-        ptr[t] = &R.candidates[t];
-        if (skip[t]) refined[t] = 0;
-        if (refined[t]) postKey[t] = leafKey(Eigen::Vector3f(R.candidates[t].center_[0], R.candidates[t].center_[1], R.candidates[t].center_[2]), width, user);
-    }
-    // footprints of the REFINED candidates only (the others read and write no map), as the device returns them
-    const int nLevels = 6;
-    std::vector<const Patch3d*> rptr;
+    // the footprinted nodes in queue order: per parent its events, then its REFINED candidates (the others read and write no map);
+    // pending items: t < T a candidate, T + node an event
+    std::vector<const Patch3d*> nodes;
+    std::vector<uint8_t> isEvent;
     std::vector<int> fpi(T, -1);
-    for (size_t t = 0; t < T; t++) if (refined[t]) { fpi[t] = (int)rptr.size(); rptr.push_back(ptr[t]); }
-    RawFootprints F;
-    if (!raw_footprints(*scene_p, rptr.data(), rptr.size(), F)) return false;
-    const double t_fp = level_now();
+    std::vector<size_t> pending;
     R.stage.assign(T, 1);
     R.counts.assign(3 * T, -1);
-    std::vector<size_t> pending;
-    for (size_t t = 0; t < T; t++) { if (skip[t]) R.stage[t] = 20; else pending.push_back(t); }
-    const int MIN = options_p->MIN_IMAGES_PER_PATCH;
+    for (size_t i = 0, j = 0; i < n; i++) {
+        for (; j < nEvents && eventCell[j] == i; j++) { pending.push_back(T + nodes.size()); nodes.push_back(events[j]); isEvent.push_back(1); }
+        for (size_t t = N * i; t < N * (i + 1); t++) {
+            if (skip[t]) { refined[t] = 0; R.stage[t] = 20; continue; }
+            if (refined[t]) {
+                postKey[t] = leafKey(Eigen::Vector3f(R.candidates[t].center_[0], R.candidates[t].center_[1], R.candidates[t].center_[2]), width, user);
+                fpi[t] = (int)nodes.size(); nodes.push_back(&R.candidates[t]); isEvent.push_back(0);
+            }
+            pending.push_back(t);
+        }
+    }
+    RawFootprints F;
+    if (!raw_footprints(*scene, nodes.data(), nodes.size(), F)) return false;
+    const double t_fp = level_now();
     // the level's conflict graph (who writes what whom reads): once, from the footprints
     ConflictGraph G;
-    {
+    if (sequential && F.n > 0) {   // (the plain frontier round decides everything in one wave)
         int maxW = 1, maxH = 1;
-        for (const Image& im : scene_p->images_) { maxW = std::max(maxW, im.getWidth()); maxH = std::max(maxH, im.getHeight()); }
-        if (sequential && F.n > 0) build_conflict_graph(F, nLevels, maxW, maxH, G);   // (the plain frontier round decides everything in one wave)
+        for (const Image& im : scene->images_) { maxW = std::max(maxW, im.getWidth()); maxH = std::max(maxH, im.getHeight()); }
+        if (nEvents) clear_event_reads(F, isEvent);
+        build_conflict_graph(F, nLevels, maxW, maxH, G);
+        if (nEvents) add_event_edges(F, isEvent, G);
     }
     const double t_graph = level_now();
-    // open[i] == w: candidate i (footprint index) was accepted or deferred in wave w -- its writes are not in the maps this wave's
-    // counts were read from (`dirty`); defer_w[i] == w: it was deferred in wave w -- nobody may overwrite what it reads (`guard`)
-    std::vector<int> open(rptr.size(), 0), defer_w(rptr.size(), 0);
+    const int MIN = options->MIN_IMAGES_PER_PATCH;
+    // open[i] == w: node i was accepted, applied or deferred in wave w -- its writes are not in the maps this wave's counts were read
+    // from (`dirty`); defer_w[i] == w: it was deferred in wave w -- nobody may overwrite what it reads, no addition may overtake its
+    // subtraction (`guard`).  For an event, flow lists only candidates, so its tests are those of §3.9: an earlier candidate accepted or
+    // deferred that writes its cells, an earlier deferred candidate that reads them.
+    std::vector<int> open(nodes.size(), 0), defer_w(nodes.size(), 0);
     FlatSet maybeOcc, occGuard;
     auto reads_hit_dirty = [&](size_t i, int wave) {
         for (uint32_t q = G.flow_off[i]; q < G.flow_off[i + 1]; q++) if (open[G.flow_adj[q]] == wave) return true;
@@ -1611,18 +1616,22 @@ bool PatchOptimizer::extendLevel(const mo3d::Patch3d* const* parents, size_t n, 
         R.waves++;
         double w0 = level_now();
         std::vector<size_t> todo;
-        for (size_t t : pending) if (refined[t]) todo.push_back(t);
+        for (size_t t : pending) if (t < T && refined[t]) todo.push_back(t);
         std::vector<int> v, b, f;
         std::vector<const Patch3d*> sub(todo.size());
-        for (size_t k = 0; k < todo.size(); k++) sub[k] = ptr[todo[k]];
-        if (!todo.empty() && !scene_p->depthGates(sub.data(), sub.size(), margin, v, b, f, absInt)) return false;
+        for (size_t k = 0; k < todo.size(); k++) sub[k] = &R.candidates[todo[k]];
+        if (!todo.empty() && !scene->depthGates(sub.data(), sub.size(), margin, v, b, f, absInt)) return false;
         std::vector<int> slot(T, -1);
         for (size_t k = 0; k < todo.size(); k++) slot[todo[k]] = (int)k;
         double w1 = level_now();
         t_gates += w1 - w0;
         maybeOcc.clear(); occGuard.clear();
         const int wave = R.waves;
-        std::vector<size_t> deferred, accNow;
+        const size_t accBefore = R.accepted.size();
+        std::vector<size_t> deferred;
+        std::vector<const Patch3d*> ops;   // the wave's accepted additions and applied subtractions, in queue order
+        std::vector<uint8_t> opSub;
+        bool anySub = false;
         auto defer = [&](size_t t) {
             deferred.push_back(t);
             occGuard.add(preKey[t]);
@@ -1632,6 +1641,13 @@ bool PatchOptimizer::extendLevel(const mo3d::Patch3d* const* parents, size_t n, 
             }
         };
         for (size_t t : pending) {
+            if (t >= T) {   // a subtraction event: always passes, occupies no leaf
+                const size_t e = t - T;
+                open[e] = wave;
+                if (reads_hit_dirty(e, wave) || writes_hit_guard(e, wave)) { defer_w[e] = wave; deferred.push_back(t); }
+                else { ops.push_back(nodes[e]); opSub.push_back(1); anySub = true; }
+                continue;
+            }
             if (occupied.count(preKey[t])) { R.stage[t] = 20; continue; }   // its leaf was taken by an earlier candidate
             if (sequential && maybeOcc.has(preKey[t])) { defer(t); continue; }
             if (!refined[t]) { R.stage[t] = 1; continue; }                  // failed in optimize or at the scale / drift gates
@@ -1649,29 +1665,36 @@ bool PatchOptimizer::extendLevel(const mo3d::Patch3d* const* parents, size_t n, 
             } else {
                 occupied.insert(postKey[t]);
                 R.stage[t] = 0;
-                R.accepted.push_back(t); accNow.push_back(t);
+                R.accepted.push_back(t);
+                ops.push_back(&R.candidates[t]); opSub.push_back(0);
                 open[(size_t)fpi[t]] = wave;
             }
         }
         double w2 = level_now();
         t_walk += w2 - w1;
-        if (!accNow.empty()) {
-            std::vector<const Patch3d*> ap(accNow.size());
-            for (size_t k = 0; k < accNow.size(); k++) ap[k] = ptr[accNow[k]];
-            if (!scene_p->setDepths(ap.data(), ap.size())) return false;
-        }
+        // (additions only: setDepths' plain batch)
+        if (!ops.empty() && !scene->setDepths(ops.data(), ops.size(), anySub ? opSub.data() : nullptr)) return false;
         t_set += level_now() - w2;
-        if (level_times()) std::fprintf(stderr, "extendLevel wave %d: %zu pending (%zu refined), %zu accepted, %zu deferred\n",
-                                        R.waves, pending.size(), todo.size(), accNow.size(), deferred.size());
+        if (level_times()) std::fprintf(stderr, "%s wave %d: %zu pending (%zu refined), %zu accepted, %zu deferred\n",
+                                        who, R.waves, pending.size(), todo.size(), R.accepted.size() - accBefore, deferred.size());
         pending.swap(deferred);
     }
     if (level_times())
-        std::fprintf(stderr, "extendLevel %zu candidates (%zu refined): candidates' leaves %.1f ms, refinement %.1f ms, footprints %.1f ms, "
-                             "conflict graph %.1f ms (%zu + %zu edges), waves: gates %.1f ms, walk %.1f ms, setDepths %.1f ms\n", T, rptr.size(),
+        std::fprintf(stderr, "%s %zu candidates (%zu refined): candidates' leaves %.1f ms, refinement %.1f ms, footprints %.1f ms, "
+                             "conflict graph %.1f ms (%zu + %zu edges), waves: gates %.1f ms, walk %.1f ms, setDepths %.1f ms\n", who, T, nodes.size() - nEvents,
                      1e3 * (t_pre - t_begin), 1e3 * (t_ref - t_pre), 1e3 * (t_fp - t_ref), 1e3 * (t_graph - t_fp), G.flow_adj.size(), G.anti_adj.size(),
                      1e3 * t_gates, 1e3 * t_walk, 1e3 * t_set);
     std::sort(R.accepted.begin(), R.accepted.end());
     return true;
+}
+
+bool PatchOptimizer::extendLevel(const mo3d::Patch3d* const* parents, size_t n, float width, std::unordered_set<uint64_t>& occupied,
+                                 float margin, bool absInt, LevelResult& R, bool sequential, LeafKeyFn leafKey, void* user) {
+    R = LevelResult();
+    const int nLevels = pyramid_levels(scene_p, "extendLevel");
+    if (nLevels < 0) return false;
+    return walk_level("extendLevel", *this, scene_p, options_p, nLevels, parents, n, nullptr, nullptr, 0, width, occupied, margin, absInt,
+                      sequential, leafKey, user, R);
 }
 
 // ---------------------------------------------------------------- filter
@@ -1718,138 +1741,24 @@ bool PatchOptimizer::filterLevel(mo3d::Patch3d* const* patches, const size_t* ce
 bool PatchOptimizer::filterExtendLevel(mo3d::Patch3d* const* patches, const size_t* cellStart, size_t nCells, float width,
                                        std::unordered_set<uint64_t>& occupied, float margin, bool absInt, FilterResult& FR, LevelResult& R,
                                        LeafKeyFn leafKey, void* user) {
-    if (!leafKey) leafKey = grid_leaf_key;
     R = LevelResult();
-    int nLevels = 1;
-    for (const Camera& c : scene_p->cameras_) nLevels = std::max(nLevels, c.getLevels());
-    if (nLevels > HPMVS_MAX_LEVELS) { std::cerr << "hpmvs: filterExtendLevel: more than HPMVS_MAX_LEVELS pyramid levels" << std::endl; return false; }
+    const int nLevels = pyramid_levels(scene_p, "filterExtendLevel");
+    if (nLevels < 0) return false;
     if (cellStart)
         for (size_t c = 0; c < nCells; c++)
             if (cellStart[c + 1] == cellStart[c]) { std::cerr << "hpmvs: filterExtendLevel: cell " << c << " is empty" << std::endl; return false; }
     if (!run_filter(scene_p, patches, cellStart, nCells, FR, "filterExtendLevel")) return false;
-    const size_t n = nCells, N = 6, T = n * N;
-    std::vector<const Patch3d*> parents(n);
-    for (size_t i = 0; i < n; i++) {
+    // the kept patches are the parents, the losers the events of their cell (before its candidates)
+    std::vector<const Patch3d*> parents(nCells), losers;
+    std::vector<size_t> loserCell;
+    for (size_t i = 0; i < nCells; i++) {
         parents[i] = patches[(size_t)FR.keep[i]];
         if (parents[i]->expanded_) { std::cerr << "hpmvs: filterExtendLevel: the kept patch of cell " << i << " is already expanded" << std::endl; return false; }
+        for (size_t r = cellStart[i]; r < cellStart[i + 1]; r++) if (FR.removed[r]) { losers.push_back(patches[r]); loserCell.push_back(i); }
     }
-    if (n == 0) return true;
-    // extendLevel's candidate steps over the kept patches
-    std::vector<CellRef> cells(n);
-    for (size_t i = 0; i < n; i++) { cells[i].c = Eigen::Vector3f(0.0f, 0.0f, 0.0f); cells[i].width = width; }
-    std::vector<uint8_t> skip(T, 0), refined;
-    std::vector<float> pre, widths(n, width);
-    if (!candidate_centers(scene_p, options_p, (int)EXTEND, parents.data(), widths.data(), n, pre)) return false;
-    std::vector<uint64_t> preKey(T), postKey(T, 0);
-    for (size_t t = 0; t < T; t++) {
-        preKey[t] = leafKey(Eigen::Vector3f(pre[3 * t], pre[3 * t + 1], pre[3 * t + 2]), width, user);
-        skip[t] = occupied.count(preKey[t]) ? 1 : 0;
-    }
-    expandBatch(EXTEND, parents.data(), cells.data(), n, skip.data(), R.candidates, refined);
-    if (R.candidates.size() != T) return false;
-    for (size_t t = 0; t < T; t++) {
-        if (skip[t]) refined[t] = 0;
-        if (refined[t]) postKey[t] = leafKey(Eigen::Vector3f(R.candidates[t].center_[0], R.candidates[t].center_[1], R.candidates[t].center_[2]), width, user);
-    }
-    // the footprinted nodes in queue order: per cell its losers (events), then its refined candidates; ONE footprint call
-    std::vector<const Patch3d*> nodes;
-    std::vector<uint8_t> isEvent;
-    std::vector<int> fpi(T, -1);
-    std::vector<size_t> queue;   // pending items: t < T a candidate, T + node an event
-    for (size_t i = 0; i < n; i++) {
-        for (size_t r = cellStart[i]; r < cellStart[i + 1]; r++)
-            if (FR.removed[r]) { queue.push_back(T + nodes.size()); nodes.push_back(patches[r]); isEvent.push_back(1); }
-        for (size_t t = N * i; t < N * (i + 1); t++) {
-            if (refined[t]) { fpi[t] = (int)nodes.size(); nodes.push_back(&R.candidates[t]); isEvent.push_back(0); }
-            if (!skip[t]) queue.push_back(t);
-        }
-    }
-    RawFootprints F;
-    if (!raw_footprints(*scene_p, nodes.data(), nodes.size(), F)) return false;
-    clear_event_reads(F, isEvent);
-    ConflictGraph G;
-    {
-        int maxW = 1, maxH = 1;
-        for (const Image& im : scene_p->images_) { maxW = std::max(maxW, im.getWidth()); maxH = std::max(maxH, im.getHeight()); }
-        if (F.n > 0) { build_conflict_graph(F, nLevels, maxW, maxH, G); add_event_edges(F, isEvent, G); }
-    }
-    R.stage.assign(T, 1);
-    R.counts.assign(3 * T, -1);
-    for (size_t t = 0; t < T; t++) if (skip[t]) R.stage[t] = 20;
-    const int MIN = options_p->MIN_IMAGES_PER_PATCH;
-    // open[i] == w: node i was accepted, applied or deferred in wave w (`dirty`); defer_w[i] == w: deferred in wave w (`guard`).  For an
-    // event, flow lists only candidates, so its tests are those of §3.9: an earlier candidate accepted or deferred that writes its cells,
-    // an earlier deferred candidate that reads them.
-    std::vector<int> open(nodes.size(), 0), defer_w(nodes.size(), 0);
-    FlatSet maybeOcc, occGuard;
-    auto reads_hit_dirty = [&](size_t i, int wave) {
-        for (uint32_t q = G.flow_off[i]; q < G.flow_off[i + 1]; q++) if (open[G.flow_adj[q]] == wave) return true;
+    if (!walk_level("filterExtendLevel", *this, scene_p, options_p, nLevels, parents.data(), nCells, losers.data(), loserCell.data(), losers.size(),
+                    width, occupied, margin, absInt, true, leafKey, user, R))
         return false;
-    };
-    auto writes_hit_guard = [&](size_t i, int wave) {
-        for (uint32_t q = G.anti_off[i]; q < G.anti_off[i + 1]; q++) if (defer_w[G.anti_adj[q]] == wave) return true;
-        return false;
-    };
-    std::vector<size_t> pending = queue;
-    while (!pending.empty()) {
-        R.waves++;
-        std::vector<size_t> todo;
-        for (size_t t : pending) if (t < T && refined[t]) todo.push_back(t);
-        std::vector<int> v, b, f;
-        std::vector<const Patch3d*> sub(todo.size());
-        for (size_t k = 0; k < todo.size(); k++) sub[k] = &R.candidates[todo[k]];
-        if (!todo.empty() && !scene_p->depthGates(sub.data(), sub.size(), margin, v, b, f, absInt)) return false;
-        std::vector<int> slot(T, -1);
-        for (size_t k = 0; k < todo.size(); k++) slot[todo[k]] = (int)k;
-        maybeOcc.clear(); occGuard.clear();
-        const int wave = R.waves;
-        std::vector<size_t> deferred;
-        std::vector<const Patch3d*> ops;
-        std::vector<uint8_t> opSub;
-        auto defer = [&](size_t t) {
-            deferred.push_back(t);
-            occGuard.add(preKey[t]);
-            if (refined[t]) {
-                open[(size_t)fpi[t]] = wave; defer_w[(size_t)fpi[t]] = wave;
-                maybeOcc.add(postKey[t]); occGuard.add(postKey[t]);
-            }
-        };
-        for (size_t t : pending) {
-            if (t >= T) {   // a subtraction event: always passes, occupies no leaf
-                const size_t e = t - T;
-                open[e] = wave;
-                if (reads_hit_dirty(e, wave) || writes_hit_guard(e, wave)) { defer_w[e] = wave; deferred.push_back(t); }
-                else { ops.push_back(nodes[e]); opSub.push_back(1); }
-                continue;
-            }
-            if (occupied.count(preKey[t])) { R.stage[t] = 20; continue; }
-            if (maybeOcc.has(preKey[t])) { defer(t); continue; }
-            if (!refined[t]) { R.stage[t] = 1; continue; }
-            if (reads_hit_dirty((size_t)fpi[t], wave)) { defer(t); continue; }
-            const int k = slot[t];
-            const int cv = v[k], cb = b[k], cf = f[k];
-            R.counts[3 * t] = cv; R.counts[3 * t + 1] = cb; R.counts[3 * t + 2] = cf;
-            if (!(cv >= MIN)) R.stage[t] = 23;
-            else if (!(cb < MIN)) R.stage[t] = 24;
-            else if (!(cf >= MIN - 1 && cf * 1.0 / (double)R.candidates[t].images_.size() > 0.75)) R.stage[t] = 25;
-            else if (occupied.count(postKey[t])) R.stage[t] = 26;
-            else if (maybeOcc.has(postKey[t]) || occGuard.has(postKey[t]) || writes_hit_guard((size_t)fpi[t], wave)) {
-                R.counts[3 * t] = R.counts[3 * t + 1] = R.counts[3 * t + 2] = -1;
-                defer(t);
-            } else {
-                occupied.insert(postKey[t]);
-                R.stage[t] = 0;
-                R.accepted.push_back(t);
-                ops.push_back(&R.candidates[t]); opSub.push_back(0);
-                open[(size_t)fpi[t]] = wave;
-            }
-        }
-        // the wave's accepted additions and applied subtractions, in queue order
-        const bool anySub = std::find(opSub.begin(), opSub.end(), (uint8_t)1) != opSub.end();   // (additions only: setDepths' plain batch)
-        if (!ops.empty() && !scene_p->setDepths(ops.data(), ops.size(), anySub ? opSub.data() : nullptr)) return false;
-        pending.swap(deferred);
-    }
-    std::sort(R.accepted.begin(), R.accepted.end());
     for (size_t i = 0; i < FR.removed.size(); i++) if (FR.removed[i]) patches[i]->images_.clear();   // images_.clear() (:72)
     return true;
 }

@@ -38,7 +38,9 @@ public:
     // one priority and runs it on each, one after the other) as a BATCHED frontier with the reference's SEQUENTIAL result: ONE
     // expandBatch for the level, then conflict-free waves of depthGates / walk in the reference's order / setDepths (a candidate is
     // decided unless a map cell it reads or would write, or its leaf, still depends on an undecided earlier candidate -- then it
-    // waits for the next wave; hpmvs_amd/frontier.py is the same walk in Python, INTEGRATION.md has the argument).  parents: the
+    // waits for the next wave; hpmvs_amd/frontier.py is the same walk in Python, INTEGRATION.md has the argument).  The walk exists once
+    // in the host layer, over a queue of candidates and subtraction events: this is its case without events, filterExtendLevel the one
+    // with.  The pyramid levels a read can be on are the scene's cameras' (false beyond HPMVS_MAX_LEVELS).  parents: the
     // leaves' patches in the scheduler's order; width: the leaves' width; `occupied`: the scheduler's occupancy as a set of leaf
     // keys, updated in place (the octree itself stays with the scheduler: `leafKey` maps a point to its leaf, default = the
     // uniform grid floor(p / width)); the scene's depth maps (Scene::resetDepths / setDepths) receive the accepted candidates.
@@ -119,9 +121,9 @@ public:
     // filter for every cell as ONE hpmvs_filter_batch, then the losers' depths taken back in ONE ordered Scene::setDepths(..., subtract).
     // false (nothing changed) for malformed offsets or a cell with no winner (the reference would keep a null pointer).
     bool filterLevel(mo3d::Patch3d* const* patches, const size_t* cellStart, size_t nCells, FilterResult& out);
-    // filter cell i, then CellProcessor::extend on its kept patch, for every cell in queue order: ONE filter call, extendLevel's candidate
-    // steps over the kept patches, and extendLevel's wave walk over a conflict graph that also holds the losers as subtraction events
-    // (DESIGN.md §3.9).  `level` is laid out as extendLevel's, the kept patches being the parents.  false before any map update for
+    // filter cell i, then CellProcessor::extend on its kept patch, for every cell in queue order: ONE filter call, then the walk of
+    // extendLevel over the kept patches with the losers in its queue and its conflict graph as subtraction events, each right before its
+    // cell's candidates.  `level` is laid out as extendLevel's, the kept patches being the parents.  false before any map update for
     // malformed offsets, an empty cell, a cell with no winner or a kept patch that is already expanded (processCell does not extend it).
     bool filterExtendLevel(mo3d::Patch3d* const* patches, const size_t* cellStart, size_t nCells, float width,
                            std::unordered_set<uint64_t>& occupied, float margin, bool absInt, FilterResult& filter, LevelResult& level,
