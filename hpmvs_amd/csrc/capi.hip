@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <time.h>
@@ -509,8 +510,8 @@ namespace {
 // hipMalloc / hipFree (and friends) wait for the device to be idle -- which it never is while single-patch callers keep an
 // open batch running (a second one starts while the first drains).  Whatever allocates or frees while a scene is in use
 // does it in an Exclusive scope: the scene lock (nobody can start an open batch meanwhile, service_open needs it) with
-// the open batches ended and drained.  A host-staged call is in such a scope twice, briefly: for its allocations and (in
-// ~Staged) for its frees; its copies, its launch and its wait run outside, so that concurrent big host batches against
+// the open batches ended and drained.  A host-staged call is in such a scope twice, briefly: for its allocations and for
+// its frees (Call below); its copies, its launch and its wait run outside, so that concurrent big host batches against
 // one scene overlap.
 struct Exclusive {
     const hpmvs_scene* s;
@@ -518,21 +519,6 @@ struct Exclusive {
     ~Exclusive() { if (s) s->mu.unlock(); }
     Exclusive(const Exclusive&) = delete;
     Exclusive& operator=(const Exclusive&) = delete;
-};
-
-struct Staged {
-    DevBatch d;
-    std::vector<void*> tmp;
-    struct Fill { void* dst; const void* src; size_t bytes; };  // src == nullptr: zero-fill
-    std::vector<Fill> fills;  // what stage_in allocated still has to be filled: stage_flush, outside the Exclusive scope
-    bool staged = false;
-    size_t staged_bytes = 0, mapped_bytes = 0;  // arrays copied through device buffers / used in place (pinned host memory)
-    const hpmvs_scene* scene = nullptr;  // set by calls against a scene: the buffers are freed in an Exclusive scope
-    ~Staged() {
-        if (tmp.empty()) return;
-        Exclusive ex(scene);
-        for (void* p : tmp) hipFree(p);
-    }
 };
 
 // Device address of [host, host + bytes) when the whole range lies in pinned host memory that is mapped into the GPU's
@@ -562,58 +548,164 @@ static void* mapped_host(const void* host, size_t bytes) {
     return d0;
 }
 
-// copy: the array is an input (its contents travel to the device).  need_zero: an output the kernel may leave untouched for
-// some patches (e.g. `color` of a failed one), which a staged call returns as 0.  allow_mapped = false: `host` only stands
-// for "non-null", the range behind it is not the caller's.
-template <typename T>
-int stage_in(Staged& st, T*& dst, const T* host, size_t count, bool copy, bool need_zero = true, bool allow_mapped = true) {
-    dst = nullptr;
-    if (!host || count == 0) return HPMVS_OK;
-    if (allow_mapped) {
-        if (void* m = mapped_host(host, sizeof(T) * count)) {
-            dst = (T*)m;
-            if (!copy && need_zero) st.fills.push_back({m, nullptr, sizeof(T) * count});
-            st.mapped_bytes += sizeof(T) * count;
-            return HPMVS_OK;
+DevBatch as_dev_batch(const hpmvs_patch_batch* b) {
+    DevBatch d;
+    memset(&d, 0, sizeof(d));
+    d.n = b->n; d.max_images = b->max_images;
+    d.center = b->center; d.normal = b->normal; d.scale = b->scale; d.n_images = b->n_images; d.images = b->images;
+    d.ok = b->ok; d.color = b->color; d.ncc = b->ncc; d.fmin = b->fmin; d.x = b->x; d.result = b->result;
+    d.nevals = b->nevals; d.stage = b->stage; d.ngrabs = b->ngrabs;
+    return d;
+}
+
+// One call of a batch entry point, for both forms of its arguments.  With device pointers (on_device) every array is handed
+// through as it is and nothing is allocated; with host pointers an array in pinned, mapped memory is used in place
+// (mapped_host) and any other one travels through a device buffer of this call.  An entry point declares its arrays (batch /
+// in / out / arr / scratch), calls begin(), launches once and returns finish(); of the form it is in it knows only what belongs
+// to one form alone (filter_batch's offset verdict, init_patches_batch reading meas_off on the host, hpmvs_last_staging).
+// A host-pointer call is in an Exclusive scope from its construction to begin() -- its allocations, and what drains the open
+// batches ahead of it even when every array turns out to be pinned; a device-pointer call enters one only when it asks for
+// scratch.  The destructor frees in a scope of its own.  The fills, the launch, the wait and the copies back run outside
+// (two threads staging big host batches against one scene overlap them, 16 workspaces; they only take turns at hipMalloc /
+// hipFree).  A failed allocation is remembered, the declarations after it do nothing and begin() returns it; every exit path
+// frees what was allocated.
+class Call {
+public:
+    // kCopyIn: an input, its contents travel to the device.  kZero: an output the kernel may leave untouched for some
+    // patches (e.g. `color` of a failed one), which the call returns as 0; it decides for an array used in place -- a device
+    // buffer that is not an input is always cleared.  kCopyBack: an output.
+    enum : unsigned { kCopyIn = 1, kZero = 2, kCopyBack = 4 };
+    // How a patch batch takes part.  kRead: its five input arrays.  kRefine (hpmvs_optimize_batch): the inputs travel both
+    // ways, scale only in; the refinement kernel writes ok / fmin / x / result / nevals / stage / ngrabs of EVERY patch
+    // (fetch and finish stages), so of the outputs only color and ncc are cleared.  kCreate: the call writes all fourteen
+    // arrays, nothing travels in.
+    enum Role { kRead, kRefine, kCreate };
+    size_t staged_bytes = 0, mapped_bytes = 0;  // host arrays copied through device buffers / used in place
+
+    Call(const hpmvs_scene* s, int on_device, hipStream_t st) : scene_(s), st_(st), device_(on_device != 0) {
+        if (!device_) { scope_.emplace(s); arrs_.reserve(24); }
+    }
+    ~Call() {
+        scope_.reset();
+        if (!owned_) return;
+        Exclusive ex(scene_);
+        for (const Arr& a : arrs_)
+            if (a.owned) hipFree(a.dev);
+    }
+    Call(const Call&) = delete;
+    Call& operator=(const Call&) = delete;
+
+    // the device address of an array of the caller's; a null or empty one stays null
+    template <typename T>
+    T* arr(const T* host, size_t count, unsigned flags) {
+        if (device_) return const_cast<T*>(host);
+        if (rc_ || !host || count == 0) return nullptr;
+        const size_t bytes = sizeof(T) * count;
+        if (void* m = mapped_host(host, bytes)) {
+            mapped_bytes += bytes;
+            if (flags & kZero) arrs_.push_back({m, nullptr, nullptr, bytes, false, true});
+            return (T*)m;
         }
+        staged_bytes += bytes;
+        const bool input = (flags & kCopyIn) != 0;
+        return (T*)alloc(bytes, input ? host : nullptr, !input, (flags & kCopyBack) ? const_cast<T*>(host) : nullptr);
     }
-    st.staged_bytes += sizeof(T) * count;
-    void* p = nullptr;
-    HIPCHK(hipMalloc(&p, sizeof(T) * count));
-    st.tmp.push_back(p);
-    st.fills.push_back({p, copy ? (const void*)host : nullptr, sizeof(T) * count});
-    dst = (T*)p;
-    return HPMVS_OK;
-}
+    template <typename T> T* in(const T* host, size_t count) { return arr(host, count, kCopyIn); }
+    template <typename T> T* out(T* host, size_t count) { return arr(host, count, kZero | kCopyBack); }
 
-// The copies / zero-fills of everything stage_in allocated.  Separate from the allocations so that only those (and the
-// frees) run in the Exclusive scope: two threads staging big host batches against one scene overlap their copies and
-// their launches (16 workspaces), they only take turns at hipMalloc / hipFree.
-// With a launch stream the fills are issued ON it (ordered with the launch, and not waiting behind an open-batch kernel the
-// way null-stream work can: ADVICE r4); a pageable source is consumed before hipMemcpyAsync returns.
-int stage_flush(Staged& st, hipStream_t on = nullptr) {
-    bool null_fill = false;
-    for (const Staged::Fill& f : st.fills) {
-        if (on) {
-            if (f.src) HIPCHK(hipMemcpyAsync(f.dst, f.src, f.bytes, hipMemcpyHostToDevice, on));
-            else HIPCHK(hipMemsetAsync(f.dst, 0, f.bytes, on));
-        } else if (f.src) { HIPCHK(hipMemcpy(f.dst, f.src, f.bytes, hipMemcpyHostToDevice)); null_fill = true; }
-        else { HIPCHK(hipMemset(f.dst, 0, f.bytes)); null_fill = true; }
+    DevBatch batch(const hpmvs_patch_batch* b, Role role) {
+        if (device_) return as_dev_batch(b);  // all fourteen pointers, whatever the role
+        DevBatch d;
+        memset(&d, 0, sizeof(d));
+        d.n = b->n; d.max_images = b->max_images;
+        const size_t n = (size_t)b->n;
+        const unsigned io = role == kRead ? kCopyIn : role == kRefine ? kCopyIn | kCopyBack : kZero | kCopyBack;
+        d.center = arr(b->center, 4 * n, io);
+        d.normal = arr(b->normal, 4 * n, io);
+        d.scale = arr(b->scale, n, role == kRefine ? kCopyIn : io);
+        d.n_images = arr(b->n_images, n, io);
+        d.images = arr(b->images, n * b->max_images, io);
+        if (role == kRead) return d;
+        const unsigned every = role == kRefine ? kCopyBack : kZero | kCopyBack;  // (written for every patch: no fill)
+        d.ok = arr(b->ok, n, every);
+        d.color = out(b->color, 3 * n);
+        d.ncc = out(b->ncc, n);
+        d.fmin = arr(b->fmin, n, every);
+        d.x = arr(b->x, 3 * n, every);
+        d.result = arr(b->result, n, every);
+        d.nevals = arr(b->nevals, n, every);
+        d.stage = arr(b->stage, n, every);
+        d.ngrabs = arr(b->ngrabs, n, every);
+        return d;
     }
-    // a null-stream fill may return before it has run (hipMemset always, a copy from pageable memory once it is staged); the launch
-    // that follows may go to a non-blocking stream of the caller's
-    if (null_fill) HIPCHK(hipStreamSynchronize(nullptr));
-    st.fills.clear();
-    return HPMVS_OK;
-}
 
-template <typename T>
-int stage_out(T* host, const T* dev, size_t count) {
-    if (!host || !dev || count == 0) return HPMVS_OK;
-    if ((const void*)dev == mapped_host(host, sizeof(T) * count)) return HPMVS_OK;  // used in place (stage_in)
-    HIPCHK(hipMemcpy(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost));
-    return HPMVS_OK;
-}
+    // device memory of the call's own, in both forms, never the caller's; freed with the call.  Also after begin(), then in a
+    // scope of its own and without the zero fill.
+    void* scratch(size_t bytes, bool zero = false) {
+        if (rc_ || bytes == 0) return nullptr;
+        const bool enter = !scope_;
+        if (enter) scope_.emplace(scene_);
+        void* p = alloc(bytes, nullptr, zero, nullptr);
+        if (enter && begun_) scope_.reset();
+        return p;
+    }
+    int error() const { return rc_; }
+
+    // Leaves the Exclusive scope and issues the copies / zero fills of what was declared.  With a stream they go ON it (ordered
+    // with the launch, and not waiting behind an open-batch kernel the way null-stream work can: ADVICE r4; a pageable source
+    // is consumed before hipMemcpyAsync returns): hpmvs_optimize_batch and hpmvs_filter_batch.  The other entries fill on the
+    // null stream and wait for it, as they always have; the launch stream is probably right for them too, but that changes
+    // their order against open-batch kernels and is left for a change of its own.
+    int begin(hipStream_t on = nullptr) {
+        scope_.reset();
+        begun_ = true;
+        if (rc_) return rc_;
+        bool null_fill = false;
+        for (const Arr& a : arrs_) {
+            if (!a.src && !a.zero) continue;
+            if (on) {
+                if (a.src) HIPCHK(hipMemcpyAsync(a.dev, a.src, a.bytes, hipMemcpyHostToDevice, on));
+                else HIPCHK(hipMemsetAsync(a.dev, 0, a.bytes, on));
+            } else if (a.src) { HIPCHK(hipMemcpy(a.dev, a.src, a.bytes, hipMemcpyHostToDevice)); null_fill = true; }
+            else { HIPCHK(hipMemset(a.dev, 0, a.bytes)); null_fill = true; }
+        }
+        // a null-stream fill may return before it has run (hipMemset always, a copy from pageable memory once it is staged); the launch
+        // that follows may go to a non-blocking stream of the caller's
+        if (null_fill) HIPCHK(hipStreamSynchronize(nullptr));
+        return HPMVS_OK;
+    }
+
+    // After the launch.  Host pointers: waits for the stream and copies back the outputs that went through device buffers
+    // (those used in place are where they belong already).  Device pointers: returns at once, unless the call owns scratch
+    // its kernels may still be using.
+    int finish() {
+        if (!device_ || owned_) HIPCHK(hipStreamSynchronize(st_));
+        for (const Arr& a : arrs_)
+            if (a.back) HIPCHK(hipMemcpy(a.back, a.dev, a.bytes, hipMemcpyDeviceToHost));
+        return HPMVS_OK;
+    }
+
+private:
+    struct Arr { void* dev; const void* src; void* back; size_t bytes; bool owned, zero; };  // src: copied in; back: copied back
+    static int device_alloc(void** p, size_t bytes) {
+        HIPCHK(hipMalloc(p, bytes));
+        return HPMVS_OK;
+    }
+    void* alloc(size_t bytes, const void* src, bool zero, void* back) {
+        void* p = nullptr;
+        if ((rc_ = device_alloc(&p, bytes))) return nullptr;
+        arrs_.push_back({p, src, back, bytes, true, zero});
+        owned_ = true;
+        return p;
+    }
+    const hpmvs_scene* scene_;  // null: a call against no scene (selftest), no lock to take
+    hipStream_t st_;
+    const bool device_;
+    bool begun_ = false, owned_ = false;
+    int rc_ = HPMVS_OK;
+    std::optional<Exclusive> scope_;
+    std::vector<Arr> arrs_;
+};
 
 int check_batch_shape(const hpmvs_scene* s, const hpmvs_options* o, const hpmvs_patch_batch* b) {
     if (!s || !o || !b) return fail(HPMVS_ERR_ARG, "null scene/options/batch");
@@ -636,57 +728,6 @@ int check_batch(const hpmvs_scene* s, const hpmvs_options* o, const hpmvs_patch_
     if (rc) return rc;
     if (b->n > 0 && (!b->center || !b->normal || !b->scale || !b->n_images || !b->images))
         return fail(HPMVS_ERR_ARG, "batch input arrays missing");
-    return HPMVS_OK;
-}
-
-// all_written: the kernel behind this call writes ok / fmin / x / result / nevals / stage / ngrabs of EVERY patch (the
-// refinement kernel does: fetch and finish stages), so arrays used in place need no zero fill first
-int stage_batch(Staged& st, const hpmvs_patch_batch* b, bool on_device, bool outputs, bool copy_inputs = true, bool all_written = false) {
-    DevBatch& d = st.d;
-    memset(&d, 0, sizeof(d));
-    d.n = b->n; d.max_images = b->max_images;
-    const size_t n = (size_t)b->n;
-    if (on_device) {
-        d.center = b->center; d.normal = b->normal; d.scale = b->scale; d.n_images = b->n_images; d.images = b->images;
-        d.ok = b->ok; d.color = b->color; d.ncc = b->ncc; d.fmin = b->fmin; d.x = b->x; d.result = b->result;
-        d.nevals = b->nevals; d.stage = b->stage; d.ngrabs = b->ngrabs;
-        return HPMVS_OK;
-    }
-    st.staged = true;
-    int rc;
-    if ((rc = stage_in(st, d.center, b->center, 4 * n, copy_inputs))) return rc;
-    if ((rc = stage_in(st, d.normal, b->normal, 4 * n, copy_inputs))) return rc;
-    if ((rc = stage_in(st, d.scale, b->scale, n, copy_inputs))) return rc;
-    if ((rc = stage_in(st, d.n_images, b->n_images, n, copy_inputs))) return rc;
-    if ((rc = stage_in(st, d.images, b->images, n * b->max_images, copy_inputs))) return rc;
-    if (outputs) {
-        if ((rc = stage_in(st, d.ok, b->ok, n, false, /*need_zero=*/!all_written))) return rc;
-        if ((rc = stage_in(st, d.color, b->color, 3 * n, false))) return rc;
-        if ((rc = stage_in(st, d.ncc, b->ncc, n, false))) return rc;
-        if ((rc = stage_in(st, d.fmin, b->fmin, n, false, /*need_zero=*/!all_written))) return rc;
-        if ((rc = stage_in(st, d.x, b->x, 3 * n, false, /*need_zero=*/!all_written))) return rc;
-        if ((rc = stage_in(st, d.result, b->result, n, false, /*need_zero=*/!all_written))) return rc;
-        if ((rc = stage_in(st, d.nevals, b->nevals, n, false, /*need_zero=*/!all_written))) return rc;
-        if ((rc = stage_in(st, d.stage, b->stage, n, false, /*need_zero=*/!all_written))) return rc;
-        if ((rc = stage_in(st, d.ngrabs, b->ngrabs, n, false, /*need_zero=*/!all_written))) return rc;
-    }
-    return HPMVS_OK;
-}
-
-int copy_outputs(hpmvs_patch_batch* b, const DevBatch& D) {
-    const size_t n = (size_t)b->n;
-    int rc;
-    if ((rc = stage_out(b->n_images, D.n_images, n))) return rc;
-    if ((rc = stage_out(b->images, D.images, n * b->max_images))) return rc;
-    if ((rc = stage_out(b->ok, D.ok, n))) return rc;
-    if ((rc = stage_out(b->color, D.color, 3 * n))) return rc;
-    if ((rc = stage_out(b->ncc, D.ncc, n))) return rc;
-    if ((rc = stage_out(b->fmin, D.fmin, n))) return rc;
-    if ((rc = stage_out(b->x, D.x, 3 * n))) return rc;
-    if ((rc = stage_out(b->result, D.result, n))) return rc;
-    if ((rc = stage_out(b->nevals, D.nevals, n))) return rc;
-    if ((rc = stage_out(b->stage, D.stage, n))) return rc;
-    if ((rc = stage_out(b->ngrabs, D.ngrabs, n))) return rc;
     return HPMVS_OK;
 }
 
@@ -744,15 +785,6 @@ static int enqueue_refinement(const hpmvs_scene* s, const DevOptions& d, const D
 }
 // ---- multi-GPU exchange ------------------------------------------------------------------------------------------
 static_assert(sizeof(hpmvs_record) == 192, "hpmvs_record is 192 bytes");
-static DevBatch as_dev_batch(const hpmvs_patch_batch* b) {
-    DevBatch d;
-    memset(&d, 0, sizeof(d));
-    d.n = b->n; d.max_images = b->max_images;
-    d.center = b->center; d.normal = b->normal; d.scale = b->scale; d.n_images = b->n_images; d.images = b->images;
-    d.ok = b->ok; d.color = b->color; d.ncc = b->ncc; d.fmin = b->fmin; d.x = b->x; d.result = b->result;
-    d.nevals = b->nevals; d.stage = b->stage; d.ngrabs = b->ngrabs;
-    return d;
-}
 extern "C" int hpmvs_pack_records(const hpmvs_patch_batch* b, hpmvs_record* records, void* stream) {
     if (!b || b->n < 0 || b->max_images < 1 || b->max_images > HPMVS_MAX_IMAGES) return fail(HPMVS_ERR_ARG, "pack_records: bad batch");
     if (b->n > 0 && (!records || !b->center || !b->normal || !b->scale || !b->n_images || !b->images))
@@ -851,35 +883,19 @@ extern "C" int hpmvs_selftest_bobyqa(int device, int n, const int32_t* kind, con
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(HPMVS_ERR_NODEVICE, "no HIP device visible");
     if (n == 0) return HPMVS_OK;
     HIPCHK(hipSetDevice(device));
-    Staged sg;  // frees its device buffers on every exit path
-    int* dkind = nullptr; double *dpar = nullptr, *dx0 = nullptr, *dlb = nullptr, *dub = nullptr, *dxf = nullptr, *dmin = nullptr, *dtr = nullptr;
-    int *drc = nullptr, *dne = nullptr, *dres = nullptr;
-    int rc;
+    Call c(nullptr, 0, nullptr);
     const size_t N = (size_t)n;
-    if ((rc = stage_in(sg, dkind, (const int*)kind, N, true))) return rc;
-    if ((rc = stage_in(sg, dpar, params, 8 * N, true))) return rc;
-    if ((rc = stage_in(sg, dx0, x0, 3 * N, true))) return rc;
-    if ((rc = stage_in(sg, dlb, lb, 3 * N, true))) return rc;
-    if ((rc = stage_in(sg, dub, ub, 3 * N, true))) return rc;
-    if ((rc = stage_in(sg, dxf, (const double*)xfinal, 3 * N, false))) return rc;
-    if ((rc = stage_in(sg, dmin, (const double*)minf, N, false))) return rc;
-    if ((rc = stage_in(sg, drc, (const int*)result, N, false))) return rc;
-    if ((rc = stage_in(sg, dne, (const int*)nevals, N, false))) return rc;
-    if ((rc = stage_in(sg, dres, (const int*)rescue_calls, N, false))) return rc;
-    if (trace && (rc = stage_in(sg, dtr, (const double*)trace, 4 * N * (size_t)trace_cap, false))) return rc;
-    double* dcold = nullptr;
-    if ((rc = stage_in(sg, dcold, (const double*)xfinal /* (any non-null host pointer: zero-filled) */, selftest_cold_doubles(n), false, true, /*allow_mapped=*/false))) return rc;
-    if ((rc = stage_flush(sg))) return rc;
+    const int32_t* dkind = c.in(kind, N);
+    const double *dpar = c.in(params, 8 * N), *dx0 = c.in(x0, 3 * N), *dlb = c.in(lb, 3 * N), *dub = c.in(ub, 3 * N);
+    double *dxf = c.out(xfinal, 3 * N), *dmin = c.out(minf, N);
+    int32_t *drc = c.out(result, N), *dne = c.out(nevals, N), *dres = c.out(rescue_calls, N);
+    double* dtr = c.out(trace, 4 * N * (size_t)trace_cap);
+    double* dcold = (double*)c.scratch(sizeof(double) * selftest_cold_doubles(n), /*zero=*/true);
+    int rc;
+    if ((rc = c.begin())) return rc;
     launch_selftest(n, dkind, dpar, dx0, dlb, dub, maxeval, dxf, dmin, drc, dne, dres, dtr, trace_cap, dcold, nullptr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    if ((rc = stage_out(xfinal, dxf, 3 * N))) return rc;
-    if ((rc = stage_out(minf, dmin, N))) return rc;
-    if ((rc = stage_out((int*)result, drc, N))) return rc;
-    if ((rc = stage_out((int*)nevals, dne, N))) return rc;
-    if ((rc = stage_out((int*)rescue_calls, dres, N))) return rc;
-    if (trace && (rc = stage_out(trace, dtr, 4 * N * (size_t)trace_cap))) return rc;
-    return HPMVS_OK;
+    return c.finish();
 }
 
 
@@ -1292,43 +1308,16 @@ int hpmvs_optimize_batch(const hpmvs_scene* s, const hpmvs_options* o, hpmvs_pat
     }
     if (!on_device && !stream && b->n <= hpmvs_scene::kStageCapPatches) return optimize_small_host_batch(s, o, b);
     hipStream_t st = (hipStream_t)stream;
-    Staged sg;
-    sg.scene = s;
-    if (!on_device) {
-        Exclusive ex(s);  // the allocations of a host-staged call (see Exclusive; ~Staged frees in one of its own)
-        rc = stage_batch(sg, b, false, true, true, /*all_written=*/true);
-        s->last_staged_bytes = sg.staged_bytes; s->last_mapped_bytes = sg.mapped_bytes;
-    } else rc = stage_batch(sg, b, true, true);
-    if (rc) return rc;
-    if ((rc = stage_flush(sg, st))) return rc;
+    Call c(s, on_device, st);
+    const DevBatch D = c.batch(b, Call::kRefine);
+    if (!on_device) { s->last_staged_bytes = c.staged_bytes; s->last_mapped_bytes = c.mapped_bytes; }  // (hpmvs_last_staging)
+    if ((rc = c.begin(st))) return rc;
     const DevOptions d = make_dev_options(o);
     {
-        {
-            std::lock_guard<std::recursive_mutex> lk(s->mu);  // workspace hand-out + the scene's single event pair
-            if ((rc = enqueue_refinement(s, d, sg.d, st))) return rc;
-        }
-        if (!on_device) {
-            HIPCHK(hipStreamSynchronize(st));
-        }
+        std::lock_guard<std::recursive_mutex> lk(s->mu);  // workspace hand-out + the scene's single event pair
+        if ((rc = enqueue_refinement(s, d, D, st))) return rc;
     }
-    if (!on_device) {
-        const size_t n = (size_t)b->n;
-        const DevBatch& D = sg.d;
-        if ((rc = stage_out(b->center, D.center, 4 * n))) return rc;
-        if ((rc = stage_out(b->normal, D.normal, 4 * n))) return rc;
-        if ((rc = stage_out(b->n_images, D.n_images, n))) return rc;
-        if ((rc = stage_out(b->images, D.images, n * b->max_images))) return rc;
-        if ((rc = stage_out(b->ok, D.ok, n))) return rc;
-        if ((rc = stage_out(b->color, D.color, 3 * n))) return rc;
-        if ((rc = stage_out(b->ncc, D.ncc, n))) return rc;
-        if ((rc = stage_out(b->fmin, D.fmin, n))) return rc;
-        if ((rc = stage_out(b->x, D.x, 3 * n))) return rc;
-        if ((rc = stage_out(b->result, D.result, n))) return rc;
-        if ((rc = stage_out(b->nevals, D.nevals, n))) return rc;
-        if ((rc = stage_out(b->stage, D.stage, n))) return rc;
-        if ((rc = stage_out(b->ngrabs, D.ngrabs, n))) return rc;
-    }
-    return HPMVS_OK;
+    return c.finish();
 }
 
 int hpmvs_init_patches_batch(const hpmvs_scene* s, const hpmvs_options* o, int start_level, int n_points,
@@ -1348,44 +1337,24 @@ int hpmvs_init_patches_batch(const hpmvs_scene* s, const hpmvs_options* o, int s
     if (n_points == 0) return HPMVS_OK;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    Staged sg;
-    sg.scene = s;
-    const double* dxyz = xyz;
-    const int32_t *doff = meas_off, *dimg = meas_img;
-    const size_t n = (size_t)n_points;
-    if (!on_device) {
-        Exclusive ex(s);  // the allocations of a host-staged call (see Exclusive)
-        if ((rc = stage_batch(sg, b, false, true, /*copy_inputs=*/false))) return rc;
-        double* tx = nullptr; int32_t *to = nullptr, *ti = nullptr;
-        const size_t nm = (size_t)meas_off[n_points];
-        if ((rc = stage_in(sg, tx, xyz, 3 * n, true))) return rc;
-        if ((rc = stage_in(sg, to, meas_off, n + 1, true))) return rc;
-        if ((rc = stage_in(sg, ti, meas_img, nm ? nm : 1, nm != 0))) return rc;
-        dxyz = tx; doff = to; dimg = ti;
-    } else if ((rc = stage_batch(sg, b, true, true, /*copy_inputs=*/false))) return rc;
-    if ((rc = stage_flush(sg))) return rc;
+    Call c(s, on_device, st);
+    const DevBatch D = c.batch(b, Call::kCreate);
+    // host arrays without any measurement: a one-element zero list (device pointers are handed through whatever the count)
+    const size_t n = (size_t)n_points, nm = on_device ? 0 : (size_t)meas_off[n_points];
+    const double* dxyz = c.in(xyz, 3 * n);
+    const int32_t* doff = c.in(meas_off, n + 1);
+    const int32_t* dimg = c.arr(meas_img, nm ? nm : 1, nm ? Call::kCopyIn : Call::kZero);
+    if ((rc = c.begin())) return rc;
     const DevOptions d = make_dev_options(o);
     {
-        {
-            std::lock_guard<std::recursive_mutex> lk(s->mu);
-            launch_seed_init(dev_scene(s), d, start_level, n_points, dxyz, doff, dimg, sg.d, st);
-            HIPCHK(hipGetLastError());
-            if ((rc = enqueue_refinement(s, d, sg.d, st))) return rc;
-            launch_drift_gate(n_points, dxyz, sg.d, st);
-            HIPCHK(hipGetLastError());
-        }
-        if (!on_device) {
-            HIPCHK(hipStreamSynchronize(st));
-        }
+        std::lock_guard<std::recursive_mutex> lk(s->mu);
+        launch_seed_init(dev_scene(s), d, start_level, n_points, dxyz, doff, dimg, D, st);
+        HIPCHK(hipGetLastError());
+        if ((rc = enqueue_refinement(s, d, D, st))) return rc;
+        launch_drift_gate(n_points, dxyz, D, st);
+        HIPCHK(hipGetLastError());
     }
-    if (!on_device) {
-        const DevBatch& D = sg.d;
-        if ((rc = stage_out(b->center, D.center, 4 * n))) return rc;
-        if ((rc = stage_out(b->normal, D.normal, 4 * n))) return rc;
-        if ((rc = stage_out(b->scale, D.scale, n))) return rc;
-        if ((rc = copy_outputs(b, D))) return rc;
-    }
-    return HPMVS_OK;
+    return c.finish();
 }
 
 int hpmvs_expand_directions(int mode, float* dxdy) {
@@ -1411,45 +1380,22 @@ int hpmvs_expand_batch(const hpmvs_scene* s, const hpmvs_options* o, int mode, c
     if (parents->n == 0) return HPMVS_OK;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    Staged sp, sg;
-    sp.scene = s; sg.scene = s;  // (this entry point had been left out of the Exclusive protocol)
+    Call c(s, on_device, st);
     const size_t n = (size_t)parents->n;
-    const float *dcc = cell_center, *dcw = cell_width;
-    const uint8_t* dskip = skip;
-    if (!on_device) {
-        Exclusive ex(s);  // the allocations of a host-staged call (see Exclusive)
-        if ((rc = stage_batch(sp, parents, false, false))) return rc;
-        if ((rc = stage_batch(sg, out, false, true, /*copy_inputs=*/false))) return rc;
-        float *tc = nullptr, *tw = nullptr;
-        uint8_t* ts = nullptr;
-        if ((rc = stage_in(sp, tc, cell_center, 3 * n, true))) return rc;
-        if ((rc = stage_in(sp, tw, cell_width, n, true))) return rc;
-        if ((rc = stage_in(sp, ts, skip, n * N, true))) return rc;
-        dcc = tc; dcw = tw; dskip = ts;
-    } else {
-        if ((rc = stage_batch(sp, parents, true, false))) return rc;
-        if ((rc = stage_batch(sg, out, true, true, /*copy_inputs=*/false))) return rc;
-    }
-    if ((rc = stage_flush(sp)) || (rc = stage_flush(sg))) return rc;
+    const DevBatch P = c.batch(parents, Call::kRead), D = c.batch(out, Call::kCreate);
+    const float *dcc = c.in(cell_center, 3 * n), *dcw = c.in(cell_width, n);
+    const uint8_t* dskip = c.in(skip, n * N);
+    if ((rc = c.begin())) return rc;
     const DevOptions d = make_dev_options(o);
     {
         std::lock_guard<std::recursive_mutex> lk(s->mu);
-        launch_expand_init(dev_scene(s), mode, parents->n, sp.d, dcc, dcw, dskip, sg.d, st);
+        launch_expand_init(dev_scene(s), mode, parents->n, P, dcc, dcw, dskip, D, st);
         HIPCHK(hipGetLastError());
-        if ((rc = enqueue_refinement(s, d, sg.d, st))) return rc;
-        launch_expand_gate(mode, parents->n, sp.d, dcc, dcw, sg.d, st);
+        if ((rc = enqueue_refinement(s, d, D, st))) return rc;
+        launch_expand_gate(mode, parents->n, P, dcc, dcw, D, st);
         HIPCHK(hipGetLastError());
     }
-    if (!on_device) {
-        HIPCHK(hipStreamSynchronize(st));
-        const DevBatch& D = sg.d;
-        const size_t m = (size_t)out->n;
-        if ((rc = stage_out(out->center, D.center, 4 * m))) return rc;
-        if ((rc = stage_out(out->normal, D.normal, 4 * m))) return rc;
-        if ((rc = stage_out(out->scale, D.scale, m))) return rc;
-        if ((rc = copy_outputs(out, D))) return rc;
-    }
-    return HPMVS_OK;
+    return c.finish();
 }
 
 // hpmvs_objective_batch is answered by the refinement kernel's own evaluator driven stand-alone (kernels_basic.hip).  A
@@ -1472,32 +1418,16 @@ int hpmvs_objective_batch(const hpmvs_scene* s, const hpmvs_options* o, const hp
     if (b->n == 0) return HPMVS_OK;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    Staged sg;
-    sg.scene = s;
-    const DevOptions d = make_dev_options(o);
+    Call c(s, on_device, st);
     const size_t n = (size_t)b->n;
-    if (on_device) {
-        if ((rc = stage_batch(sg, b, true, false))) return rc;
-        launch_objective_chosen(dev_scene(s), d, sg.d, x, f_out, ngrabs_out, st);
-        HIPCHK(hipGetLastError());
-        return HPMVS_OK;
-    }
-    double *dx = nullptr, *df = nullptr;
-    int32_t* dg = nullptr;
-    {
-        Exclusive ex(s);  // the allocations of a host-staged call (see Exclusive)
-        if ((rc = stage_batch(sg, b, false, false))) return rc;
-        if ((rc = stage_in(sg, dx, x, 3 * n, true))) return rc;
-        if ((rc = stage_in(sg, df, f_out, n, false))) return rc;
-        if ((rc = stage_in(sg, dg, ngrabs_out, n, false))) return rc;
-    }
-    if ((rc = stage_flush(sg))) return rc;
-    launch_objective_chosen(dev_scene(s), d, sg.d, dx, df, dg, st);
+    const DevBatch D = c.batch(b, Call::kRead);
+    const double* dx = c.in(x, 3 * n);
+    double* df = c.out(f_out, n);
+    int32_t* dg = c.out(ngrabs_out, n);
+    if ((rc = c.begin())) return rc;
+    launch_objective_chosen(dev_scene(s), make_dev_options(o), D, dx, df, dg, st);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    if ((rc = stage_out(f_out, df, n))) return rc;
-    if ((rc = stage_out(ngrabs_out, dg, n))) return rc;
-    return HPMVS_OK;
+    return c.finish();
 }
 
 int hpmvs_inccs_batch(const hpmvs_scene* s, const hpmvs_options* o, const hpmvs_patch_batch* b, int ref_idx, int robust,
@@ -1508,27 +1438,13 @@ int hpmvs_inccs_batch(const hpmvs_scene* s, const hpmvs_options* o, const hpmvs_
     if (b->n == 0) return HPMVS_OK;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    Staged sg;
-    sg.scene = s;
-    const DevOptions d = make_dev_options(o);
-    const size_t n = (size_t)b->n;
-    if (on_device) {
-        if ((rc = stage_batch(sg, b, true, false))) return rc;
-        launch_inccs(dev_scene(s), d, sg.d, ref_idx, robust, out, st);
-        HIPCHK(hipGetLastError());
-        return HPMVS_OK;
-    }
-    float* dout = nullptr;
-    {
-        Exclusive ex(s);  // the allocations of a host-staged call (see Exclusive)
-        if ((rc = stage_batch(sg, b, false, false))) return rc;
-        if ((rc = stage_in(sg, dout, out, n * b->max_images, false))) return rc;
-    }
-    if ((rc = stage_flush(sg))) return rc;
-    launch_inccs(dev_scene(s), d, sg.d, ref_idx, robust, dout, st);
+    Call c(s, on_device, st);
+    const DevBatch D = c.batch(b, Call::kRead);
+    float* dout = c.out(out, (size_t)b->n * b->max_images);
+    if ((rc = c.begin())) return rc;
+    launch_inccs(dev_scene(s), make_dev_options(o), D, ref_idx, robust, dout, st);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    return stage_out(out, dout, n * b->max_images);
+    return c.finish();
 }
 
 // ---- depth maps and the acceptance gates over them (kernel_depth.hip)
@@ -1615,18 +1531,13 @@ int hpmvs_set_depths_batch(hpmvs_scene* s, const hpmvs_patch_batch* b, int on_de
     if (b->n == 0) return HPMVS_OK;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    Staged sg;
-    sg.scene = s;
-    if (!on_device) {
-        Exclusive ex(s);  // the allocations of a host-staged call (see Exclusive)
-        if ((rc = stage_batch(sg, b, false, false))) return rc;
-        if (b->ok) { if ((rc = stage_in(sg, sg.d.ok, b->ok, (size_t)b->n, true))) return rc; }
-    } else if ((rc = stage_batch(sg, b, true, false))) return rc;
-    if ((rc = stage_flush(sg))) return rc;
-    launch_set_depths(dev_scene(s), s->ddepth, sg.d, st);
+    Call c(s, on_device, st);
+    DevBatch D = c.batch(b, Call::kRead);
+    D.ok = c.in(b->ok, (size_t)b->n);  // optional: without it every patch counts
+    if ((rc = c.begin())) return rc;
+    launch_set_depths(dev_scene(s), s->ddepth, D, st);
     HIPCHK(hipGetLastError());
-    if (!on_device) HIPCHK(hipStreamSynchronize(st));
-    return HPMVS_OK;
+    return c.finish();
 }
 // Scene::setDepths(patch_i, subtract[i]) for i = 0 .. n - 1 IN THAT ORDER (kernel_depth.hip: keys, sort, per-cell replay).
 // Without a subtraction the calls commute and the batch goes to set_depths_kernel.
@@ -1640,48 +1551,29 @@ int hpmvs_depth_ops_batch(hpmvs_scene* s, const hpmvs_patch_batch* b, const uint
     if (s->depth_floats >= ((size_t)1 << 32)) return fail(HPMVS_ERR_STATE, "depth_ops_batch: the scene's depth maps hold 2^32 cells or more");
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    Staged sg;
-    sg.scene = s;
-    const uint8_t* dsub = nullptr;
-    unsigned long long *keys = nullptr, *sorted = nullptr;
-    unsigned int* counter = nullptr;
-    {
-        Exclusive ex(s);  // the allocations of this call (see Exclusive)
-        if (!on_device) {
-            if ((rc = stage_batch(sg, b, false, false))) return rc;
-            if (b->ok) { if ((rc = stage_in(sg, sg.d.ok, b->ok, (size_t)b->n, true))) return rc; }
-            uint8_t* t = nullptr;
-            if ((rc = stage_in(sg, t, subtract, (size_t)b->n, true))) return rc;
-            dsub = t;
-        } else {
-            if ((rc = stage_batch(sg, b, true, false))) return rc;
-            dsub = subtract;
-        }
-        void* p = nullptr;
-        HIPCHK(hipMalloc(&p, cap * sizeof(unsigned long long))); sg.tmp.push_back(p); keys = (unsigned long long*)p;
-        HIPCHK(hipMalloc(&p, cap * sizeof(unsigned long long))); sg.tmp.push_back(p); sorted = (unsigned long long*)p;
-        HIPCHK(hipMalloc(&p, sizeof(unsigned int))); sg.tmp.push_back(p); counter = (unsigned int*)p;
-    }
-    if ((rc = stage_flush(sg))) return rc;
+    Call c(s, on_device, st);
+    DevBatch D = c.batch(b, Call::kRead);
+    D.ok = c.in(b->ok, (size_t)b->n);
+    const uint8_t* dsub = c.in(subtract, (size_t)b->n);
+    unsigned long long* keys = (unsigned long long*)c.scratch(cap * sizeof(unsigned long long));
+    unsigned long long* sorted = (unsigned long long*)c.scratch(cap * sizeof(unsigned long long));
+    unsigned int* counter = (unsigned int*)c.scratch(sizeof(unsigned int));
+    if ((rc = c.begin())) return rc;
     HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned int), st));
-    launch_depth_ops_keys(dev_scene(s), s->ddepth, s->depth_pool, sg.d, keys, counter, st);
+    launch_depth_ops_keys(dev_scene(s), s->ddepth, s->depth_pool, D, keys, counter, st);
     HIPCHK(hipGetLastError());
-    unsigned int count = 0;
+    unsigned int count = 0;  // the sort's size depends on it: read back mid-call
     HIPCHK(hipMemcpyAsync(&count, counter, sizeof(count), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (count == 0) return HPMVS_OK;
     size_t temp_bytes = 0;
     if (depth_ops_sort(nullptr, &temp_bytes, keys, sorted, count, st) != 0) return fail(HPMVS_ERR_HIP, "depth_ops_batch: rocPRIM size query failed");
-    void* temp = nullptr;
-    {
-        Exclusive ex(s);
-        HIPCHK(hipMalloc(&temp, temp_bytes ? temp_bytes : 1)); sg.tmp.push_back(temp);
-    }
+    void* temp = c.scratch(temp_bytes ? temp_bytes : 1);
+    if (!temp) return c.error();
     if (depth_ops_sort(temp, &temp_bytes, keys, sorted, count, st) != 0) return fail(HPMVS_ERR_HIP, "depth_ops_batch: rocPRIM sort failed");
-    launch_depth_ops_apply(dev_scene(s), s->ddepth, s->depth_pool, sg.d, dsub, sorted, count, st);
+    launch_depth_ops_apply(dev_scene(s), s->ddepth, s->depth_pool, D, dsub, sorted, count, st);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));   // (the temporaries are freed when this call returns)
-    return HPMVS_OK;
+    return c.finish();  // (waits in both forms: the temporaries are freed when this call returns)
 }
 // Scene::getLevelSupport(patch, minLevel) (src/hpmvs/Scene.cpp:334-343) per patch
 int hpmvs_level_support_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, int min_level, int32_t* support, int on_device, void* stream) {
@@ -1693,25 +1585,13 @@ int hpmvs_level_support_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, 
     int rc;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    Staged sg;
-    sg.scene = s;
-    if (on_device) {
-        if ((rc = stage_batch(sg, b, true, false))) return rc;
-        launch_level_support(dev_scene(s), sg.d, min_level, support, st);
-        HIPCHK(hipGetLastError());
-        return HPMVS_OK;
-    }
-    int32_t* dsup = nullptr;
-    {
-        Exclusive ex(s);
-        if ((rc = stage_batch(sg, b, false, false))) return rc;
-        if ((rc = stage_in(sg, dsup, support, (size_t)b->n, false))) return rc;
-    }
-    if ((rc = stage_flush(sg))) return rc;
-    launch_level_support(dev_scene(s), sg.d, min_level, dsup, st);
+    Call c(s, on_device, st);
+    const DevBatch D = c.batch(b, Call::kRead);
+    int32_t* dsup = c.out(support, (size_t)b->n);
+    if ((rc = c.begin())) return rc;
+    launch_level_support(dev_scene(s), D, min_level, dsup, st);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    return stage_out(support, dsup, (size_t)b->n);
+    return c.finish();
 }
 // CellProcessor::regularize (src/hpmvs/CellProcessor.cpp:309-367) for a level of cells against a versioned leaf table
 // (kernel_regularize.hip).  Every device byte comes from a launch workspace: [1 KB counter block, untouched] [header] [hash keys]
@@ -1860,31 +1740,13 @@ int hpmvs_filter_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, const i
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)b->n, nc = (size_t)n_cells;
-    Staged sg;
-    sg.scene = s;
-    const float *dcen = nullptr, *dnor = nullptr;
-    const int32_t* dcs = nullptr;
-    float* ddist = nullptr;
-    int32_t* dkeep = nullptr;
-    int32_t* bad = nullptr;
-    {
-        Exclusive ex(s);  // the allocations of this call (see Exclusive)
-        if (on_device) {
-            dcen = b->center; dnor = b->normal; dcs = cell_start; ddist = dist; dkeep = keep;
-            void* p = nullptr;
-            HIPCHK(hipMalloc(&p, sizeof(int32_t))); sg.tmp.push_back(p); bad = (int32_t*)p;
-        } else {
-            float *c = nullptr, *nm = nullptr;
-            int32_t* cs = nullptr;
-            if ((rc = stage_in(sg, c, b->center, 4 * n, true))) return rc;
-            if ((rc = stage_in(sg, nm, b->normal, 4 * n, true))) return rc;
-            if ((rc = stage_in(sg, cs, cell_start, nc + 1, true))) return rc;
-            if ((rc = stage_in(sg, ddist, dist, n, false, /*need_zero=*/false))) return rc;
-            if ((rc = stage_in(sg, dkeep, keep, nc, false, /*need_zero=*/false))) return rc;
-            dcen = c; dnor = nm; dcs = cs;
-        }
-    }
-    if ((rc = stage_flush(sg, st))) return rc;
+    Call c(s, on_device, st);
+    const float *dcen = c.in(b->center, 4 * n), *dnor = c.in(b->normal, 4 * n);
+    const int32_t* dcs = c.in(cell_start, nc + 1);
+    float* ddist = c.arr(dist, n, Call::kCopyBack);   // (the kernel writes every row and every cell: no zero fill)
+    int32_t* dkeep = c.arr(keep, nc, Call::kCopyBack);
+    int32_t* bad = on_device ? (int32_t*)c.scratch(sizeof(int32_t)) : nullptr;  // (host offsets were checked above)
+    if ((rc = c.begin(st))) return rc;
     if (on_device) {
         int32_t h = 0;
         HIPCHK(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
@@ -1896,10 +1758,7 @@ int hpmvs_filter_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, const i
     }
     launch_filter(dcen, dnor, dcs, n_cells, b->n, ddist, dkeep, st);
     HIPCHK(hipGetLastError());
-    if (on_device) return HPMVS_OK;
-    HIPCHK(hipStreamSynchronize(st));
-    if ((rc = stage_out(dist, (const float*)ddist, n))) return rc;
-    return stage_out(keep, (const int32_t*)dkeep, nc);
+    return c.finish();
 }
 int hpmvs_depth_gates_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, float margin, int abs_int,
                             int32_t* n_visible, int32_t* n_blocking, int32_t* n_free, int on_device, void* stream) {
@@ -1909,30 +1768,14 @@ int hpmvs_depth_gates_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, fl
     if (b->n == 0) return HPMVS_OK;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    Staged sg;
-    sg.scene = s;
-    if (on_device) {
-        if ((rc = stage_batch(sg, b, true, false))) return rc;
-        launch_depth_gates(dev_scene(s), s->ddepth, sg.d, margin, abs_int, n_visible, n_blocking, n_free, st);
-        HIPCHK(hipGetLastError());
-        return HPMVS_OK;
-    }
+    Call c(s, on_device, st);
     const size_t n = (size_t)b->n;
-    int32_t *dv = nullptr, *db = nullptr, *df = nullptr;
-    {
-        Exclusive ex(s);  // the allocations of a host-staged call (see Exclusive)
-        if ((rc = stage_batch(sg, b, false, false))) return rc;
-        if ((rc = stage_in(sg, dv, n_visible, n, false))) return rc;
-        if ((rc = stage_in(sg, db, n_blocking, n, false))) return rc;
-        if ((rc = stage_in(sg, df, n_free, n, false))) return rc;
-    }
-    if ((rc = stage_flush(sg))) return rc;
-    launch_depth_gates(dev_scene(s), s->ddepth, sg.d, margin, abs_int, dv, db, df, st);
+    const DevBatch D = c.batch(b, Call::kRead);
+    int32_t *dv = c.out(n_visible, n), *db = c.out(n_blocking, n), *df = c.out(n_free, n);
+    if ((rc = c.begin())) return rc;
+    launch_depth_gates(dev_scene(s), s->ddepth, D, margin, abs_int, dv, db, df, st);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    if ((rc = stage_out(n_visible, dv, n))) return rc;
-    if ((rc = stage_out(n_blocking, db, n))) return rc;
-    return stage_out(n_free, df, n);
+    return c.finish();
 }
 
 int hpmvs_depth_footprints_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, int32_t* writes, int32_t* frees,
@@ -1943,32 +1786,15 @@ int hpmvs_depth_footprints_batch(const hpmvs_scene* s, const hpmvs_patch_batch* 
     if (b->n == 0) return HPMVS_OK;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    Staged sg;
-    sg.scene = s;
-    if (on_device) {
-        if ((rc = stage_batch(sg, b, true, false))) return rc;
-        launch_depth_footprints(dev_scene(s), s->ddepth, sg.d, writes, frees, attached, view_block, st);
-        HIPCHK(hipGetLastError());
-        return HPMVS_OK;
-    }
+    Call c(s, on_device, st);
     const size_t n = (size_t)b->n, M = (size_t)b->max_images, V = (size_t)s->n_views;
-    int32_t *dw = nullptr, *df = nullptr, *da = nullptr, *dv = nullptr;
-    {
-        Exclusive ex(s);  // the allocations of a host-staged call (see Exclusive)
-        if ((rc = stage_batch(sg, b, false, false))) return rc;
-        if ((rc = stage_in(sg, dw, writes, n * M * 4, false))) return rc;
-        if ((rc = stage_in(sg, df, frees, n * M * 4, false))) return rc;
-        if ((rc = stage_in(sg, da, attached, n * M * 3, false))) return rc;
-        if ((rc = stage_in(sg, dv, view_block, n * V * 3, false))) return rc;
-    }
-    if ((rc = stage_flush(sg))) return rc;
-    launch_depth_footprints(dev_scene(s), s->ddepth, sg.d, dw, df, da, dv, st);
+    const DevBatch D = c.batch(b, Call::kRead);
+    int32_t *dw = c.out(writes, n * M * 4), *df = c.out(frees, n * M * 4);
+    int32_t *da = c.out(attached, n * M * 3), *dv = c.out(view_block, n * V * 3);
+    if ((rc = c.begin())) return rc;
+    launch_depth_footprints(dev_scene(s), s->ddepth, D, dw, df, da, dv, st);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    if ((rc = stage_out(writes, dw, n * M * 4))) return rc;
-    if ((rc = stage_out(frees, df, n * M * 4))) return rc;
-    if ((rc = stage_out(attached, da, n * M * 3))) return rc;
-    return stage_out(view_block, dv, n * V * 3);
+    return c.finish();
 }
 
 // how many patches of the last refinement launch outgrew the batch kernel's 64-id rows and were redone by the wide kernel
