@@ -51,6 +51,11 @@ class LeafTable(C.Structure):
                 ("cell_width", C.c_void_p), ("patch_center", C.c_void_p), ("born", C.c_void_p), ("died", C.c_void_p)]
 
 
+class SeedTreeInfo(C.Structure):
+    _fields_ = [("root_center", C.c_float * 3), ("root_width", C.c_float), ("scale_floor", C.c_float), ("n_rows", C.c_int32),
+                ("n_leaves", C.c_int32)]
+
+
 EXPORTS = [
     "hpmvs_last_error", "hpmvs_device_count", "hpmvs_build_id", "hpmvs_default_options", "hpmvs_camera_from_nvm",
     "hpmvs_scene_create", "hpmvs_scene_set_view", "hpmvs_scene_set_covis", "hpmvs_scene_commit",
@@ -63,7 +68,7 @@ EXPORTS = [
     "hpmvs_set_depths_batch", "hpmvs_depth_gates_batch", "hpmvs_depth_footprints_batch", "hpmvs_depth_ops_batch", "hpmvs_level_support_batch",
     "hpmvs_host_alloc", "hpmvs_host_free", "hpmvs_last_staging",
     "hpmvs_undistort", "hpmvs_undistort_map", "hpmvs_scene_set_view_distorted",
-    "hpmvs_regularize_batch", "hpmvs_filter_batch",
+    "hpmvs_regularize_batch", "hpmvs_filter_batch", "hpmvs_seed_tree_batch",
 ]
 
 _lib = None
@@ -126,6 +131,8 @@ def lib():
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.hpmvs_level_support_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     L.hpmvs_filter_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.hpmvs_seed_tree_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_int, C.c_int, C.POINTER(SeedTreeInfo), C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     _lib = L
     return L
 
@@ -516,3 +523,19 @@ def filter_batch(scene: Scene, patches: Batch, cell_start):
     b = patches.c_struct()
     _chk(lib().hpmvs_filter_batch(scene.h, C.byref(b), cs.ctypes.data, len(cs) - 1, dist.ctypes.data, keep.ctypes.data, 0, None))
     return dist, keep
+
+
+def seed_tree_batch(scene: Scene, batch: Batch, patch_init_maxlevel: int = 9, set_depths: bool = True):
+    """The second half of Scene::initPatches (reference Scene.cpp:183-199) for the rows of `batch` with ok != 0, in row order
+    (include/hpmvs_amd.h: hpmvs_seed_tree_batch): bounding box, root, the scale floor (batch.scale is updated in place), the octree
+    of the sequential patchTree_.add loop and, with set_depths, setDepths of the same rows.  Returns (SeedTreeInfo, rows [n],
+    cell_start [n + 1], cell_center [n, 3], cell_width [n], cell_level [n], patch_center [n, 3]), zero from n_rows / n_leaves on."""
+    n = batch.n
+    info = SeedTreeInfo()
+    rows = np.zeros(n, np.int32); cs = np.zeros(n + 1, np.int32)
+    cc = np.zeros((n, 3), np.float32); cw = np.zeros(n, np.float32); cl = np.zeros(n, np.int32); pc = np.zeros((n, 3), np.float32)
+    b = batch.c_struct()
+    _chk(lib().hpmvs_seed_tree_batch(scene.h, C.byref(b), int(patch_init_maxlevel), int(bool(set_depths)), C.byref(info),
+                                     rows.ctypes.data, cs.ctypes.data, cc.ctypes.data, cw.ctypes.data, cl.ctypes.data,
+                                     pc.ctypes.data, 0, None))
+    return info, rows, cs, cc, cw, cl, pc

@@ -1760,6 +1760,91 @@ int hpmvs_filter_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, const i
     HIPCHK(hipGetLastError());
     return c.finish();
 }
+// The second half of Scene::initPatches (src/hpmvs/Scene.cpp:183-199) for the rows with ok != 0 (kernel_seed_tree.hip): bounding
+// box, root, scale floor, the octree of the sequential patchTree_.add loop as leaf tables, and setDepths.  The root is known only
+// on the device; a root that is not finite raises a flag there that every writing kernel honours, and the one read-back of the
+// call's record (before setDepths is enqueued) turns it into the refusal.
+static_assert(sizeof(hpmvs_seed_tree_info) == 28 && (kSeedBlkInts - kSeedBlkInfo) * 4 >= 28, "hpmvs_seed_tree_info is 7 words of the device record");
+int hpmvs_seed_tree_batch(hpmvs_scene* s, hpmvs_patch_batch* b, int patch_init_maxlevel, int set_depths, hpmvs_seed_tree_info* info,
+                          int32_t* rows, int32_t* cell_start, float* cell_center, float* cell_width, int32_t* cell_level,
+                          float* patch_center, int on_device, void* stream) {
+    if (hpmvs_device_count() <= 0) return fail(HPMVS_ERR_NODEVICE, "seed_tree_batch: no HIP device visible");
+    if (!s || !b || !info) return fail(HPMVS_ERR_ARG, "seed_tree_batch: null scene / batch / info");
+    if (!s->committed) return fail(HPMVS_ERR_STATE, "seed_tree_batch: scene not committed");
+    if (b->n < 0) return fail(HPMVS_ERR_ARG, "seed_tree_batch: negative count");
+    if (patch_init_maxlevel < 0 || patch_init_maxlevel > HPMVS_MAX_TREE_DEPTH)
+        return fail(HPMVS_ERR_ARG, "seed_tree_batch: PATCH_INIT_MAXLEVEL must lie in 0 .. 21 (a deeper floor exceeds HPMVS_MAX_TREE_DEPTH)");
+    if (!cell_start) return fail(HPMVS_ERR_ARG, "seed_tree_batch: cell_start missing");
+    if (b->n > 0 && (!b->center || !b->scale || !rows || !cell_center || !cell_width || !cell_level))
+        return fail(HPMVS_ERR_ARG, "seed_tree_batch: batch or output arrays missing");
+    if (set_depths) {
+        if (!s->depth_pool || !s->ddepth) return fail(HPMVS_ERR_ARG, "seed_tree_batch: set_depths on a scene without depth maps (hpmvs_scene_depth_reset)");
+        if (b->n > 0 && (b->max_images < 1 || b->max_images > HPMVS_MAX_IMAGES || !b->normal || !b->n_images || !b->images))
+            return fail(HPMVS_ERR_ARG, "seed_tree_batch: set_depths needs the batch's normals and image lists");
+    }
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (b->n == 0) {   // getBoundingBox's unit cube
+        const seed::Root r = seed::make_root(nullptr, nullptr, 0, patch_init_maxlevel);
+        if (on_device) HIPCHK(hipMemsetAsync(cell_start, 0, sizeof(int32_t), st));
+        else cell_start[0] = 0;
+        memcpy(info->root_center, r.c, sizeof(r.c));
+        info->root_width = r.w; info->scale_floor = r.floor; info->n_rows = 0; info->n_leaves = 0;
+        return HPMVS_OK;
+    }
+    int rc;
+    const size_t n = (size_t)b->n;
+    Call c(s, on_device, st);
+    DevBatch D;
+    memset(&D, 0, sizeof(D));
+    D.n = b->n; D.max_images = b->max_images;
+    D.center = c.in(b->center, 4 * n);
+    D.scale = c.arr(b->scale, n, Call::kCopyIn | Call::kCopyBack);   // in/out: the floor
+    D.ok = c.in(b->ok, n);                                            // optional: without it every row counts
+    if (set_depths) {
+        D.normal = c.in(b->normal, 4 * n);
+        D.n_images = c.in(b->n_images, n);
+        D.images = c.in(b->images, n * (size_t)b->max_images);
+    }
+    // (the emit kernel writes every entry of every output, zeros behind the counts, or nothing at all: no zero fill)
+    SeedTreeOut out;
+    out.rows = c.arr(rows, n, Call::kCopyBack);
+    out.cell_start = c.arr(cell_start, n + 1, Call::kCopyBack);
+    out.cell_center = c.arr(cell_center, 3 * n, Call::kCopyBack);
+    out.cell_width = c.arr(cell_width, n, Call::kCopyBack);
+    out.cell_level = c.arr(cell_level, n, Call::kCopyBack);
+    out.patch_center = c.arr(patch_center, 3 * n, Call::kCopyBack);
+    // the temporaries, O(n), as one block: 64 bytes per row and rocPRIM's own scratch (a function of n alone)
+    SeedTreeScratch t;
+    t.temp_bytes = seed_tree_temp_bytes(b->n);
+    const size_t a8 = reg_align(8 * n), a4 = reg_align(4 * n), a0 = reg_align(sizeof(int32_t) * kSeedBlkInts);
+    char* w = (char*)c.scratch(a0 + 5 * a8 + 4 * a4 + t.temp_bytes);
+    t.blk = (int32_t*)w; w += a0;
+    t.key_a = (unsigned long long*)w; w += a8;
+    t.key_b = (unsigned long long*)w; w += a8;
+    t.pair_a = (seed::Clamp*)w; w += a8;
+    t.pair_b = (seed::Clamp*)w; w += a8;
+    t.pair_c = (seed::Clamp*)w; w += a8;
+    t.row_a = (int32_t*)w; w += a4;
+    t.row_b = (int32_t*)w; w += a4;
+    t.dep = (int32_t*)w; w += a4;
+    t.depth = (int32_t*)w; w += a4;
+    t.temp = w;
+    if ((rc = c.begin(st))) return rc;
+    if (launch_seed_tree(D.center, D.scale, D.ok, b->n, patch_init_maxlevel, t, out, st) != 0)
+        return fail(HPMVS_ERR_HIP, "seed_tree_batch: a rocPRIM call failed");
+    HIPCHK(hipGetLastError());
+    int32_t h[kSeedBlkInts];
+    HIPCHK(hipMemcpyAsync(h, t.blk, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (h[kSeedBlkBad]) return fail(HPMVS_ERR_ARG, "seed_tree_batch: the survivors' bounding box is not finite");
+    memcpy(info, h + kSeedBlkInfo, sizeof(*info));
+    if (set_depths) {
+        launch_set_depths(dev_scene(s), s->ddepth, D, st);
+        HIPCHK(hipGetLastError());
+    }
+    return c.finish();   // (waits in both forms: the temporaries are freed when this call returns)
+}
 int hpmvs_depth_gates_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, float margin, int abs_int,
                             int32_t* n_visible, int32_t* n_blocking, int32_t* n_free, int on_device, void* stream) {
     int rc = check_depth_batch(s, b, "depth_gates_batch");

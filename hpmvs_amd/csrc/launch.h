@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dev_types.h"
+#include "seed_tree.hpp"
 
 namespace hpmvs {
 
@@ -96,6 +97,25 @@ void launch_regularize(const DevScene& sc, const RegTree& t, const RegCells& cl,
 void launch_filter_check(const int32_t* cell_start, int n_cells, int n, int32_t* bad, hipStream_t st);
 void launch_filter(const float* center, const float* normal, const int32_t* cell_start, int n_cells, int n, float* dist, int32_t* keep,
                    hipStream_t st);
+
+// the seed octree of Scene::initPatches (kernel_seed_tree.hip, include/hpmvs_amd.h: hpmvs_seed_tree_batch).  blk: the call's
+// device record -- bounding box as ordered integers, rows with ok != 0, refusal flag, then the hpmvs_seed_tree_info the host reads
+constexpr int kSeedBlkMin = 0, kSeedBlkMax = 3, kSeedBlkRows = 6, kSeedBlkBad = 7, kSeedBlkInfo = 8, kSeedBlkInts = 16;
+struct SeedTreeScratch {
+    int32_t* blk;                            // [kSeedBlkInts]
+    unsigned long long *key_a, *key_b;       // [n] each
+    int32_t *row_a, *row_b, *dep, *depth;    // [n] each
+    seed::Clamp *pair_a, *pair_b, *pair_c;     // [n] each
+    void* temp;                              // seed_tree_temp_bytes(n)
+    size_t temp_bytes;
+};
+struct SeedTreeOut {
+    int32_t* rows; int32_t* cell_start; float* cell_center; float* cell_width; int32_t* cell_level; float* patch_center;
+};
+size_t seed_tree_temp_bytes(int n);
+// enqueues steps 1-7 on st; != 0: a rocPRIM call failed.  A root that is not finite sets blk[kSeedBlkBad] and nothing is written.
+int launch_seed_tree(const float* center, float* scale, const uint8_t* ok, int n, int maxlevel, const SeedTreeScratch& s,
+                     const SeedTreeOut& out, hipStream_t st);
 
 // refined-patch records of the multi-GPU exchange (include/hpmvs_amd.h: hpmvs_record, 192 bytes)
 void launch_pack_records(const DevBatch& b, void* records, hipStream_t st);

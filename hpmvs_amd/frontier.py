@@ -562,3 +562,42 @@ def filter_extend_level(scene: api.Scene, patches: api.Batch, cell_start, width:
     L = _level(scene, _rows(patches, F.keep), width, occupied, margin, abs_int, options or api.default_options(), key, n_levels,
                events=_rows(patches, losers), event_cell=cell_of[losers])
     return F, L
+
+
+@dataclass
+class SeedTree:
+    """The octree Scene::initPatches leaves behind (reference Scene.cpp:183-199), as the level calls read it: the nonempty leaves
+    in Leaf_iterator order and the batch rows they hold, in data order."""
+    root_center: np.ndarray        # [3] Cell::c_ of the root Branch
+    root_width: float
+    scale_floor: float             # width / (1 << PATCH_INIT_MAXLEVEL + 1): no scale_3dx_ lies below it afterwards
+    rows: np.ndarray               # [n_rows] rows of the batch with ok != 0, leaf by leaf
+    cell_start: np.ndarray         # [n_leaves + 1] leaf l holds rows[cell_start[l] : cell_start[l + 1]]
+    cell_center: np.ndarray        # [n_leaves, 3] Leaf::c_
+    cell_width: np.ndarray         # [n_leaves]
+    cell_level: np.ndarray         # [n_leaves] nodeLevel
+    patch_center: np.ndarray       # [n_leaves, 3] data[0]->center_
+
+    @property
+    def n_leaves(self):
+        return len(self.cell_width)
+
+    def snapshot(self) -> OctreeSnapshot:
+        """The tree as regularize_level / process_level read it: every leaf present from the start (born -1, died INT32_MAX)."""
+        return OctreeSnapshot(self.root_center, self.root_width, self.cell_center, self.cell_width, self.patch_center)
+
+    def cells(self, batch: api.Batch) -> api.Batch:
+        """The rows of `batch` gathered in cell order: with cell_start, what filter_level / filter_extend_level take."""
+        out = _rows(batch, self.rows)
+        out.ok[:] = 1
+        return out
+
+
+def seed_tree(scene: api.Scene, batch: api.Batch, patch_init_maxlevel: int = 9, set_depths: bool = True) -> SeedTree:
+    """The second half of Scene::initPatches for the survivors (ok != 0) of `batch`, e.g. of api.init_patches_batch, in row order:
+    ONE hpmvs_seed_tree_batch.  batch.scale receives the scale floor; with set_depths the scene's depth maps (api.depth_reset
+    first) receive the survivors' depths."""
+    info, rows, cs, cc, cw, cl, pc = api.seed_tree_batch(scene, batch, patch_init_maxlevel, set_depths)
+    R, L = int(info.n_rows), int(info.n_leaves)
+    return SeedTree(np.array(info.root_center, np.float32), float(info.root_width), float(info.scale_floor), rows[:R].copy(),
+                    cs[:L + 1].copy(), cc[:L].copy(), cw[:L].copy(), cl[:L].copy(), pc[:L].copy())

@@ -599,6 +599,34 @@ bool Scene::setDepths(const Patch3d* const* patches, size_t n, const uint8_t* su
     if (hpmvs_depth_ops_batch(dev, &hb.b, sub.data(), 0, nullptr) != HPMVS_OK) { std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl; return false; }
     return true;
 }
+bool Scene::seedTree(std::vector<Ppatch3d>& patches, const HpmvsOptions& options, SeedTree& out, bool setDepths) const {
+    hpmvs_scene* dev = deviceScene();
+    if (!dev) return false;
+    const size_t n = patches.size();
+    std::vector<const Patch3d*> pp(n);
+    for (size_t i = 0; i < n; i++) pp[i] = patches[i].get();
+    HostBatch hb(pp.data(), n);
+    const PinnedAlloc<char> pin(true);
+    PVec<int32_t> rows(n, pin), cs(n + 1, pin), cl(n, pin);
+    PVec<float> cc(3 * n, pin), cw(n, pin), pc(3 * n, pin);
+    hpmvs_seed_tree_info info;
+    if (hpmvs_seed_tree_batch(dev, &hb.b, options.PATCH_INIT_MAXLEVEL, setDepths ? 1 : 0, &info, rows.data(), cs.data(), cc.data(), cw.data(),
+                              cl.data(), pc.data(), 0, nullptr) != HPMVS_OK) {
+        std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl;
+        return false;
+    }
+    for (size_t i = 0; i < n; i++) patches[i]->scale_3dx_ = hb.scale[i];
+    const size_t R = (size_t)info.n_rows, L = (size_t)info.n_leaves;
+    for (int k = 0; k < 3; k++) out.rootCenter[k] = info.root_center[k];
+    out.rootWidth = info.root_width; out.scaleFloor = info.scale_floor;
+    out.rows.assign(rows.begin(), rows.begin() + R);
+    out.cellStart.assign(cs.begin(), cs.begin() + L + 1);
+    out.cellCenter.assign(cc.begin(), cc.begin() + 3 * L);
+    out.cellWidth.assign(cw.begin(), cw.begin() + L);
+    out.cellLevel.assign(cl.begin(), cl.begin() + L);
+    out.patchCenter.assign(pc.begin(), pc.begin() + 3 * L);
+    return true;
+}
 bool Scene::levelSupport(const Patch3d* const* patches, size_t n, int minLevel, std::vector<int>& support) const {
     support.assign(n, 0);
     hpmvs_scene* dev = deviceScene();

@@ -1,6 +1,7 @@
 // mo3d::Scene -- the part of the reference's Scene the refinement path reads (reference
 // include/hpmvs/Scene.h:69-71: cameras_, images_, covis_; cached by PatchOptimizer at
-// src/hpmvs/PatchOptimizer.cpp:38-41).  The octree and the scheduler stay with the host application; the
+// src/hpmvs/PatchOptimizer.cpp:38-41).  The octree object and the scheduler stay with the host application (seedTree builds
+// the initial tree's leaf tables); the
 // depth maps (reference Scene.h:74-76) live in HBM next to the pyramids, with batch forms of setDepths and of the
 // three acceptance tests the expansion gates its candidates on.  The scene must be complete before the first PatchOptimizer is constructed and is
 // immutable afterwards, exactly as in the reference; at that point it is uploaded to HBM once and
@@ -29,8 +30,24 @@ public:
     bool extractCoVisiblilty(const NVM_Model& model, const HpmvsOptions& options);
     // The seed loop of Scene::initPatches (src/hpmvs/Scene.cpp:112-178) as ONE batched GPU call: seed
     // construction, optimize(), drift gate.  Survivors are appended to `out` in point order; inserting
-    // them into the octree / depth maps (Scene.cpp:183-199) stays with the host application.
+    // them into the octree / depth maps (Scene.cpp:183-199) is seedTree below.
     bool initPatches(const NVM_Model& model, const HpmvsOptions& options, std::vector<Ppatch3d>& out) const;
+    // The second half of Scene::initPatches (src/hpmvs/Scene.cpp:183-199) as ONE batched GPU call (hpmvs_seed_tree_batch):
+    // getBoundingBox, the root Branch, scale_3dx_ = max(scale_3dx_, width / (1 << PATCH_INIT_MAXLEVEL + 1)) written to every
+    // patch, the octree the sequential patchTree_.add loop builds -- as the leaf tables the level calls read, not as pointers --
+    // and, with setDepths, Scene::setDepths(p, false) of every patch (resetDepths first).  Insertion order is the vector's.
+    // The octree object itself stays with the host application, which can build any pointer form it needs from the tables.
+    struct SeedTree {
+        float rootCenter[3], rootWidth, scaleFloor;
+        std::vector<int32_t> rows;         // patch indices leaf by leaf (Leaf_iterator order), data order within a leaf
+        std::vector<int32_t> cellStart;    // [leaves + 1] leaf l holds rows[cellStart[l] .. cellStart[l + 1] - 1]
+        std::vector<float> cellCenter;     // [leaves][3] Leaf::c_
+        std::vector<float> cellWidth;      // [leaves]
+        std::vector<int32_t> cellLevel;    // [leaves] nodeLevel
+        std::vector<float> patchCenter;    // [leaves][3] data[0]->center_
+        size_t leaves() const { return cellWidth.size(); }
+    };
+    bool seedTree(std::vector<Ppatch3d>& patches, const HpmvsOptions& options, SeedTree& out, bool setDepths = true) const;
     // ---- depth maps (src/hpmvs/Scene.cpp:74-80) and the acceptance tests over them, batched on the device.
     // resetDepths: allocate / clear (MAX_DEPTH = 1000).  setDepths: Scene::setDepths(patch) (Scene.cpp:351-381) for
     // every patch.  depthGates: per patch the counts of Scene::depthTests, viewBlockTest and pixelFreeTests

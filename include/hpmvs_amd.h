@@ -31,6 +31,8 @@
  *                               src/hpmvs/CellProcessor.cpp:84-142 and :210-262.
  *   hpmvs_regularize_batch   <- CellProcessor::regularize, src/hpmvs/CellProcessor.cpp:309-367.
  *   hpmvs_filter_batch       <- CellProcessor::filter, src/hpmvs/CellProcessor.cpp:43-82.
+ *   hpmvs_seed_tree_batch    <- the second half of Scene::initPatches, src/hpmvs/Scene.cpp:183-199
+ *                               (getBoundingBox, swapRoot, the scale floor, patchTree_.add, setDepths).
  *   hpmvs_camera_from_nvm    <- Camera::init, src/hpmvs/Camera.cpp:34-81.
  */
 #ifndef HPMVS_AMD_H
@@ -310,6 +312,39 @@ int hpmvs_regularize_batch(const hpmvs_scene *s, const hpmvs_patch_batch *cells,
  * on_device != 0. */
 int hpmvs_filter_batch(const hpmvs_scene *s, const hpmvs_patch_batch *patches, const int32_t *cell_start, int n_cells, float *dist,
                        int32_t *keep, int on_device, void *stream);
+
+/* ---- the seed octree: the second half of Scene::initPatches (src/hpmvs/Scene.cpp:183-199) -------------------------------------
+ * For the rows of `b` with ok[i] != 0 (every row when ok is NULL), in row order -- the survivors of hpmvs_init_patches_batch --:
+ * getBoundingBox (doctree.h:732-756: max starts at FLT_MIN, a NaN coordinate never enters), the root Branch((min + max) / 2,
+ * max(dist)), scale = max(scale, width / (1 << PATCH_INIT_MAXLEVEL + 1)) written back to b->scale, and the octree the sequential
+ * loop patchTree_.add(p, scale) leaves behind, as the tables the level calls read:
+ *   rows         [n]      the n_rows rows, leaf by leaf in Leaf_iterator order, in data order (= row order) within a leaf
+ *   cell_start   [n + 1]  leaf l holds rows[cell_start[l] .. cell_start[l + 1] - 1]; cell_start[n_leaves] = n_rows
+ *   cell_center  [n][3]   Leaf::c_, by the reference's Cell(parent, idx) descent (hpmvs_regularize_batch accepts it bit for bit)
+ *   cell_width   [n]      Leaf::width_
+ *   cell_level   [n]      the leaf's depth below the root (nodeLevel), >= 1: the root is a Branch
+ *   patch_center [n][3]   data[0]->center_ (nullable)
+ * Entries from n_rows / n_leaves on come back 0.  The tree is computed in closed form (add only ever splits: DESIGN.md §3.10) and
+ * equals the sequential insertion's leaf for leaf; insertion order is row order (the reference's is whatever order its OpenMP
+ * threads reach the critical section in).  set_depths != 0 then runs setDepths(p, false) for the same rows (needs
+ * hpmvs_scene_depth_reset, and the batch's normal / n_images / images, which are not read otherwise).  No row: the reference's
+ * unit cube (centre 0, width 2), n_leaves = 0.
+ * HPMVS_ERR_ARG before any write for patch_init_maxlevel outside 0 .. HPMVS_MAX_TREE_DEPTH, for a bounding box that is not finite
+ * (the reference would carry on with it) and for set_depths on a scene without depth maps.  A root width so small that its
+ * halvings are subnormal is cut off at HPMVS_MAX_TREE_DEPTH levels.  Host or device pointers as for hpmvs_optimize_batch (info is
+ * always a host structure); the call is host-synchronous in both forms: the record with the counts is read back once, and its
+ * temporaries (O(n)) are freed on return. */
+typedef struct {
+    float root_center[3];
+    float root_width;
+    float scale_floor;
+    int32_t n_rows;     /* rows with ok != 0 */
+    int32_t n_leaves;   /* nonempty leaves */
+} hpmvs_seed_tree_info;
+int hpmvs_seed_tree_batch(hpmvs_scene *s, hpmvs_patch_batch *b, int patch_init_maxlevel, int set_depths,
+                          hpmvs_seed_tree_info *info, int32_t *rows /*[n]*/, int32_t *cell_start /*[n+1]*/,
+                          float *cell_center /*[n][3]*/, float *cell_width /*[n]*/, int32_t *cell_level /*[n]*/,
+                          float *patch_center /*[n][3], nullable*/, int on_device, void *stream);
 
 /* Host-pointer calls and pinned memory.  An array of a host-pointer call (on_device = 0) that lies in pinned host memory
  * mapped into the GPU's address space -- hipHostMalloc / hipHostRegister, torch's pin_memory(), hpmvs_host_alloc below --
