@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -51,6 +52,11 @@ class LeafTable(C.Structure):
                 ("cell_width", C.c_void_p), ("patch_center", C.c_void_p), ("born", C.c_void_p), ("died", C.c_void_p)]
 
 
+class OctreeIndex(C.Structure):
+    _fields_ = [("root_center", C.c_float * 3), ("root_width", C.c_float), ("n_branches", C.c_int32), ("n_leaves", C.c_int32),
+                ("branch_key", C.c_void_p), ("leaf_key", C.c_void_p)]
+
+
 class SeedTreeInfo(C.Structure):
     _fields_ = [("root_center", C.c_float * 3), ("root_width", C.c_float), ("scale_floor", C.c_float), ("n_rows", C.c_int32),
                 ("n_leaves", C.c_int32)]
@@ -68,7 +74,7 @@ EXPORTS = [
     "hpmvs_set_depths_batch", "hpmvs_depth_gates_batch", "hpmvs_depth_footprints_batch", "hpmvs_depth_ops_batch", "hpmvs_level_support_batch",
     "hpmvs_host_alloc", "hpmvs_host_free", "hpmvs_last_staging",
     "hpmvs_undistort", "hpmvs_undistort_map", "hpmvs_scene_set_view_distorted",
-    "hpmvs_regularize_batch", "hpmvs_filter_batch", "hpmvs_seed_tree_batch",
+    "hpmvs_regularize_batch", "hpmvs_filter_batch", "hpmvs_seed_tree_batch", "hpmvs_octree_locate_batch",
 ]
 
 _lib = None
@@ -133,6 +139,7 @@ def lib():
     L.hpmvs_filter_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.hpmvs_seed_tree_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_int, C.c_int, C.POINTER(SeedTreeInfo), C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.hpmvs_octree_locate_batch.argtypes = [C.c_void_p, C.POINTER(OctreeIndex), C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
     _lib = L
     return L
 
@@ -539,3 +546,40 @@ def seed_tree_batch(scene: Scene, batch: Batch, patch_init_maxlevel: int = 9, se
                                      rows.ctypes.data, cs.ctypes.data, cc.ctypes.data, cw.ctypes.data, cl.ctypes.data,
                                      pc.ctypes.data, 0, None))
     return info, rows, cs, cc, cw, cl, pc
+
+
+OCTREE_MAX_DEPTH = 21   # HPMVS_MAX_TREE_DEPTH: levels of a path key
+OCTREE_OUTPUTS = ("inside", "leaf_key", "leaf_index", "leaf_width", "leaf_center", "target_key")
+
+
+@dataclass
+class OctreeLocation:
+    inside: np.ndarray             # [n] uint8 root.contains(p)
+    leaf_key: np.ndarray           # [n] uint64 path key of the leaf root->at(p)
+    leaf_index: np.ndarray         # [n] int32 index into the leaf keys given, -1: an empty leaf
+    leaf_width: np.ndarray         # [n] float32
+    leaf_center: np.ndarray        # [n, 3] float32
+    target_key: np.ndarray         # [n] uint64 addConditional's leaf, 0: refused (or no add_width)
+
+
+def octree_locate_batch(scene: Scene, root_center, root_width, branch_key, leaf_key, points, add_width=None) -> OctreeLocation:
+    """root->at(p), getRoot()->contains(p) and DynOctTree::addConditional's target for every point against an octree given as
+    path keys (include/hpmvs_amd.h: hpmvs_octree_locate_batch): branch_key the branches below the root, leaf_key the nonempty
+    leaves.  add_width: a scalar or [n] (None: no target keys).  HpmvsError when the keys are no tree."""
+    bk = np.ascontiguousarray(branch_key, dtype=np.uint64).reshape(-1)
+    lk = np.ascontiguousarray(leaf_key, dtype=np.uint64).reshape(-1)
+    pts = np.asarray(points, dtype=np.float32)
+    pts = np.ascontiguousarray(pts.reshape(-1, pts.shape[-1] if pts.ndim > 1 else 3)[:, :3])   # [n, 3] or [n, 4] centres
+    n = len(pts)
+    aw = None if add_width is None else np.ascontiguousarray(np.broadcast_to(np.asarray(add_width, dtype=np.float32), (n,)))
+    t = OctreeIndex()
+    for k in range(3):
+        t.root_center[k] = float(np.float32(root_center[k]))
+    t.root_width = float(np.float32(root_width))
+    t.n_branches, t.n_leaves = len(bk), len(lk)
+    t.branch_key, t.leaf_key = bk.ctypes.data, lk.ctypes.data
+    r = OctreeLocation(np.zeros(n, np.uint8), np.zeros(n, np.uint64), np.zeros(n, np.int32), np.zeros(n, np.float32),
+                       np.zeros((n, 3), np.float32), np.zeros(n, np.uint64))
+    _chk(lib().hpmvs_octree_locate_batch(scene.h, C.byref(t), n, pts.ctypes.data, None if aw is None else aw.ctypes.data,
+                                         *[getattr(r, k).ctypes.data for k in OCTREE_OUTPUTS], 0, None))
+    return r

@@ -22,6 +22,7 @@
 #include "../../include/hpmvs_amd.h"
 #include "dev_types.h"
 #include "launch.h"
+#include "octree.hpp"
 
 using namespace hpmvs;
 
@@ -1844,6 +1845,70 @@ int hpmvs_seed_tree_batch(hpmvs_scene* s, hpmvs_patch_batch* b, int patch_init_m
         HIPCHK(hipGetLastError());
     }
     return c.finish();   // (waits in both forms: the temporaries are freed when this call returns)
+}
+// root->at(p), Cell::contains and addConditional's target for a level's points against the scheduler's octree (kernel_octree.hip,
+// octree.hpp).  The table lives in a launch workspace: [1 KB counter block, untouched] [verdict] [keys] [values]; the arrays go
+// through Call.  The verdict of the check kernel is read back before the locate kernel is enqueued: a refused table writes nothing.
+int hpmvs_octree_locate_batch(const hpmvs_scene* s, const hpmvs_octree_index* t, int n, const float* points, const float* add_width,
+                              uint8_t* inside, uint64_t* leaf_key, int32_t* leaf_index, float* leaf_width, float* leaf_center,
+                              uint64_t* target_key, int on_device, void* stream) {
+    if (hpmvs_device_count() <= 0) return fail(HPMVS_ERR_NODEVICE, "octree_locate_batch: no HIP device visible");
+    if (!s || !t) return fail(HPMVS_ERR_ARG, "octree_locate_batch: null scene / octree");
+    if (!s->committed) return fail(HPMVS_ERR_STATE, "octree_locate_batch: scene not committed");
+    if (n < 0 || t->n_branches < 0 || t->n_leaves < 0) return fail(HPMVS_ERR_ARG, "octree_locate_batch: negative count");
+    if ((t->n_branches > 0 && !t->branch_key) || (t->n_leaves > 0 && !t->leaf_key)) return fail(HPMVS_ERR_ARG, "octree_locate_batch: key arrays missing");
+    if (n > 0 && !points) return fail(HPMVS_ERR_ARG, "octree_locate_batch: points missing");
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(t->root_center[k])) return fail(HPMVS_ERR_ARG, "octree_locate_batch: root centre not finite");
+    if (!(t->root_width > 0.0f) || !std::isfinite(t->root_width)) return fail(HPMVS_ERR_ARG, "octree_locate_batch: root width must be finite and > 0");
+    const size_t nb = (size_t)t->n_branches, nl = (size_t)t->n_leaves, np = (size_t)n;
+    if (nb + nl > ((size_t)1 << 29)) return fail(HPMVS_ERR_ARG, "octree_locate_batch: the octree does not fit the launch workspace");
+    const size_t slots = octree::table_slots(nb + nl);
+    const size_t o_hdr = kQueueSlotBytes, o_keys = reg_align(o_hdr + 16), o_vals = reg_align(o_keys + 8 * slots), o_end = reg_align(o_vals + 4 * slots);
+    if (o_end > s->ws_bytes) return fail(HPMVS_ERR_ARG, "octree_locate_batch: the octree does not fit the launch workspace");
+    int rc;
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    Call c(s, on_device, st);
+    const unsigned long long* dbk = (const unsigned long long*)c.in(t->branch_key, nb);
+    const unsigned long long* dlk = (const unsigned long long*)c.in(t->leaf_key, nl);
+    const float* dpts = c.in(points, 3 * np);
+    const float* daw = c.in(add_width, np);
+    OctreeLocateOut out;   // (the kernel writes every entry of every output it is given: no zero fill)
+    out.inside = c.arr(inside, np, Call::kCopyBack);
+    out.leaf_key = (unsigned long long*)c.arr(leaf_key, np, Call::kCopyBack);
+    out.leaf_index = c.arr(leaf_index, np, Call::kCopyBack);
+    out.leaf_width = c.arr(leaf_width, np, Call::kCopyBack);
+    out.leaf_center = c.arr(leaf_center, 3 * np, Call::kCopyBack);
+    out.target_key = (unsigned long long*)c.arr(target_key, np, Call::kCopyBack);
+    if ((rc = c.begin(st))) return rc;
+    // the scene lock is held from here on: the workspace is this call's until its last kernel has been enqueued
+    std::lock_guard<std::recursive_mutex> lk(s->mu);
+    if ((rc = service_quiesce(s))) return rc;
+    int32_t* q;
+    int slot;
+    if ((rc = acquire_workspace(s, &q, &slot, st))) return rc;
+    struct Release { const hpmvs_scene* s; int slot; hipStream_t st; ~Release() { hipEventRecord(s->slot_done[slot], st); s->slot_used[slot] = true; } } rel{s, slot, st};
+    char* w = (char*)q;
+    int32_t* verdict = (int32_t*)(w + o_hdr);
+    unsigned long long* keys = (unsigned long long*)(w + o_keys);
+    int32_t* vals = (int32_t*)(w + o_vals);
+    HIPCHK(hipMemsetAsync(verdict, 0, 16, st));
+    HIPCHK(hipMemsetAsync(keys, 0, 8 * slots, st));
+    if (nb + nl) {
+        launch_octree_build(dbk, t->n_branches, dlk, t->n_leaves, keys, vals, (uint32_t)slots, verdict, st);
+        HIPCHK(hipGetLastError());
+        int32_t h = 0;
+        HIPCHK(hipMemcpyAsync(&h, verdict, sizeof(h), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (h & octree::kBadKey) return fail(HPMVS_ERR_ARG, "octree_locate_batch: a word is no path key of a cell below the root (a leaf deeper than 21 levels, a branch deeper than 20)");
+        if (h & octree::kBadTwice) return fail(HPMVS_ERR_ARG, "octree_locate_batch: a key occurs twice (within the branch or leaf keys, or in both)");
+        if (h & octree::kBadOrphan) return fail(HPMVS_ERR_ARG, "octree_locate_batch: a key's parent prefix is neither a branch nor the root");
+    }
+    const float root[4] = {t->root_center[0], t->root_center[1], t->root_center[2], t->root_width};
+    launch_octree_locate(root, keys, vals, (uint32_t)slots, n, dpts, daw, out, st);
+    HIPCHK(hipGetLastError());
+    return c.finish();
 }
 int hpmvs_depth_gates_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, float margin, int abs_int,
                             int32_t* n_visible, int32_t* n_blocking, int32_t* n_free, int on_device, void* stream) {

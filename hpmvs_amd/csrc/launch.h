@@ -117,6 +117,18 @@ size_t seed_tree_temp_bytes(int n);
 int launch_seed_tree(const float* center, float* scale, const uint8_t* ok, int n, int maxlevel, const SeedTreeScratch& s,
                      const SeedTreeOut& out, hipStream_t st);
 
+// leaf look-ups in the scheduler's octree (kernel_octree.hip, octree.hpp, include/hpmvs_amd.h: hpmvs_octree_locate_batch).
+// launch_octree_build enters the branch keys (value -2) and the nonempty leaves' keys (value: index) into the table keys / vals
+// (`slots` entries, keys zeroed by the caller) and then checks it: *verdict collects octree::kBad* bits.  Every output of
+// launch_octree_locate is nullable; root = c_ (3), width_.
+struct OctreeLocateOut {
+    uint8_t* inside; unsigned long long* leaf_key; int32_t* leaf_index; float* leaf_width; float* leaf_center; unsigned long long* target_key;
+};
+void launch_octree_build(const unsigned long long* branch_key, int nb, const unsigned long long* leaf_key, int nl, unsigned long long* keys,
+                         int32_t* vals, uint32_t slots, int32_t* verdict, hipStream_t st);
+void launch_octree_locate(const float* root, const unsigned long long* keys, const int32_t* vals, uint32_t slots, int n,
+                          const float* points, const float* add_width, const OctreeLocateOut& out, hipStream_t st);
+
 // refined-patch records of the multi-GPU exchange (include/hpmvs_amd.h: hpmvs_record, 192 bytes)
 void launch_pack_records(const DevBatch& b, void* records, hipStream_t st);
 void launch_unpack_records(const void* records, int n, const DevBatch& b, hipStream_t st);

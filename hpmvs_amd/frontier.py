@@ -40,6 +40,10 @@ The octree itself stays with the scheduler (out of scope): `oc
 `cell_key` the caller's map from a point to its leaf (default: the uniform grid of leaf width `width`).
 Stage codes as in hpmvs_expand_batch, plus 20 = leaf already taken (no refinement), 23 / 24 / 25 = depthTests /
 viewBlockTest / pixelFreeTests threshold, 26 = addConditional found the refined patch's leaf taken.
+
+`extend_level_tree` / `filter_extend_level_tree` are the same walk against the REAL octree (`Octree`: branch keys + nonempty leaf
+keys, looked up on the device by hpmvs_octree_locate_batch): the pre-gate sees leaves of any depth, addConditional splits, and a
+candidate that ends outside the tree's root is a border candidate, stage 27.
 """
 from __future__ import annotations
 
@@ -90,6 +94,8 @@ class LevelResult:
     accepted: list                 # candidate indices in the reference's order
     waves: int                     # gate / setDepths passes it took
     deferred_per_wave: list = field(default_factory=list)
+    border: list = field(default_factory=list)   # extend_level_tree: the stage-27 candidates in queue order (the scheduler routes them)
+    leaf_key: dict = field(default_factory=dict)  # extend_level_tree: accepted candidate -> path key of the leaf it went into
 
 
 MAX_LEVELS = 8                     # HPMVS_MAX_LEVELS
@@ -115,33 +121,52 @@ def _pyramid_levels(scene: api.Scene, who: str) -> int:
     return n_levels
 
 
-def _candidates(scene, parents, width, occupied, o, key):
+class _GridKeys:
+    """The candidates' leaves on the caller's uniform grid (`key`, default cell_key) with the caller's `occupied` set."""
+
+    def __init__(self, key, width, occupied):
+        self.key, self.width, self.occupied = key, width, occupied
+
+    def pre(self, center):
+        pre_key = [self.key(c, self.width) for c in center]
+        return pre_key, np.array([k in self.occupied for k in pre_key], np.uint8)   # level-start occupancy: those are never refined
+
+    def post(self, center, refined):
+        return [self.key(center[t], self.width) if refined[t] else None for t in range(len(center))], None
+
+
+def _candidates(scene, parents, width, keys, o):
     """The candidate steps of a level: the six candidates of every parent before optimize and their leaves (`pre_key`), ONE
-    hpmvs_expand_batch over those whose leaf is free when the level starts, the refined ones' leaves (`post_key`)."""
+    hpmvs_expand_batch over those whose leaf is free when the level starts, the refined ones' leaves (`post_key`) and, on the
+    real tree, the refined ones that left the root (`border`, else None).  `keys`: _GridKeys or _TreeKeys."""
     n = parents.n
     N = 6 * n
     cc = np.zeros((n, 3), np.float32)
     widths = np.full(n, width, np.float32)
     # the candidates before optimize (everything skipped: constructed only) -> their leaves
     pre = api.expand_batch(scene, api.EXPAND_EXTEND, parents, cc, widths, np.ones(N, np.uint8), options=o)
-    pre_key = [key(pre.center[t], width) for t in range(N)]
-    skip = np.array([k in occupied for k in pre_key], np.uint8)   # level-start occupancy: those are never refined
+    pre_key, skip = keys.pre(pre.center)
     out = api.expand_batch(scene, api.EXPAND_EXTEND, parents, cc, widths, skip, options=o)
     refined = (out.stage == 0) & (skip == 0)
-    post_key = [key(out.center[t], width) if refined[t] else None for t in range(N)]
-    return out, pre_key, post_key, skip, refined
+    post_key, border = keys.post(out.center, refined)
+    return out, pre_key, post_key, skip, refined, border
 
 
 def _walk(queue, pre_key, post_key, refined, n_images, reads, writes, ev_cells, occupied, min_images, stage, counts, gates, apply,
-          sequential=True):
+          sequential=True, border=None):
     """The wave walk of the module docstring over `queue`: items ("c", t) (candidate t) and ("e", j) (subtraction event j) in the
     reference's order.  reads(t) / writes(t): the map cells refined candidate t's gates read / its setDepths would write (sets);
     ev_cells[j]: the cells event j writes.  The device is reached through two callables only: gates(list of candidates) -> their
     (depthTests, viewBlockTest, pixelFreeTests) counts from the maps as they are, apply(ops) enters a wave's accepted candidates
     and applied events, given as queue items in queue order.  `stage` (preset to each candidate's refinement result) and `counts`
     are filled in place, `occupied` grows.  Returns (accepted in queue order, waves, deferred per wave).  sequential = False
-    drops every deferral of a candidate (one wave; meaningful without events only)."""
+    drops every deferral of a candidate (one wave; meaningful without events only).
+    border: the refined candidates that lie outside the tree's root (a set, or flags indexed by candidate; default none).  Such
+    a candidate waits on its reads like any other and, past the three counts, gets stage 27: it writes no depth and occupies no
+    leaf (its post_key is never looked at), so while deferred it only guards what it reads."""
     MIN = min_images
+    is_border = (lambda t: False) if border is None else (lambda t: t in border) if isinstance(border, (set, frozenset)) \
+        else (lambda t: bool(border[t]))
     accepted, waves, deferred_log = [], 0, []
     pending = list(queue)
     while pending:
@@ -156,9 +181,10 @@ def _walk(queue, pre_key, post_key, refined, n_images, reads, writes, ev_cells, 
             deferred.append(("c", t))
             occ_guard.add(pre_key[t])
             if refined[t]:
-                dirty.update(writes(t)); cand_dirty.update(writes(t))
                 guard.update(reads(t)); cand_guard.update(reads(t))
-                maybe_occ.add(post_key[t]); occ_guard.add(post_key[t])
+                if not is_border(t):
+                    dirty.update(writes(t)); cand_dirty.update(writes(t))
+                    maybe_occ.add(post_key[t]); occ_guard.add(post_key[t])
 
         for kind, t in pending:
             if kind == "e":
@@ -190,6 +216,8 @@ def _walk(queue, pre_key, post_key, refined, n_images, reads, writes, ev_cells, 
                 stage[t] = 24
             elif not (f_ >= MIN - 1 and f_ * 1.0 / n_images[t] > 0.75):
                 stage[t] = 25
+            elif is_border(t):
+                stage[t] = 27                       # handed to borderCellFn_: not inserted, no depths
             else:
                 k_ = post_key[t]
                 if k_ in occupied:
@@ -209,11 +237,11 @@ def _walk(queue, pre_key, post_key, refined, n_images, reads, writes, ev_cells, 
     return accepted, waves, deferred_log
 
 
-def _level(scene, parents, width, occupied, margin, abs_int, o, key, n_levels, sequential=True, events=None, event_cell=()):
+def _level(scene, parents, width, occupied, margin, abs_int, o, keys, n_levels, sequential=True, events=None, event_cell=()):
     """CellProcessor::extend over `parents` with the subtraction events `events` (a Batch, or None): event j comes before the
     candidates of parent event_cell[j] (non-decreasing).  The candidate steps, ONE hpmvs_depth_footprints_batch over the refined
     candidates followed by the events, the queue, and the walk with the device behind its two callables."""
-    out, pre_key, post_key, skip, refined = _candidates(scene, parents, width, occupied, o, key)
+    out, pre_key, post_key, skip, refined, border = _candidates(scene, parents, width, keys, o)
     N = 6 * parents.n
     rc = np.nonzero(refined)[0]
     n_ev = events.n if events is not None else 0
@@ -279,8 +307,9 @@ def _level(scene, parents, width, occupied, margin, abs_int, o, key, n_levels, s
     stage = np.where(skip != 0, 20, out.stage).astype(np.int32)
     counts = np.full((N, 3), -1, np.int32)
     accepted, waves, deferred_log = _walk(queue, pre_key, post_key, refined, out.n_images, reads, writes, ev_cells, occupied,
-                                          int(o.MIN_IMAGES_PER_PATCH), stage, counts, gates, apply, sequential)
-    return LevelResult(out, stage, counts, sorted(accepted), waves, deferred_log)
+                                          int(o.MIN_IMAGES_PER_PATCH), stage, counts, gates, apply, sequential, border)
+    return LevelResult(out, stage, counts, sorted(accepted), waves, deferred_log, [t for kind, t in queue if kind == "c" and stage[t] == 27],
+                       {t: post_key[t] for t in accepted} if border is not None else {})
 
 
 def extend_level(scene: api.Scene, parents: api.Batch, width: float, occupied: set, margin: float = 1.0, abs_int: int = 0,
@@ -291,7 +320,7 @@ def extend_level(scene: api.Scene, parents: api.Batch, width: float, occupied: s
     one wave, not the reference's result when candidates of a level interact through the maps.
     `n_levels` is kept for existing callers and ignored: the pyramid levels a read can be on are the scene's cameras' (at most
     HPMVS_MAX_LEVELS, ValueError beyond), so no value given here can hide a read from the walk."""
-    return _level(scene, parents, width, occupied, margin, abs_int, options or api.default_options(), key,
+    return _level(scene, parents, width, occupied, margin, abs_int, options or api.default_options(), _GridKeys(key, width, occupied),
                   _pyramid_levels(scene, "extend_level"), sequential)
 
 
@@ -549,17 +578,22 @@ def filter_extend_level(scene: api.Scene, patches: api.Batch, cell_start, width:
 
     `expanded`: expanded_ per row (default 0).  ValueError before any map update for a cell with no winner, an empty cell or a
     kept patch that is already expanded (processCell does not extend it, :380)."""
-    n_levels = _pyramid_levels(scene, "filter_extend_level")
+    return _filter_extend(scene, patches, cell_start, width, _GridKeys(key, width, occupied), occupied, expanded, margin, abs_int,
+                          options, "filter_extend_level")
+
+
+def _filter_extend(scene, patches, cell_start, width, keys, occupied, expanded, margin, abs_int, options, who):
+    n_levels = _pyramid_levels(scene, who)
     cs = _cell_offsets(patches, cell_start)
     exp = np.zeros(patches.n, np.uint8) if expanded is None else np.ascontiguousarray(expanded).astype(np.uint8).reshape(patches.n)
     if (np.diff(cs) == 0).any():
-        raise ValueError(f"filter_extend_level: cell {int(np.nonzero(np.diff(cs) == 0)[0][0])} is empty")
+        raise ValueError(f"{who}: cell {int(np.nonzero(np.diff(cs) == 0)[0][0])} is empty")
     F = _filter(scene, patches, cs)
     if exp[F.keep].any():
-        raise ValueError(f"filter_extend_level: the kept patch of cell {int(np.nonzero(exp[F.keep])[0][0])} is already expanded")
+        raise ValueError(f"{who}: the kept patch of cell {int(np.nonzero(exp[F.keep])[0][0])} is already expanded")
     losers = np.nonzero(F.removed)[0]
     cell_of = np.repeat(np.arange(len(cs) - 1), np.diff(cs))
-    L = _level(scene, _rows(patches, F.keep), width, occupied, margin, abs_int, options or api.default_options(), key, n_levels,
+    L = _level(scene, _rows(patches, F.keep), width, occupied, margin, abs_int, options or api.default_options(), keys, n_levels,
                events=_rows(patches, losers), event_cell=cell_of[losers])
     return F, L
 
@@ -601,3 +635,256 @@ def seed_tree(scene: api.Scene, batch: api.Batch, patch_init_maxlevel: int = 9, 
     R, L = int(info.n_rows), int(info.n_leaves)
     return SeedTree(np.array(info.root_center, np.float32), float(info.root_width), float(info.scale_floor), rows[:R].copy(),
                     cs[:L + 1].copy(), cc[:L].copy(), cw[:L].copy(), cl[:L].copy(), pc[:L].copy())
+
+
+# ---- the level calls against the real octree -------------------------------------------------------
+
+MAX_TREE_DEPTH = api.OCTREE_MAX_DEPTH
+
+
+def key_depth(key: int) -> int:
+    """Levels of a path key below the root (the root is 1: depth 0)."""
+    return (int(key).bit_length() - 1) // 3
+
+
+class Octree:
+    """The scheduler's DynOctTree (reference include/hpmvs/doctree.h) as hpmvs_octree_locate_batch reads it: the set of branch
+    keys and a dict nonempty leaf key -> the caller's row.  Path keys: a sentinel bit, then 3 bits per level (z y x, Branch::at's
+    child test x > c_); the root Branch is key 1 and implicit.  An empty leaf is a key in neither container whose parent is a
+    branch.  Cells follow from the root by Cell(parent, idx) (double arithmetic, float storage).  The host operations have the
+    reference's meaning; a row is whatever the caller keeps per leaf (an index, a list of patches)."""
+    ROOT = 1
+
+    def __init__(self, root_center, root_width, root_level: int = 0):
+        self.root_center = np.array(root_center, dtype=np.float32).reshape(3)
+        self.root_width = np.float32(root_width)
+        self.root_level = int(root_level)      # rootLevel_: nodeLevel of the root (a subtree keeps the level of its cut)
+        self.branches = set()
+        self.leaves = {}
+        self._below = {}                       # branch key -> nonempty leaves below it
+        self._cells = {self.ROOT: (self.root_center, self.root_width)}
+
+    # -- cells
+    def cell(self, key: int):
+        """(c_, width_) of the cell with path `key`."""
+        c = self._cells.get(key)
+        if c is None:
+            pc, pw = self.cell(key >> 3)
+            c = self._cells[key] = child_cell(pc, pw, key & 7)
+        return c
+
+    def node_level(self, key: int) -> int:
+        """DynOctTree::nodeLevel: log2(root width / width) + rootLevel_."""
+        return key_depth(key) + self.root_level
+
+    def contains(self, p) -> bool:
+        """getRoot()->contains(p) (doctree.cpp:38-42): hw = width_ / 2.0 as float; > below, <= above."""
+        hw = np.float32(float(self.root_width) / 2.0)
+        c = self.root_center
+        q = [np.float32(p[k]) for k in range(3)]
+        return bool(all(q[k] > np.float32(c[k] - hw) for k in range(3)) and all(q[k] <= np.float32(c[k] + hw) for k in range(3)))
+
+    def at(self, p, start: int = ROOT) -> int:
+        """root->at(p): the key of the leaf (of any depth, empty or not) that p descends to, whatever p is."""
+        key = start
+        while True:
+            key = (key << 3) | octant(self.cell(key)[0], p)
+            if key not in self.branches:
+                return key
+
+    def row(self, key: int):
+        return self.leaves.get(key)
+
+    # -- changes
+    def _count(self, key: int, d: int):
+        k = key >> 3
+        while k:
+            self._below[k] = self._below.get(k, 0) + d
+            k >>= 3
+
+    def insert(self, key: int, row):
+        """Put `row` into the EMPTY leaf `key`, creating the branches on the way (what addConditional's splits leave behind)."""
+        if not 1 <= key_depth(key) <= MAX_TREE_DEPTH or key in self.branches or key in self.leaves:
+            raise ValueError(f"Octree.insert: {key:#x} is a branch, a nonempty leaf or no key within {MAX_TREE_DEPTH} levels")
+        k = key >> 3
+        while k != self.ROOT:
+            if k in self.leaves:
+                raise ValueError(f"Octree.insert: {key:#x} lies below the nonempty leaf {k:#x}")
+            self.branches.add(k)
+            k >>= 3
+        self.leaves[key] = row
+        self._count(key, +1)
+
+    def split(self, key: int):
+        """Leaf::split: the leaf becomes a Branch with eight empty leaves; its row (None for an empty leaf) is returned."""
+        if key in self.branches or key_depth(key) >= MAX_TREE_DEPTH or (key >> 3) != self.ROOT and (key >> 3) not in self.branches:
+            raise ValueError(f"Octree.split: {key:#x} is no leaf that can be split")
+        row = self.leaves.pop(key, None)
+        if row is not None:
+            self._count(key, -1)
+        self.branches.add(key)
+        return row
+
+    def add_conditional(self, p, width, row):
+        """DynOctTree::addConditional(p, width) (doctree.h:397-419): None when p's leaf is nonempty or narrower than `width`,
+        else the key of the leaf `row` went into, after splitting while leaf width / 2.0 > width."""
+        width = np.float32(width)
+        key = self.at(p)
+        if key in self.leaves or self.cell(key)[1] < width:
+            return None
+        while key_depth(key) < MAX_TREE_DEPTH and float(self.cell(key)[1]) / 2.0 > float(width):
+            self.branches.add(key)
+            key = (key << 3) | octant(self.cell(key)[0], p)
+        self.leaves[key] = row
+        self._count(key, +1)
+        return key
+
+    def remove(self, key: int) -> int:
+        """DynOctTree::remove(leaf) (doctree.h:422-450): the leaf is cleared; when its parent Branch is then empty all through, the
+        parent becomes ONE empty leaf (remove_internal collapses one level only; the root stays a Branch).  Returns the key of
+        the leaf that is there afterwards."""
+        if self.leaves.pop(key, None) is not None:
+            self._count(key, -1)
+        par = key >> 3
+        if par == self.ROOT or self._below.get(par, 0):
+            return key
+        self._drop(par)
+        return par
+
+    def _drop(self, key: int):
+        self.branches.discard(key)
+        self._below.pop(key, None)
+        for i in range(8):
+            if ((key << 3) | i) in self.branches:
+                self._drop((key << 3) | i)
+
+    # -- views
+    @staticmethod
+    def _aligned(key: int) -> int:
+        d = key_depth(key)
+        return (key ^ (1 << (3 * d))) << (3 * (MAX_TREE_DEPTH - d))
+
+    def leaf_table(self):
+        """The nonempty leaves in Leaf_iterator order (children 0 .. 7, depth first): (keys [L] uint64, rows (list), cell_center
+        [L, 3], cell_width [L])."""
+        keys = sorted(self.leaves, key=self._aligned)
+        cc = np.array([self.cell(k)[0] for k in keys], np.float32).reshape(len(keys), 3)
+        cw = np.array([self.cell(k)[1] for k in keys], np.float32)
+        return np.array(keys, np.uint64), [self.leaves[k] for k in keys], cc, cw
+
+    def snapshot(self, patch_center) -> "OctreeSnapshot":
+        """The tree as regularize_level reads it; patch_center[l]: data[0]->center_ of leaf l of leaf_table()."""
+        _, _, cc, cw = self.leaf_table()
+        return OctreeSnapshot(self.root_center, float(self.root_width), cc, cw, patch_center)
+
+    def branch_keys(self) -> np.ndarray:
+        return np.array(sorted(self.branches), np.uint64)
+
+    def subtree(self, key: int) -> "Octree":
+        """The tree below the branch `key`, re-rooted there (the reference's subtrees, DynOctTree::swapRoot): keys re-based, the
+        root's level kept for nodeLevel."""
+        if key != self.ROOT and key not in self.branches:
+            raise ValueError(f"Octree.subtree: {key:#x} is no branch")
+        d = key_depth(key)
+        c, w = self.cell(key)
+        sub = Octree(c, w, self.root_level + d)
+
+        def rebase(k):
+            dk = key_depth(k) - d
+            return (k & ((1 << (3 * dk)) - 1)) | (1 << (3 * dk)) if dk > 0 and (k >> (3 * dk)) == key else 0
+
+        sub.branches = {rebase(k) for k in self.branches} - {0}
+        for k, row in self.leaves.items():
+            if rebase(k):
+                sub.leaves[rebase(k)] = row
+                sub._count(rebase(k), +1)
+        return sub
+
+    @classmethod
+    def from_seed_tree(cls, tree: "SeedTree") -> "Octree":
+        """The tree right after Scene::initPatches: leaf l of `tree` under the key its cell_center descends to in cell_level[l]
+        levels, row l; the branches are all proper prefixes (add() only ever splits)."""
+        t = cls(tree.root_center, tree.root_width)
+        for l in range(tree.n_leaves):
+            key = cls.ROOT
+            for _ in range(int(tree.cell_level[l])):
+                key = (key << 3) | octant(t.cell(key)[0], tree.cell_center[l])
+            if t.cell(key)[1] != tree.cell_width[l]:
+                raise ValueError(f"Octree.from_seed_tree: leaf {l} is not a cell of the root's subdivision")
+            t.insert(key, l)
+        return t
+
+    def locate(self, scene: api.Scene, points, add_width=None) -> api.OctreeLocation:
+        """ONE hpmvs_octree_locate_batch against the tree as it stands (leaf_index: into leaf_table())."""
+        return api.octree_locate_batch(scene, self.root_center, self.root_width, self.branch_keys(), self.leaf_table()[0], points, add_width)
+
+
+REFUSED = 0   # no path key: what addConditional's refusal maps to; in `occupied` from the start of a level
+
+
+class _TreeKeys:
+    """The candidates' leaves in the real tree: two hpmvs_octree_locate_batch calls per level.  Within a level every parent has
+    the same width w, an exact level width of the tree, so addConditional(0.9 w) ends at the depth d* of width w: whatever the
+    tree as the level finds it decides is static (a nonempty leaf, or structure finer than w: never refined / REFUSED), and
+    whatever the level's own insertions decide is equality of the d*-prefix of the point -- the walk's pre_key / post_key."""
+
+    def __init__(self, scene, tree: Octree, width):
+        self.scene, self.tree = scene, tree
+        self.width = np.float32(width)
+        self.add_width = np.float32(float(self.width) * 0.9)     # cell->width_ * 0.9, narrowed by addConditional's float parameter
+        w, d = tree.root_width, 0
+        while w > self.width and d < MAX_TREE_DEPTH:
+            w = np.float32(float(w) / 2.0); d += 1
+        if w != self.width or d < 1:
+            raise ValueError("extend_level_tree: `width` is not the width of a level of the tree")
+        self.index = (tree.branch_keys(), tree.leaf_table()[0])
+
+    def _locate(self, points):
+        t = self.tree
+        return api.octree_locate_batch(self.scene, t.root_center, t.root_width, self.index[0], self.index[1], points, self.add_width)
+
+    def pre(self, center):
+        r = self._locate(center)
+        inside = r.inside != 0
+        skip = inside & ((r.leaf_index >= 0) | (r.leaf_width < self.width))            # CellProcessor.cpp:124
+        # an outside candidate is never pre-gated: a key that nothing else can hold
+        return [int(r.target_key[t]) if inside[t] else ("outside", t) for t in range(len(center))], skip.astype(np.uint8)
+
+    def post(self, center, refined):
+        r = self._locate(center)
+        border = refined & (r.inside == 0)                                              # CellProcessor.cpp:147
+        key = [None if not refined[t] else ("border", t) if border[t] else int(r.target_key[t]) for t in range(len(center))]
+        return key, border
+
+
+def _insert_accepted(tree: Octree, L: LevelResult, rows):
+    for k, t in enumerate(L.accepted):
+        tree.insert(L.leaf_key[t], rows[k] if rows is not None else ("extend", t))
+
+
+def extend_level_tree(scene: api.Scene, parents: api.Batch, width: float, tree: Octree, margin: float = 1.0, abs_int: int = 0,
+                      options=None, sequential: bool = True, events=None, event_cell=(), rows=None) -> LevelResult:
+    """extend_level against the scheduler's real octree (or a subtree of it): CellProcessor::extend over `parents`, the leaves
+    of ONE node level (all of width `width`), in the scheduler's order.  The walk is extend_level's; the keys come from
+    hpmvs_octree_locate_batch (_TreeKeys).  Stage codes as extend_level's, where 20 is the pre-gate (a nonempty leaf of any
+    depth, or structure finer than `width`, inside the root), 26 addConditional's refusal, and 27 = BORDER: a candidate that
+    passed every gate but lies outside tree's root.  Border candidates are returned in LevelResult.border (queue order) for the
+    scheduler to route (processBorderCellQueue); they are not inserted and write no depths.  The accepted candidates are
+    inserted into `tree` at LevelResult.leaf_key, with the branches on the way, under rows[k] for the k-th accepted (default a
+    ("extend", candidate) tuple).  events / event_cell: subtraction events as in filter_extend_level."""
+    keys = _TreeKeys(scene, tree, width)
+    L = _level(scene, parents, width, {REFUSED}, margin, abs_int, options or api.default_options(), keys,
+               _pyramid_levels(scene, "extend_level_tree"), sequential, events, event_cell)
+    _insert_accepted(tree, L, rows)
+    return L
+
+
+def filter_extend_level_tree(scene: api.Scene, patches: api.Batch, cell_start, width: float, tree: Octree, expanded=None,
+                             margin: float = 1.0, abs_int: int = 0, options=None, rows=None):
+    """filter_extend_level against the real octree: the same walk with extend_level_tree's keys, the filters' losers as events.
+    Returns (FilterResult, LevelResult)."""
+    keys = _TreeKeys(scene, tree, width)
+    F, L = _filter_extend(scene, patches, cell_start, width, keys, {REFUSED}, expanded, margin, abs_int, options,
+                          "filter_extend_level_tree")
+    _insert_accepted(tree, L, rows)
+    return F, L

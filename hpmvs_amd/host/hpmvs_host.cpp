@@ -627,6 +627,27 @@ bool Scene::seedTree(std::vector<Ppatch3d>& patches, const HpmvsOptions& options
     out.patchCenter.assign(pc.begin(), pc.begin() + 3 * L);
     return true;
 }
+bool Scene::octreeLocate(const OctreeIndex& tree, const std::vector<float>& points, const std::vector<float>& addWidth,
+                         OctreeLocation& out) const {
+    hpmvs_scene* dev = deviceScene();
+    if (!dev) return false;
+    const size_t n = points.size() / 3;
+    if (points.size() != 3 * n || (!addWidth.empty() && addWidth.size() != n)) { std::cerr << "hpmvs: octreeLocate: points [n][3], addWidth [n] or empty" << std::endl; return false; }
+    hpmvs_octree_index t;
+    for (int k = 0; k < 3; k++) t.root_center[k] = tree.rootCenter[k];
+    t.root_width = tree.rootWidth;
+    t.n_branches = (int32_t)tree.branchKeys.size(); t.n_leaves = (int32_t)tree.leafKeys.size();
+    t.branch_key = tree.branchKeys.data(); t.leaf_key = tree.leafKeys.data();
+    out.inside.assign(n, 0); out.leafKey.assign(n, 0); out.leafIndex.assign(n, 0); out.leafWidth.assign(n, 0.0f);
+    out.leafCenter.assign(3 * n, 0.0f); out.targetKey.assign(n, 0);
+    if (hpmvs_octree_locate_batch(dev, &t, (int)n, points.data(), addWidth.empty() ? nullptr : addWidth.data(), out.inside.data(),
+                                  out.leafKey.data(), out.leafIndex.data(), out.leafWidth.data(), out.leafCenter.data(),
+                                  out.targetKey.data(), 0, nullptr) != HPMVS_OK) {
+        std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl;
+        return false;
+    }
+    return true;
+}
 bool Scene::levelSupport(const Patch3d* const* patches, size_t n, int minLevel, std::vector<int>& support) const {
     support.assign(n, 0);
     hpmvs_scene* dev = deviceScene();

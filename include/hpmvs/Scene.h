@@ -20,6 +20,14 @@
 #include <hpmvs/Patch3d.h>
 struct hpmvs_scene;
 namespace mo3d {
+// A DynOctTree as path keys (include/hpmvs_amd.h: hpmvs_octree_index): the root cell, every Branch below it, the nonempty leaves.
+struct OctreeIndex {
+    float rootCenter[3];
+    float rootWidth;
+    std::vector<uint64_t> branchKeys;
+    std::vector<uint64_t> leafKeys;
+};
+
 class Scene {
 public:
     Scene();
@@ -70,6 +78,22 @@ public:
     // pixels, every pyramid level) and pixelFreeTests' cell; writes[i]: the cell per attached image.  nLevels: pyramid levels.
     bool depthFootprints(const Patch3d* const* patches, size_t n, std::vector<std::vector<uint64_t> >& reads,
                          std::vector<std::vector<uint64_t> >& writes, int nLevels = 6) const;
+    // The scheduler's octree as CellProcessor::extend consults it (CellProcessor.cpp:122-125, 147-154), for a list of points as
+    // ONE batched GPU call (hpmvs_octree_locate_batch): root->at(p), getRoot()->contains(p) and the leaf
+    // DynOctTree::addConditional(p, addWidth) would put p in.  OctreeIndex names the tree by path keys (sentinel bit, 3 bits per
+    // level z y x, root = 1): every Branch below the root and the nonempty leaves; addWidth empty: no target keys.  False (and
+    // hpmvs_last_error) when the keys are no tree.  The batched level on top of it is not here yet: PatchOptimizer::extendLevel
+    // still takes its per-point LeafKeyFn.
+    struct OctreeLocation {
+        std::vector<uint8_t> inside;       // [n] root.contains(p)
+        std::vector<uint64_t> leafKey;     // [n] path key of the located leaf
+        std::vector<int32_t> leafIndex;    // [n] index into OctreeIndex::leafKeys, -1: an empty leaf
+        std::vector<float> leafWidth;      // [n]
+        std::vector<float> leafCenter;     // [n][3]
+        std::vector<uint64_t> targetKey;   // [n] 0: addConditional refuses
+    };
+    bool octreeLocate(const OctreeIndex& tree, const std::vector<float>& points /*[n][3]*/, const std::vector<float>& addWidth /*[n] or empty*/,
+                      OctreeLocation& out) const;
     std::map<std::string, int> dict_;
     std::vector<Camera> cameras_;
     std::vector<Image> images_;

@@ -346,6 +346,40 @@ int hpmvs_seed_tree_batch(hpmvs_scene *s, hpmvs_patch_batch *b, int patch_init_m
                           float *cell_center /*[n][3]*/, float *cell_width /*[n]*/, int32_t *cell_level /*[n]*/,
                           float *patch_center /*[n][3], nullable*/, int on_device, void *stream);
 
+/* The scheduler's octree as CellProcessor::extend consults it (reference src/hpmvs/CellProcessor.cpp:122-125, 147-154): for every
+ * point the leaf root->at(p) of any depth, getRoot()->contains(p) and the leaf DynOctTree::addConditional(p, add_width) would put
+ * it in (include/hpmvs/doctree.h:250-255, 397-419; src/hpmvs/doctree.cpp:30-42).  The tree is given as PATH KEYS: a sentinel bit,
+ * then 3 bits per level (z y x, a bit set where p > c_), the root being 1; at most HPMVS_MAX_TREE_DEPTH levels.  branch_key: every
+ * Branch below the root (the root, or a subtree's root, is implicit); leaf_key: the NONEMPTY leaves.  An empty leaf is a key in
+ * neither set below a branch; the empty tree (no key at all) has eight empty leaves at depth 1.  Centres and widths follow from
+ * the root by Cell(parent, idx) (double arithmetic, float storage).
+ *   inside[i]       root.contains(points[i])  (a point outside still descends to a leaf, as Branch::at does; a NaN coordinate
+ *                   takes child bit 0)
+ *   leaf_key[i]     key of the located leaf;  leaf_index[i]  its index in t->leaf_key, -1 for an empty leaf
+ *   leaf_width[i], leaf_center[i]             its width_ / c_
+ *   target_key[i]   0 when addConditional(points[i], add_width[i]) refuses (nonempty leaf, or leaf width < add_width), else the
+ *                   key of the leaf reached by splitting while width / 2.0 > add_width (cut off at HPMVS_MAX_TREE_DEPTH levels,
+ *                   where the reference would go on splitting); 0 everywhere without add_width
+ * Every output is nullable.  n = 0 and an empty tree are valid.  HPMVS_ERR_ARG before any output is written when the keys are no
+ * tree: a word that is no key of a cell below the root, a leaf deeper than HPMVS_MAX_TREE_DEPTH levels or a branch deeper than
+ * HPMVS_MAX_TREE_DEPTH - 1, a key that occurs twice (in one array or in both), a key whose parent prefix is neither a branch nor the
+ * root; also for a root that is not finite or has no positive width.  (Whether the branches' other children are complete is not
+ * the table's business: what is in neither set is an empty leaf.)  The look-up table is built in a launch workspace of the scene
+ * (12 bytes per slot, 2 x keys slots); host or device pointers as for hpmvs_optimize_batch (t is always a host structure, its
+ * key arrays follow on_device).  The call is host-synchronous in both forms up to the table's verdict. */
+typedef struct {
+    float root_center[3];
+    float root_width;
+    int32_t n_branches;
+    int32_t n_leaves;
+    const uint64_t *branch_key;   /* [n_branches] */
+    const uint64_t *leaf_key;     /* [n_leaves] */
+} hpmvs_octree_index;
+int hpmvs_octree_locate_batch(const hpmvs_scene *s, const hpmvs_octree_index *t, int n, const float *points /*[n][3]*/,
+                              const float *add_width /*[n], nullable*/, uint8_t *inside /*[n]*/, uint64_t *leaf_key /*[n]*/,
+                              int32_t *leaf_index /*[n]*/, float *leaf_width /*[n]*/, float *leaf_center /*[n][3]*/,
+                              uint64_t *target_key /*[n]*/, int on_device, void *stream);
+
 /* Host-pointer calls and pinned memory.  An array of a host-pointer call (on_device = 0) that lies in pinned host memory
  * mapped into the GPU's address space -- hipHostMalloc / hipHostRegister, torch's pin_memory(), hpmvs_host_alloc below --
  * is used IN PLACE: the kernels read a patch's inputs once and write its outputs once, so they travel over PCIe while the
