@@ -75,6 +75,7 @@ EXPORTS = [
     "hpmvs_host_alloc", "hpmvs_host_free", "hpmvs_last_staging",
     "hpmvs_undistort", "hpmvs_undistort_map", "hpmvs_scene_set_view_distorted",
     "hpmvs_regularize_batch", "hpmvs_filter_batch", "hpmvs_seed_tree_batch", "hpmvs_octree_locate_batch",
+    "hpmvs_octree_insert_batch", "hpmvs_octree_route_batch",
 ]
 
 _lib = None
@@ -140,6 +141,8 @@ def lib():
     L.hpmvs_seed_tree_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_int, C.c_int, C.POINTER(SeedTreeInfo), C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.hpmvs_octree_locate_batch.argtypes = [C.c_void_p, C.POINTER(OctreeIndex), C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
+    L.hpmvs_octree_insert_batch.argtypes = [C.c_void_p, C.POINTER(OctreeIndex), C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+    L.hpmvs_octree_route_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     _lib = L
     return L
 
@@ -562,24 +565,66 @@ class OctreeLocation:
     target_key: np.ndarray         # [n] uint64 addConditional's leaf, 0: refused (or no add_width)
 
 
-def octree_locate_batch(scene: Scene, root_center, root_width, branch_key, leaf_key, points, add_width=None) -> OctreeLocation:
-    """root->at(p), getRoot()->contains(p) and DynOctTree::addConditional's target for every point against an octree given as
-    path keys (include/hpmvs_amd.h: hpmvs_octree_locate_batch): branch_key the branches below the root, leaf_key the nonempty
-    leaves.  add_width: a scalar or [n] (None: no target keys).  HpmvsError when the keys are no tree."""
-    bk = np.ascontiguousarray(branch_key, dtype=np.uint64).reshape(-1)
-    lk = np.ascontiguousarray(leaf_key, dtype=np.uint64).reshape(-1)
-    pts = np.asarray(points, dtype=np.float32)
-    pts = np.ascontiguousarray(pts.reshape(-1, pts.shape[-1] if pts.ndim > 1 else 3)[:, :3])   # [n, 3] or [n, 4] centres
-    n = len(pts)
-    aw = None if add_width is None else np.ascontiguousarray(np.broadcast_to(np.asarray(add_width, dtype=np.float32), (n,)))
+def _octree_index(root_center, root_width, bk, lk) -> OctreeIndex:
     t = OctreeIndex()
     for k in range(3):
         t.root_center[k] = float(np.float32(root_center[k]))
     t.root_width = float(np.float32(root_width))
     t.n_branches, t.n_leaves = len(bk), len(lk)
     t.branch_key, t.leaf_key = bk.ctypes.data, lk.ctypes.data
+    return t
+
+
+def _points3(points) -> np.ndarray:
+    pts = np.asarray(points, dtype=np.float32)
+    return np.ascontiguousarray(pts.reshape(-1, pts.shape[-1] if pts.ndim > 1 else 3)[:, :3])   # [n, 3] or [n, 4] centres
+
+
+def octree_locate_batch(scene: Scene, root_center, root_width, branch_key, leaf_key, points, add_width=None) -> OctreeLocation:
+    """root->at(p), getRoot()->contains(p) and DynOctTree::addConditional's target for every point against an octree given as
+    path keys (include/hpmvs_amd.h: hpmvs_octree_locate_batch): branch_key the branches below the root, leaf_key the nonempty
+    leaves.  add_width: a scalar or [n] (None: no target keys).  HpmvsError when the keys are no tree."""
+    bk = np.ascontiguousarray(branch_key, dtype=np.uint64).reshape(-1)
+    lk = np.ascontiguousarray(leaf_key, dtype=np.uint64).reshape(-1)
+    pts = _points3(points)
+    n = len(pts)
+    aw = None if add_width is None else np.ascontiguousarray(np.broadcast_to(np.asarray(add_width, dtype=np.float32), (n,)))
+    t = _octree_index(root_center, root_width, bk, lk)
     r = OctreeLocation(np.zeros(n, np.uint8), np.zeros(n, np.uint64), np.zeros(n, np.int32), np.zeros(n, np.float32),
                        np.zeros((n, 3), np.float32), np.zeros(n, np.uint64))
     _chk(lib().hpmvs_octree_locate_batch(scene.h, C.byref(t), n, pts.ctypes.data, None if aw is None else aw.ctypes.data,
                                          *[getattr(r, k).ctypes.data for k in OCTREE_OUTPUTS], 0, None))
     return r
+
+
+@dataclass
+class OctreeInsertion:
+    accepted: np.ndarray           # [n] uint8 addConditional's return, in queue order
+    leaf_key: np.ndarray           # [n] uint64 *outleaf: the leaf the patch went into, or the one that refused it
+    blocker: np.ndarray            # [n] int32 queue index of the earlier patch behind a refusal, -1: accepted, or refused by the tree
+
+
+def octree_insert_batch(scene: Scene, root_center, root_width, branch_key, leaf_key, points, add_width) -> OctreeInsertion:
+    """DynOctTree::addConditional(points[i], add_width[i]) for i = 0 .. n - 1 in that order against the octree given as path
+    keys, every patch seeing the earlier ones' leaves (include/hpmvs_amd.h: hpmvs_octree_insert_batch; the insertion loop of
+    CellProcessor::processBorderCellQueue).  The keys given are not changed: the caller enters the accepted ones."""
+    bk = np.ascontiguousarray(branch_key, dtype=np.uint64).reshape(-1)
+    lk = np.ascontiguousarray(leaf_key, dtype=np.uint64).reshape(-1)
+    pts = _points3(points)
+    n = len(pts)
+    aw = np.ascontiguousarray(np.broadcast_to(np.asarray(add_width, dtype=np.float32), (n,)))
+    t = _octree_index(root_center, root_width, bk, lk)
+    r = OctreeInsertion(np.zeros(n, np.uint8), np.zeros(n, np.uint64), np.zeros(n, np.int32))
+    _chk(lib().hpmvs_octree_insert_batch(scene.h, C.byref(t), n, pts.ctypes.data, aw.ctypes.data, r.accepted.ctypes.data,
+                                         r.leaf_key.ctypes.data, r.blocker.ctypes.data, 0, None))
+    return r
+
+
+def octree_route_batch(scene: Scene, roots, points) -> np.ndarray:
+    """For every point the index of the first root in list order (roots [n_trees, 4]: c_, width_) whose Cell::contains holds,
+    -1 when none does (include/hpmvs_amd.h: hpmvs_octree_route_batch; CellProcessor::distributeBorderCell)."""
+    rt = np.ascontiguousarray(np.asarray(roots, dtype=np.float32).reshape(-1, 4))
+    pts = _points3(points)
+    tree = np.zeros(len(pts), np.int32)
+    _chk(lib().hpmvs_octree_route_batch(scene.h, len(rt), rt.ctypes.data, len(pts), pts.ctypes.data, tree.ctypes.data, 0, None))
+    return tree

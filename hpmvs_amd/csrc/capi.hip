@@ -1846,27 +1846,59 @@ int hpmvs_seed_tree_batch(hpmvs_scene* s, hpmvs_patch_batch* b, int patch_init_m
     }
     return c.finish();   // (waits in both forms: the temporaries are freed when this call returns)
 }
-// root->at(p), Cell::contains and addConditional's target for a level's points against the scheduler's octree (kernel_octree.hip,
-// octree.hpp).  The table lives in a launch workspace: [1 KB counter block, untouched] [verdict] [keys] [values]; the arrays go
-// through Call.  The verdict of the check kernel is read back before the locate kernel is enqueued: a refused table writes nothing.
+// ---- the scheduler's octree as path keys (hpmvs_octree_index; kernel_octree.hip, kernel_octree_insert.hip, octree.hpp).  The
+// look-up table lives in a launch workspace: [1 KB counter block, untouched] [verdict] [keys] [values]; the arrays go through
+// Call.  The verdict of the check kernel is read back before the kernel that uses the table is enqueued: a refused table
+// writes nothing.
+struct OctreeLayout { size_t slots, o_hdr, o_keys, o_vals; };
+static int octree_index_check(const hpmvs_scene* s, const hpmvs_octree_index* t, int n, const float* points, const std::string& who,
+                              OctreeLayout* L) {
+    if (hpmvs_device_count() <= 0) return fail(HPMVS_ERR_NODEVICE, who + ": no HIP device visible");
+    if (!s || !t) return fail(HPMVS_ERR_ARG, who + ": null scene / octree");
+    if (!s->committed) return fail(HPMVS_ERR_STATE, who + ": scene not committed");
+    if (n < 0 || t->n_branches < 0 || t->n_leaves < 0) return fail(HPMVS_ERR_ARG, who + ": negative count");
+    if ((t->n_branches > 0 && !t->branch_key) || (t->n_leaves > 0 && !t->leaf_key)) return fail(HPMVS_ERR_ARG, who + ": key arrays missing");
+    if (n > 0 && !points) return fail(HPMVS_ERR_ARG, who + ": points missing");
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(t->root_center[k])) return fail(HPMVS_ERR_ARG, who + ": root centre not finite");
+    if (!(t->root_width > 0.0f) || !std::isfinite(t->root_width)) return fail(HPMVS_ERR_ARG, who + ": root width must be finite and > 0");
+    const size_t nk = (size_t)t->n_branches + (size_t)t->n_leaves;
+    if (nk > ((size_t)1 << 29)) return fail(HPMVS_ERR_ARG, who + ": the octree does not fit the launch workspace");
+    L->slots = octree::table_slots(nk);
+    L->o_hdr = kQueueSlotBytes;
+    L->o_keys = reg_align(L->o_hdr + 16);
+    L->o_vals = reg_align(L->o_keys + 8 * L->slots);
+    if (reg_align(L->o_vals + 4 * L->slots) > s->ws_bytes) return fail(HPMVS_ERR_ARG, who + ": the octree does not fit the launch workspace");
+    return HPMVS_OK;
+}
+// builds and checks the table in the workspace w (the caller holds it); host-synchronous up to the verdict
+static int octree_table_build(const hpmvs_octree_index* t, const unsigned long long* dbk, const unsigned long long* dlk, const OctreeLayout& L,
+                              char* w, hipStream_t st, const std::string& who) {
+    int32_t* verdict = (int32_t*)(w + L.o_hdr);
+    unsigned long long* keys = (unsigned long long*)(w + L.o_keys);
+    int32_t* vals = (int32_t*)(w + L.o_vals);
+    HIPCHK(hipMemsetAsync(verdict, 0, 16, st));
+    HIPCHK(hipMemsetAsync(keys, 0, 8 * L.slots, st));
+    if (t->n_branches + t->n_leaves == 0) return HPMVS_OK;
+    launch_octree_build(dbk, t->n_branches, dlk, t->n_leaves, keys, vals, (uint32_t)L.slots, verdict, st);
+    HIPCHK(hipGetLastError());
+    int32_t h = 0;
+    HIPCHK(hipMemcpyAsync(&h, verdict, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (h & octree::kBadKey) return fail(HPMVS_ERR_ARG, who + ": a word is no path key of a cell below the root (a leaf deeper than 21 levels, a branch deeper than 20)");
+    if (h & octree::kBadTwice) return fail(HPMVS_ERR_ARG, who + ": a key occurs twice (within the branch or leaf keys, or in both)");
+    if (h & octree::kBadOrphan) return fail(HPMVS_ERR_ARG, who + ": a key's parent prefix is neither a branch nor the root");
+    return HPMVS_OK;
+}
+// root->at(p), Cell::contains and addConditional's target for a level's points against the scheduler's octree
 int hpmvs_octree_locate_batch(const hpmvs_scene* s, const hpmvs_octree_index* t, int n, const float* points, const float* add_width,
                               uint8_t* inside, uint64_t* leaf_key, int32_t* leaf_index, float* leaf_width, float* leaf_center,
                               uint64_t* target_key, int on_device, void* stream) {
-    if (hpmvs_device_count() <= 0) return fail(HPMVS_ERR_NODEVICE, "octree_locate_batch: no HIP device visible");
-    if (!s || !t) return fail(HPMVS_ERR_ARG, "octree_locate_batch: null scene / octree");
-    if (!s->committed) return fail(HPMVS_ERR_STATE, "octree_locate_batch: scene not committed");
-    if (n < 0 || t->n_branches < 0 || t->n_leaves < 0) return fail(HPMVS_ERR_ARG, "octree_locate_batch: negative count");
-    if ((t->n_branches > 0 && !t->branch_key) || (t->n_leaves > 0 && !t->leaf_key)) return fail(HPMVS_ERR_ARG, "octree_locate_batch: key arrays missing");
-    if (n > 0 && !points) return fail(HPMVS_ERR_ARG, "octree_locate_batch: points missing");
-    for (int k = 0; k < 3; k++)
-        if (!std::isfinite(t->root_center[k])) return fail(HPMVS_ERR_ARG, "octree_locate_batch: root centre not finite");
-    if (!(t->root_width > 0.0f) || !std::isfinite(t->root_width)) return fail(HPMVS_ERR_ARG, "octree_locate_batch: root width must be finite and > 0");
+    const char* who = "octree_locate_batch";
+    OctreeLayout L;
+    int rc = octree_index_check(s, t, n, points, who, &L);
+    if (rc) return rc;
     const size_t nb = (size_t)t->n_branches, nl = (size_t)t->n_leaves, np = (size_t)n;
-    if (nb + nl > ((size_t)1 << 29)) return fail(HPMVS_ERR_ARG, "octree_locate_batch: the octree does not fit the launch workspace");
-    const size_t slots = octree::table_slots(nb + nl);
-    const size_t o_hdr = kQueueSlotBytes, o_keys = reg_align(o_hdr + 16), o_vals = reg_align(o_keys + 8 * slots), o_end = reg_align(o_vals + 4 * slots);
-    if (o_end > s->ws_bytes) return fail(HPMVS_ERR_ARG, "octree_locate_batch: the octree does not fit the launch workspace");
-    int rc;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     Call c(s, on_device, st);
@@ -1890,23 +1922,87 @@ int hpmvs_octree_locate_batch(const hpmvs_scene* s, const hpmvs_octree_index* t,
     if ((rc = acquire_workspace(s, &q, &slot, st))) return rc;
     struct Release { const hpmvs_scene* s; int slot; hipStream_t st; ~Release() { hipEventRecord(s->slot_done[slot], st); s->slot_used[slot] = true; } } rel{s, slot, st};
     char* w = (char*)q;
-    int32_t* verdict = (int32_t*)(w + o_hdr);
-    unsigned long long* keys = (unsigned long long*)(w + o_keys);
-    int32_t* vals = (int32_t*)(w + o_vals);
-    HIPCHK(hipMemsetAsync(verdict, 0, 16, st));
-    HIPCHK(hipMemsetAsync(keys, 0, 8 * slots, st));
-    if (nb + nl) {
-        launch_octree_build(dbk, t->n_branches, dlk, t->n_leaves, keys, vals, (uint32_t)slots, verdict, st);
-        HIPCHK(hipGetLastError());
-        int32_t h = 0;
-        HIPCHK(hipMemcpyAsync(&h, verdict, sizeof(h), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (h & octree::kBadKey) return fail(HPMVS_ERR_ARG, "octree_locate_batch: a word is no path key of a cell below the root (a leaf deeper than 21 levels, a branch deeper than 20)");
-        if (h & octree::kBadTwice) return fail(HPMVS_ERR_ARG, "octree_locate_batch: a key occurs twice (within the branch or leaf keys, or in both)");
-        if (h & octree::kBadOrphan) return fail(HPMVS_ERR_ARG, "octree_locate_batch: a key's parent prefix is neither a branch nor the root");
-    }
+    if ((rc = octree_table_build(t, dbk, dlk, L, w, st, who))) return rc;
     const float root[4] = {t->root_center[0], t->root_center[1], t->root_center[2], t->root_width};
-    launch_octree_locate(root, keys, vals, (uint32_t)slots, n, dpts, daw, out, st);
+    launch_octree_locate(root, (unsigned long long*)(w + L.o_keys), (int32_t*)(w + L.o_vals), (uint32_t)L.slots, n, dpts, daw, out, st);
+    HIPCHK(hipGetLastError());
+    return c.finish();
+}
+// CellProcessor::processBorderCellQueue's insertion loop (CellProcessor.cpp:500-531): addConditional(points[i], add_width[i]) for
+// i = 0 .. n - 1 IN THAT ORDER against the tree t, which stays the caller's (kernel_octree_insert.hip: static kernel, stable sort by
+// static leaf, one wavefront per leaf's run).  The scratch is the call's own, sized by n alone.
+int hpmvs_octree_insert_batch(const hpmvs_scene* s, const hpmvs_octree_index* t, int n, const float* points, const float* add_width,
+                              uint8_t* accepted, uint64_t* leaf_key, int32_t* blocker, int on_device, void* stream) {
+    const char* who = "octree_insert_batch";
+    OctreeLayout L;
+    int rc = octree_index_check(s, t, n, points, who, &L);
+    if (rc) return rc;
+    if (n > 0 && (!add_width || !accepted || !leaf_key)) return fail(HPMVS_ERR_ARG, "octree_insert_batch: add_width / accepted / leaf_key missing");
+    const size_t nb = (size_t)t->n_branches, nl = (size_t)t->n_leaves, np = (size_t)n;
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    Call c(s, on_device, st);
+    const unsigned long long* dbk = (const unsigned long long*)c.in(t->branch_key, nb);
+    const unsigned long long* dlk = (const unsigned long long*)c.in(t->leaf_key, nl);
+    const float* dpts = c.in(points, 3 * np);
+    const float* daw = c.in(add_width, np);
+    OctreeInsertOut out;   // (the static and the replay kernel between them write every entry: no zero fill)
+    out.accepted = c.arr(accepted, np, Call::kCopyBack);
+    out.leaf_key = (unsigned long long*)c.arr(leaf_key, np, Call::kCopyBack);
+    out.blocker = c.arr(blocker, np, Call::kCopyBack);
+    OctreeInsertScratch S;
+    memset(&S, 0, sizeof(S));
+    if (n > 0) {
+        S.temp_bytes = octree_insert_temp_bytes(n);
+        if (S.temp_bytes == (size_t)-1) return fail(HPMVS_ERR_HIP, "octree_insert_batch: rocPRIM size query failed");
+        // one block: four 8-byte arrays, three 4-byte ones, then rocPRIM's temporary storage
+        const size_t o_temp = reg_align(44 * np);
+        char* blk = (char*)c.scratch(o_temp + S.temp_bytes);
+        if (!blk) return c.error();
+        S.path = (unsigned long long*)blk; S.key_a = S.path + np; S.key_b = S.key_a + np; S.acc_key = S.key_b + np;
+        S.val_a = (uint32_t*)(S.acc_key + np); S.val_b = S.val_a + np; S.acc_owner = (int32_t*)(S.val_b + np);
+        S.temp = blk + o_temp;
+    }
+    if ((rc = c.begin(st))) return rc;
+    // the scene lock is held from here on: the workspace is this call's until its last kernel has been enqueued
+    std::lock_guard<std::recursive_mutex> lk(s->mu);
+    if ((rc = service_quiesce(s))) return rc;
+    int32_t* q;
+    int slot;
+    if ((rc = acquire_workspace(s, &q, &slot, st))) return rc;
+    struct Release { const hpmvs_scene* s; int slot; hipStream_t st; ~Release() { hipEventRecord(s->slot_done[slot], st); s->slot_used[slot] = true; } } rel{s, slot, st};
+    char* w = (char*)q;
+    if ((rc = octree_table_build(t, dbk, dlk, L, w, st, who))) return rc;
+    const float root[4] = {t->root_center[0], t->root_center[1], t->root_center[2], t->root_width};
+    if (launch_octree_insert(root, (unsigned long long*)(w + L.o_keys), (int32_t*)(w + L.o_vals), (uint32_t)L.slots, n, dpts, daw, S, out, st))
+        return fail(HPMVS_ERR_HIP, "octree_insert_batch: rocPRIM sort failed");
+    HIPCHK(hipGetLastError());
+    return c.finish();   // (waits in both forms: the scratch is freed when this call returns)
+}
+// distributeBorderCell's search (CellProcessor.cpp:487-498, 533-540): the first root in list order that contains the point.  The
+// roots are a host array in both forms, like an hpmvs_octree_index: they are checked here and travel in the call's scratch.
+int hpmvs_octree_route_batch(const hpmvs_scene* s, int n_trees, const float* roots, int n, const float* points, int32_t* tree, int on_device,
+                             void* stream) {
+    if (hpmvs_device_count() <= 0) return fail(HPMVS_ERR_NODEVICE, "octree_route_batch: no HIP device visible");
+    if (!s) return fail(HPMVS_ERR_ARG, "octree_route_batch: null scene");
+    if (!s->committed) return fail(HPMVS_ERR_STATE, "octree_route_batch: scene not committed");
+    if (n < 0 || n_trees < 0) return fail(HPMVS_ERR_ARG, "octree_route_batch: negative count");
+    if ((n_trees > 0 && !roots) || (n > 0 && (!points || !tree))) return fail(HPMVS_ERR_ARG, "octree_route_batch: roots / points / tree missing");
+    for (int k = 0; k < 4 * n_trees; k++)
+        if (!std::isfinite(roots[k]) || (k % 4 == 3 && !(roots[k] > 0.0f)))
+            return fail(HPMVS_ERR_ARG, "octree_route_batch: a root is not finite or has no positive width");
+    if (n == 0) return HPMVS_OK;
+    int rc;
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    Call c(s, on_device, st);
+    const float* dpts = c.in(points, 3 * (size_t)n);
+    int32_t* dtree = c.arr(tree, (size_t)n, Call::kCopyBack);   // (every entry is written)
+    float* droots = n_trees ? (float*)c.scratch(16 * (size_t)n_trees) : nullptr;
+    if (n_trees && !droots) return c.error();
+    if ((rc = c.begin(st))) return rc;
+    if (n_trees) HIPCHK(hipMemcpyAsync(droots, roots, 16 * (size_t)n_trees, hipMemcpyHostToDevice, st));   // (pageable: consumed before it returns)
+    launch_octree_route(n_trees, droots, n, dpts, dtree, st);
     HIPCHK(hipGetLastError());
     return c.finish();
 }

@@ -129,6 +129,25 @@ void launch_octree_build(const unsigned long long* branch_key, int nb, const uns
 void launch_octree_locate(const float* root, const unsigned long long* keys, const int32_t* vals, uint32_t slots, int n,
                           const float* points, const float* add_width, const OctreeLocateOut& out, hipStream_t st);
 
+// a round's border patches (kernel_octree_insert.hip, include/hpmvs_amd.h: hpmvs_octree_route_batch, hpmvs_octree_insert_batch).
+// launch_octree_insert reads the table launch_octree_build made and enqueues static kernel, sort and replay on st; != 0: the
+// rocPRIM call failed.  Every entry of every output is written (blocker is nullable).  roots: [n_trees][4] c_, width_ on the device.
+struct OctreeInsertOut {
+    uint8_t* accepted; unsigned long long* leaf_key; int32_t* blocker;
+};
+struct OctreeInsertScratch {
+    unsigned long long *path, *key_a, *key_b, *acc_key;   // [n] each
+    uint32_t *val_a, *val_b;                              // [n] each
+    int32_t* acc_owner;                                   // [n]
+    void* temp;                                           // octree_insert_temp_bytes(n)
+    size_t temp_bytes;
+};
+size_t octree_insert_temp_bytes(int n);   // (size_t)-1: the size query failed
+int launch_octree_insert(const float* root, const unsigned long long* keys, const int32_t* vals, uint32_t slots, int n,
+                         const float* points, const float* add_width, const OctreeInsertScratch& s, const OctreeInsertOut& out,
+                         hipStream_t st);
+void launch_octree_route(int n_trees, const float* roots, int n, const float* points, int32_t* tree, hipStream_t st);
+
 // refined-patch records of the multi-GPU exchange (include/hpmvs_amd.h: hpmvs_record, 192 bytes)
 void launch_pack_records(const DevBatch& b, void* records, hipStream_t st);
 void launch_unpack_records(const void* records, int n, const DevBatch& b, hipStream_t st);

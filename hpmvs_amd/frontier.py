@@ -818,6 +818,15 @@ class Octree:
         """ONE hpmvs_octree_locate_batch against the tree as it stands (leaf_index: into leaf_table())."""
         return api.octree_locate_batch(scene, self.root_center, self.root_width, self.branch_keys(), self.leaf_table()[0], points, add_width)
 
+    def insert_batch(self, scene: api.Scene, points, add_width, rows):
+        """addConditional(points[i], add_width[i]) for i = 0 .. n - 1 in that order as ONE hpmvs_octree_insert_batch against the
+        tree as it stands (every patch sees the earlier ones' leaves), then insert(key, rows[i]) for the accepted patches in
+        queue order.  Returns api.OctreeInsertion (accepted, leaf_key, blocker: include/hpmvs_amd.h)."""
+        r = api.octree_insert_batch(scene, self.root_center, self.root_width, self.branch_keys(), self.leaf_table()[0], points, add_width)
+        for i in np.nonzero(r.accepted)[0]:
+            self.insert(int(r.leaf_key[i]), rows[i])
+        return r
+
 
 REFUSED = 0   # no path key: what addConditional's refusal maps to; in `occupied` from the start of a level
 
@@ -888,3 +897,42 @@ def filter_extend_level_tree(scene: api.Scene, patches: api.Batch, cell_start, w
                           "filter_extend_level_tree")
     _insert_accepted(tree, L, rows)
     return F, L
+
+
+# ---- a round's border patches (reference CellProcessor.cpp:487-540) ---------------------------------
+
+def route_border(scene: api.Scene, trees, points) -> np.ndarray:
+    """CellProcessor::distributeBorderCell for every point as ONE hpmvs_octree_route_batch: the index of the first tree of
+    `trees` (a list of Octree, such as the subtree()s) whose root contains it, -1 for a patch that no root contains (it is
+    dropped, as in the reference)."""
+    roots = np.array([[*t.root_center, t.root_width] for t in trees], np.float32).reshape(len(trees), 4)
+    return api.octree_route_batch(scene, roots, points)
+
+
+@dataclass
+class BorderResult:
+    accepted: np.ndarray           # rows of `border` that went into the tree, in queue order
+    leaf_key: np.ndarray           # [len(accepted)] uint64 path key of the leaf each went into
+    node_level: np.ndarray         # [len(accepted)] int32 DynOctTree::nodeLevel of that leaf
+    flatness: np.ndarray           # [len(accepted)] float32 0: no regularization on border cells (CellProcessor.cpp:514)
+    priority: np.ndarray           # [len(accepted)] float32 handed through for the scheduler's processing_queue
+    insertion: api.OctreeInsertion  # every row's decision, leaf and blocker
+
+
+def insert_border(scene: api.Scene, tree: Octree, border: api.Batch, priority, rows=None) -> BorderResult:
+    """CellProcessor::processBorderCellQueue for one tree: the queued border patches `border` (queue order; routed here by
+    route_border) go in with addConditional(center, scale_3dx_ * 2.0) -- ONE Octree.insert_batch --, the accepted ones write
+    their depths -- ONE hpmvs_set_depths_batch: additions are a minimum, their order does not matter -- and come back with
+    flatness 0 and their priorities for the scheduler's queue.  rows[i]: what the tree keeps for row i (default ("border", i))."""
+    n = border.n
+    priority = np.broadcast_to(np.asarray(priority, np.float32), (n,))
+    add_width = np.array([float(x) * 2.0 for x in border.scale], np.float32)   # double product, narrowed by the float parameter
+    r = tree.insert_batch(scene, border.center, add_width, rows if rows is not None else [("border", i) for i in range(n)])
+    acc = np.nonzero(r.accepted)[0]
+    if len(acc):
+        batch = _rows(border, acc)
+        batch.ok[:] = 1
+        api.set_depths_batch(scene, batch)
+    keys = r.leaf_key[acc]
+    return BorderResult(acc, keys, np.array([tree.node_level(int(k)) for k in keys], np.int32), np.zeros(len(acc), np.float32),
+                        priority[acc].copy(), r)

@@ -648,6 +648,37 @@ bool Scene::octreeLocate(const OctreeIndex& tree, const std::vector<float>& poin
     }
     return true;
 }
+bool Scene::octreeInsert(const OctreeIndex& tree, const std::vector<float>& points, const std::vector<float>& addWidth,
+                         OctreeInsertion& out) const {
+    hpmvs_scene* dev = deviceScene();
+    if (!dev) return false;
+    const size_t n = points.size() / 3;
+    if (points.size() != 3 * n || addWidth.size() != n) { std::cerr << "hpmvs: octreeInsert: points [n][3], addWidth [n]" << std::endl; return false; }
+    hpmvs_octree_index t;
+    for (int k = 0; k < 3; k++) t.root_center[k] = tree.rootCenter[k];
+    t.root_width = tree.rootWidth;
+    t.n_branches = (int32_t)tree.branchKeys.size(); t.n_leaves = (int32_t)tree.leafKeys.size();
+    t.branch_key = tree.branchKeys.data(); t.leaf_key = tree.leafKeys.data();
+    out.accepted.assign(n, 0); out.leafKey.assign(n, 0); out.blocker.assign(n, 0);
+    if (hpmvs_octree_insert_batch(dev, &t, (int)n, points.data(), addWidth.data(), out.accepted.data(), out.leafKey.data(),
+                                  out.blocker.data(), 0, nullptr) != HPMVS_OK) {
+        std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl;
+        return false;
+    }
+    return true;
+}
+bool Scene::octreeRoute(const std::vector<float>& roots, const std::vector<float>& points, std::vector<int32_t>& out) const {
+    hpmvs_scene* dev = deviceScene();
+    if (!dev) return false;
+    const size_t n = points.size() / 3, nt = roots.size() / 4;
+    if (points.size() != 3 * n || roots.size() != 4 * nt) { std::cerr << "hpmvs: octreeRoute: roots [t][4], points [n][3]" << std::endl; return false; }
+    out.assign(n, 0);
+    if (hpmvs_octree_route_batch(dev, (int)nt, roots.data(), (int)n, points.data(), out.data(), 0, nullptr) != HPMVS_OK) {
+        std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl;
+        return false;
+    }
+    return true;
+}
 bool Scene::levelSupport(const Patch3d* const* patches, size_t n, int minLevel, std::vector<int>& support) const {
     support.assign(n, 0);
     hpmvs_scene* dev = deviceScene();

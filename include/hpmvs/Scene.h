@@ -94,6 +94,19 @@ public:
     };
     bool octreeLocate(const OctreeIndex& tree, const std::vector<float>& points /*[n][3]*/, const std::vector<float>& addWidth /*[n] or empty*/,
                       OctreeLocation& out) const;
+    // A round's border patches (CellProcessor.cpp:487-540), each as ONE batched GPU call.  octreeRoute: for every point the index
+    // of the first root in list order (roots [t][4]: c_, width_) that contains it, -1 when none does (distributeBorderCell).
+    // octreeInsert: DynOctTree::addConditional(points[i], addWidth[i]) for i = 0 .. n - 1 IN THAT ORDER, every patch seeing the
+    // leaves of the earlier ones (processBorderCellQueue's loop; addWidth = scale_3dx_ * 2.0 there).  The tree is not changed:
+    // the caller enters the accepted keys.  Results as hpmvs_octree_insert_batch's (include/hpmvs_amd.h).
+    struct OctreeInsertion {
+        std::vector<uint8_t> accepted;     // [n] addConditional's return
+        std::vector<uint64_t> leafKey;     // [n] *outleaf: the leaf the patch went into, or the one that refused it
+        std::vector<int32_t> blocker;      // [n] the earlier patch behind a refusal; -1: accepted, or refused by the tree itself
+    };
+    bool octreeInsert(const OctreeIndex& tree, const std::vector<float>& points /*[n][3]*/, const std::vector<float>& addWidth /*[n]*/,
+                      OctreeInsertion& out) const;
+    bool octreeRoute(const std::vector<float>& roots /*[t][4]*/, const std::vector<float>& points /*[n][3]*/, std::vector<int32_t>& out) const;
     std::map<std::string, int> dict_;
     std::vector<Camera> cameras_;
     std::vector<Image> images_;

@@ -33,6 +33,9 @@
  *   hpmvs_filter_batch       <- CellProcessor::filter, src/hpmvs/CellProcessor.cpp:43-82.
  *   hpmvs_seed_tree_batch    <- the second half of Scene::initPatches, src/hpmvs/Scene.cpp:183-199
  *                               (getBoundingBox, swapRoot, the scale floor, patchTree_.add, setDepths).
+ *   hpmvs_octree_locate_batch <- the tree look-ups of CellProcessor::extend, src/hpmvs/CellProcessor.cpp:122-125, 147-154.
+ *   hpmvs_octree_route_batch, <- CellProcessor::distributeBorderCell and ::processBorderCellQueue,
+ *   hpmvs_octree_insert_batch    src/hpmvs/CellProcessor.cpp:487-540 (the root search and the addConditional loop).
  *   hpmvs_camera_from_nvm    <- Camera::init, src/hpmvs/Camera.cpp:34-81.
  */
 #ifndef HPMVS_AMD_H
@@ -379,6 +382,34 @@ int hpmvs_octree_locate_batch(const hpmvs_scene *s, const hpmvs_octree_index *t,
                               const float *add_width /*[n], nullable*/, uint8_t *inside /*[n]*/, uint64_t *leaf_key /*[n]*/,
                               int32_t *leaf_index /*[n]*/, float *leaf_width /*[n]*/, float *leaf_center /*[n][3]*/,
                               uint64_t *target_key /*[n]*/, int on_device, void *stream);
+
+/* A round's border patches (reference src/hpmvs/CellProcessor.cpp:487-540): candidates of CellProcessor::extend that passed every
+ * gate but left their subtree's root.  distributeBorderCell hands each to the first processor whose root contains it;
+ * processBorderCellQueue inserts them, in queue order, with addConditional(p, scale * 2.0).
+ *
+ * hpmvs_octree_insert_batch is that loop for one tree: addConditional(points[i], add_width[i]) for i = 0 .. n - 1 IN THAT ORDER,
+ * every patch seeing the leaves the earlier ones created (the widths differ per patch, so an earlier insertion can leave a later
+ * point a nonempty leaf, a leaf that has become too narrow, or a deeper leaf to start from).  The tree t is the caller's and is
+ * NOT modified: the caller enters the accepted keys (the branches on the way are their proper prefixes).
+ *   accepted[i]   1 when the patch was inserted
+ *   leaf_key[i]   *outleaf: the key of the leaf the patch went into, or of the leaf that refused it (the located leaf of t when t
+ *                 itself refuses -- nonempty, or narrower than add_width[i] --, else the leaf the earlier insertions left there)
+ *   blocker[i]    -1 for an accepted patch and for a refusal by t itself; else the queue index of the earlier patch behind the
+ *                 refusal: the owner of the nonempty leaf, or for a leaf that has become too narrow the accepted patch whose key
+ *                 shares the longest prefix with the point's path (the lowest index among equals).  Nullable.
+ * Splitting stops at HPMVS_MAX_TREE_DEPTH levels as for target_key above.  The comparisons are the reference's as written: a NaN
+ * add_width refuses nothing and splits nothing, the patch goes into the leaf it finds.  n = 0 and the empty tree are valid; the
+ * table is checked as for hpmvs_octree_locate_batch (HPMVS_ERR_ARG before any output is written).  Scratch of 44 n bytes plus the
+ * sort's is the call's own; the call is host-synchronous in both forms.
+ *
+ * hpmvs_octree_route_batch: tree[i] = the first t in list order whose root (roots[t]: c_ x y z, width_) contains points[i]
+ * (Cell::contains), -1 when none does (distributeBorderCell drops such a patch).  roots is a HOST array in both forms, like an
+ * hpmvs_octree_index; a root that is not finite or has no positive width is HPMVS_ERR_ARG.  n = 0 and n_trees = 0 are valid. */
+int hpmvs_octree_insert_batch(const hpmvs_scene *s, const hpmvs_octree_index *t, int n, const float *points /*[n][3]*/,
+                              const float *add_width /*[n]*/, uint8_t *accepted /*[n]*/, uint64_t *leaf_key /*[n]*/,
+                              int32_t *blocker /*[n], nullable*/, int on_device, void *stream);
+int hpmvs_octree_route_batch(const hpmvs_scene *s, int n_trees, const float *roots /*[n_trees][4]: c_, width_*/, int n,
+                             const float *points /*[n][3]*/, int32_t *tree /*[n]*/, int on_device, void *stream);
 
 /* Host-pointer calls and pinned memory.  An array of a host-pointer call (on_device = 0) that lies in pinned host memory
  * mapped into the GPU's address space -- hipHostMalloc / hipHostRegister, torch's pin_memory(), hpmvs_host_alloc below --
