@@ -455,6 +455,7 @@ __global__ void __launch_bounds__(256) tail_unpack_kernel(const DevTail* __restr
     const DevTail r = in[t];
     const long long i = (long long)patch_offset + r.patch;
     if (i < 0 || i >= b.n) return;
+    if ((int)r.count > kWideImages - kMaxImages) return;   // (malformed: more ids than a tail holds -- rejected whole)
     for (int k = 0; k < (int)r.count && kMaxImages + k < b.max_images; k++)
         b.images[(size_t)i * b.max_images + kMaxImages + k] = (int32_t)r.images[k];
 }

@@ -96,13 +96,15 @@ def pack_records(center, normal, color, scale, fmin, ok, n_images, images, check
 
 def pack_tails(ok, n_images, images) -> torch.Tensor:
     """[t, 392] uint8: the tails of the refined patches (ok != 0) whose list is longer than the record's 64 ids, in patch
-    order -- the bytes `hpmvs_pack_record_tails` writes."""
+    order -- the bytes `hpmvs_pack_record_tails` writes.  `ok` = None is the C ABI's absent `ok`: every long list gets a tail."""
     n, cols = images.shape
     dev = images.device
     if cols <= MAX_RECORD_IMAGES or n == 0:
         return torch.zeros((0, TAIL_BYTES), dtype=torch.uint8, device=dev)
     nim = n_images.to(dev).to(torch.int64)
-    has = (ok.to(dev) != 0) & (nim > MAX_RECORD_IMAGES) & (nim <= cols)
+    has = (nim > MAX_RECORD_IMAGES) & (nim <= min(cols, MAX_LIST_IMAGES))
+    if ok is not None:
+        has = has & (ok.to(dev) != 0)
     idx = torch.nonzero(has)[:, 0]
     t = int(idx.numel())
     out = torch.zeros((t, TAIL_BYTES), dtype=torch.uint8, device=dev)
@@ -168,7 +170,10 @@ def unpack_records(rec: torch.Tensor, tails: torch.Tensor = None) -> dict:
         tl = tails.cpu().contiguous()
         t = tl.shape[0]
         patch = tl[:, 0:4].contiguous().view(torch.int32).view(t).numpy()
-        cnt = tl[:, 4:6].contiguous().view(torch.int16).view(t).numpy().astype(np.int64)
+        cnt = tl[:, 4:6].contiguous().view(torch.int16).view(t).numpy().astype(np.uint16).astype(np.int64)
+        if int(cnt.max()) > TAIL_IDS:
+            bad = int(np.argmax(cnt > TAIL_IDS))
+            raise ValueError(f"malformed tail {bad}: count {int(cnt[bad])} but a tail holds {TAIL_IDS} ids")
         tid = tl[:, 8:8 + 2 * TAIL_IDS].contiguous().view(torch.int16).view(t, TAIL_IDS).numpy().astype(np.uint16)
         wide = np.full((n, MAX_RECORD_IMAGES + int(cnt.max())), -1, np.int32)
         wide[:, :MAX_RECORD_IMAGES] = images

@@ -471,7 +471,11 @@ typedef struct hpmvs_record {
  * record is unchanged (format version 1 = no tails anywhere = what rounds 1-5 sent).
  *   hpmvs_pack_record_tails    tails of the refined patches (ok != 0) with n_images > 64, in patch order; *n_tails (host int) is
  *                              their number (the call synchronises the stream); HPMVS_ERR_ARG when `cap` tails do not hold them
- *   hpmvs_unpack_record_tails  ids 64.. of patch (patch_offset + tail.patch) of a batch that hpmvs_unpack_records has filled */
+ *   hpmvs_unpack_record_tails  ids 64.. of patch (patch_offset + tail.patch) of a batch that hpmvs_unpack_records has filled.
+ *                              A tail whose patch falls outside the batch is dropped; an all-zero tail (the padding of a gathered
+ *                              segment: patch 0, count 0) writes nothing; a MALFORMED tail, count > HPMVS_MAX_IMAGES -
+ *                              HPMVS_RECORD_IMAGES, is rejected whole: none of its ids is written, the tails around it are applied
+ *                              (hpmvs_amd.distributed.unpack_records raises ValueError for such a tail) */
 typedef struct hpmvs_record_tail {
     int32_t patch;   /* index of the patch in the sender's shard */
     uint16_t count;  /* ids in this tail = n_images - 64 */
