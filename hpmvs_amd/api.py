@@ -76,6 +76,7 @@ EXPORTS = [
     "hpmvs_undistort", "hpmvs_undistort_map", "hpmvs_scene_set_view_distorted",
     "hpmvs_regularize_batch", "hpmvs_filter_batch", "hpmvs_seed_tree_batch", "hpmvs_octree_locate_batch",
     "hpmvs_octree_insert_batch", "hpmvs_octree_route_batch",
+    "hpmvs_scene_center", "hpmvs_init_patches_sphere_batch",
 ]
 
 _lib = None
@@ -111,6 +112,9 @@ def lib():
     L.hpmvs_optimize_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(PatchBatch), C.c_int, C.c_void_p]
     L.hpmvs_init_patches_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.POINTER(PatchBatch), C.c_int, C.c_void_p]
+    L.hpmvs_init_patches_sphere_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.POINTER(PatchBatch), C.c_int, C.c_void_p]
+    L.hpmvs_scene_center.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]
     L.hpmvs_objective_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(PatchBatch), C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.hpmvs_inccs_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(PatchBatch), C.c_int, C.c_int,
@@ -175,6 +179,18 @@ def camera_from_nvm(f, q, c, width, height, max_level=5) -> Camera:
     return cam
 
 
+def scene_center(cameras):
+    """Scene::getSceneCenter (reference Scene.cpp:210-239) for a sequence of Camera structs, e.g. Scene.cameras: the point
+    closest to every optical axis and the largest distance from it to a camera centre, as (center[3] float64, radius), or None
+    where the reference has no valid centre (fewer than 2 cameras, parallel axes).  Host code; needs no GPU."""
+    cams = (Camera * max(1, len(cameras)))(*cameras)
+    center, radius, valid = (C.c_double * 3)(), C.c_double(), C.c_int()
+    _chk(lib().hpmvs_scene_center(cams, len(cameras), center, C.byref(radius), C.byref(valid)))
+    if not valid.value:
+        return None
+    return np.array(center[:], dtype=np.float64), radius.value
+
+
 def _ptr(a):
     """numpy array / torch tensor / int -> raw address (or None)."""
     if a is None:
@@ -222,10 +238,12 @@ class Scene:
         self.device = device
         self.n_views = synth_scene.n_views
         self.view_levels = []   # pyramid levels per view (Camera::getLevels)
+        self.cameras = []       # the hpmvs_camera structs of the views (scene_center(scene.cameras))
         _chk(L.hpmvs_scene_create(self.n_views, device, C.byref(self.h)))
         for i, v in enumerate(synth_scene.views):
             cam = camera_from_nvm(v.f, v.q, v.c, v.width, v.height, synth_scene.max_level)
             self.view_levels.append(int(cam.n_levels))
+            self.cameras.append(cam)
             rgb = v.rgb
             if isinstance(rgb, np.ndarray):
                 rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
@@ -352,11 +370,13 @@ def optimize_batch(scene: Scene, batch: Batch, options: Options | None = None) -
 
 
 def init_patches_batch(scene: Scene, xyz, meas_off, meas_img, start_level=4, max_images=FAST_IMAGES,
-                       options: Options | None = None) -> Batch:
+                       options: Options | None = None, sphere=None) -> Batch:
     """Scene::initPatches seed loop on the GPU (reference Scene.cpp:112-178): seeds built on device, refined,
     drift-gated.  Returns the batch (seed patches, refined where ok).  max_images: the rows of the batch's image lists; a point
     with more measurements than that ends at stage 100 (the C ABI's maximum, 64, by default: in a 50-view scene most NVM points
-    have more than 32)."""
+    have more than 32).  sphere = (cx, cy, cz, r): the scene-centre gate of --only_sphere (Scene.cpp:118-121), e.g.
+    (*center, radius) of scene_center(scene.cameras); a point farther than r from the centre ends at stage 13 before any other
+    test.  None: no gate."""
     o = options or default_options()
     xyz = np.ascontiguousarray(xyz, dtype=np.float64)
     off = np.ascontiguousarray(meas_off, dtype=np.int32)
@@ -365,8 +385,13 @@ def init_patches_batch(scene: Scene, xyz, meas_off, meas_img, start_level=4, max
     batch = Batch(np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32), np.zeros(n, np.float32),
                   np.zeros(n, np.int32), np.full((n, max_images), -1, np.int32))
     b = batch.c_struct()
-    _chk(lib().hpmvs_init_patches_batch(scene.h, C.byref(o), start_level, n, xyz.ctypes.data, off.ctypes.data,
-                                        img.ctypes.data if len(img) else None, C.byref(b), 0, None))
+    if sphere is None:
+        _chk(lib().hpmvs_init_patches_batch(scene.h, C.byref(o), start_level, n, xyz.ctypes.data, off.ctypes.data,
+                                            img.ctypes.data if len(img) else None, C.byref(b), 0, None))
+        return batch
+    sph = np.ascontiguousarray(sphere, dtype=np.float64).reshape(4)
+    _chk(lib().hpmvs_init_patches_sphere_batch(scene.h, C.byref(o), start_level, n, xyz.ctypes.data, off.ctypes.data,
+                                               img.ctypes.data if len(img) else None, sph.ctypes.data, C.byref(b), 0, None))
     return batch
 
 

@@ -234,6 +234,94 @@ int hpmvs_camera_from_nvm(double f, const double q[4], const double c[3], int wi
     return HPMVS_OK;
 }
 
+// Scene::getSceneCenter, reference src/hpmvs/Scene.cpp:210-239 over TriangulateMidpoint (include/hpmvs/Triangulation.hpp:28-53):
+// the point closest to every camera's optical axis and the largest distance from it to a camera centre.  Float64, host only.
+// The 4x4 system is accumulated with the reference's expressions in camera order; it is solved by Householder QR with
+// column pivoting like the reference's Eigen::ColPivHouseholderQR, but not by Eigen's code: equal to solver accuracy.
+int hpmvs_scene_center(const hpmvs_camera* cams, int n, double center[3], double* radius, int* valid) {
+    if (!center || !radius || !valid || n < 0 || (n > 0 && !cams)) return fail(HPMVS_ERR_ARG, "scene_center: bad argument");
+    *valid = 0;
+    center[0] = center[1] = center[2] = 0.0;
+    *radius = 0.0;
+    if (n < 2) return HPMVS_OK;  // n == 0: the reference returns false (Scene.cpp:218); n == 1: its CHECK_GE(origins.size(), 2) aborts
+    double A[4][4] = {{0}}, b[4] = {0};
+    std::vector<double> org((size_t)3 * n);
+    for (int i = 0; i < n; i++) {
+        // cam.oAxis_.head<3>().cast<double>().normalized(), cam.center_.cast<double>().hnormalized() (Scene.cpp:215-216)
+        const double z[3] = {(double)cams[i].zaxis[0], (double)cams[i].zaxis[1], (double)cams[i].zaxis[2]};
+        const double nz = std::sqrt((z[0] * z[0] + z[1] * z[1]) + z[2] * z[2]);
+        const double d[4] = {z[0] / nz, z[1] / nz, z[2] / nz, 0.0};
+        const double w = (double)cams[i].center[3];
+        double* o = &org[(size_t)3 * i];
+        for (int k = 0; k < 3; k++) o[k] = (double)cams[i].center[k] / w;
+        const double oh[4] = {o[0], o[1], o[2], 1.0};
+        for (int r = 0; r < 4; r++) {
+            double t[4];
+            for (int c = 0; c < 4; c++) t[c] = (r == c ? 1.0 : 0.0) - d[r] * d[c];  // A_term = I - d_h d_h^T
+            for (int c = 0; c < 4; c++) A[r][c] += t[c];
+            b[r] += ((t[0] * oh[0] + t[1] * oh[1]) + t[2] * oh[2]) + t[3] * oh[3];
+        }
+    }
+    // Householder QR with column pivoting: A P = Q R, applied to b as it goes
+    int perm[4] = {0, 1, 2, 3};
+    double rdiag0 = 0.0;
+    for (int k = 0; k < 4; k++) {
+        int piv = k;
+        double best = -1.0;
+        for (int c = k; c < 4; c++) {
+            double s2 = 0.0;
+            for (int r = k; r < 4; r++) s2 += A[r][c] * A[r][c];
+            if (s2 > best) { best = s2; piv = c; }  // (NaN never wins: the solution is checked below)
+        }
+        if (piv != k) {
+            for (int r = 0; r < 4; r++) std::swap(A[r][k], A[r][piv]);
+            std::swap(perm[k], perm[piv]);
+        }
+        const double nrm = std::sqrt(best);
+        if (k == 0) rdiag0 = nrm;
+        // Numerically rank deficient: |R_kk| <= 64 * 2^-52 * |R_00|.  The fourth column of A is (0, 0, 0, n) and no column is
+        // longer, so this is the 3x3 block sum(I - d d^T) having an eigenvalue below ~1.4e-14 n: axes parallel to ~1e-7 rad.
+        if (!(nrm > 64.0 * 2.220446049250313e-16 * rdiag0)) return HPMVS_OK;
+        const double alpha = A[k][k] > 0.0 ? -nrm : nrm;
+        double v[4] = {0, 0, 0, 0};
+        v[k] = A[k][k] - alpha;
+        for (int r = k + 1; r < 4; r++) v[r] = A[r][k];
+        double vv = 0.0;
+        for (int r = k; r < 4; r++) vv += v[r] * v[r];
+        if (vv > 0.0) {
+            for (int c = k; c < 4; c++) {
+                double dot = 0.0;
+                for (int r = k; r < 4; r++) dot += v[r] * A[r][c];
+                const double f = 2.0 * dot / vv;
+                for (int r = k; r < 4; r++) A[r][c] -= f * v[r];
+            }
+            double dot = 0.0;
+            for (int r = k; r < 4; r++) dot += v[r] * b[r];
+            const double f = 2.0 * dot / vv;
+            for (int r = k; r < 4; r++) b[r] -= f * v[r];
+        }
+    }
+    double y[4], x[4];
+    for (int k = 3; k >= 0; k--) {
+        double t = b[k];
+        for (int c = k + 1; c < 4; c++) t -= A[k][c] * y[c];
+        y[k] = t / A[k][k];
+    }
+    for (int k = 0; k < 4; k++) x[perm[k]] = y[k];
+    const double ctr[3] = {x[0] / x[3], x[1] / x[3], x[2] / x[3]};  // center_homog.hnormalized() (Scene.cpp:225)
+    double rmax = 0.0;  // radius = dists[dists.size() - 1] of the sorted distances: the maximum (Scene.cpp:233)
+    for (int i = 0; i < n; i++) {
+        const double e[3] = {ctr[0] - org[3 * i], ctr[1] - org[3 * i + 1], ctr[2] - org[3 * i + 2]};
+        const double dist = std::sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+        if (!(dist <= rmax)) rmax = dist;  // (a NaN distance surfaces here and fails the check below)
+    }
+    if (!std::isfinite(ctr[0]) || !std::isfinite(ctr[1]) || !std::isfinite(ctr[2]) || !std::isfinite(rmax)) return HPMVS_OK;
+    center[0] = ctr[0]; center[1] = ctr[1]; center[2] = ctr[2];
+    *radius = rmax;
+    *valid = 1;
+    return HPMVS_OK;
+}
+
 int hpmvs_scene_create(int n_views, int device, hpmvs_scene** out) {
     if (!out || n_views <= 0 || n_views > 65535) return fail(HPMVS_ERR_ARG, "scene_create: bad n_views/out");
     int ndev = 0;
@@ -1324,8 +1412,21 @@ int hpmvs_optimize_batch(const hpmvs_scene* s, const hpmvs_options* o, hpmvs_pat
 int hpmvs_init_patches_batch(const hpmvs_scene* s, const hpmvs_options* o, int start_level, int n_points,
                              const double* xyz, const int32_t* meas_off, const int32_t* meas_img, hpmvs_patch_batch* b,
                              int on_device, void* stream) {
+    return hpmvs_init_patches_sphere_batch(s, o, start_level, n_points, xyz, meas_off, meas_img, nullptr, b, on_device, stream);
+}
+
+int hpmvs_init_patches_sphere_batch(const hpmvs_scene* s, const hpmvs_options* o, int start_level, int n_points,
+                                    const double* xyz, const int32_t* meas_off, const int32_t* meas_img,
+                                    const double* sphere, hpmvs_patch_batch* b, int on_device, void* stream) {
     int rc = check_batch_shape(s, o, b);
     if (rc) return rc;
+    SeedSphere sph = {{0.0, 0.0, 0.0}, 0.0, 0};
+    if (sphere) {
+        // a centre that is not finite, a NaN or a negative radius: no sphere at all (r = +inf is one, and gates nothing)
+        if (!std::isfinite(sphere[0]) || !std::isfinite(sphere[1]) || !std::isfinite(sphere[2]) || !(sphere[3] >= 0.0))
+            return fail(HPMVS_ERR_ARG, "init_patches_batch: sphere needs a finite centre and a radius >= 0");
+        sph.c[0] = sphere[0]; sph.c[1] = sphere[1]; sph.c[2] = sphere[2]; sph.r = sphere[3]; sph.on = 1;
+    }
     if (b->n != n_points) return fail(HPMVS_ERR_ARG, "init_patches_batch: b->n must equal n_points");
     if (n_points > 0 && (!xyz || !meas_off || !b->center || !b->normal || !b->scale || !b->n_images ||
                          !b->images || !b->ok))
@@ -1349,7 +1450,7 @@ int hpmvs_init_patches_batch(const hpmvs_scene* s, const hpmvs_options* o, int s
     const DevOptions d = make_dev_options(o);
     {
         std::lock_guard<std::recursive_mutex> lk(s->mu);
-        launch_seed_init(dev_scene(s), d, start_level, n_points, dxyz, doff, dimg, D, st);
+        launch_seed_init(dev_scene(s), d, start_level, n_points, dxyz, doff, dimg, sph, D, st);
         HIPCHK(hipGetLastError());
         if ((rc = enqueue_refinement(s, d, D, st))) return rc;
         launch_drift_gate(n_points, dxyz, D, st);

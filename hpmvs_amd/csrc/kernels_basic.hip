@@ -173,17 +173,28 @@ void launch_inccs(const DevScene& sc, const DevOptions& o, const DevBatch& b, in
 // Seed construction of Scene::initPatches (reference src/hpmvs/Scene.cpp:118-163), one thread per
 // NVM point.  Seeds that the reference skips before optimize() get n_images = -reason; the
 // refinement kernel drops them immediately with stage = reason.
+// The scene-centre sphere (Scene.cpp:118-121, FILTER_SCENE_CENTER) is tested first, in float64 on the float64 point:
+// (pt.xyz - sceneCenter).norm() > sceneRadius, the norm summed left to right.  Written as `dist > r`: a point on the
+// sphere and a NaN coordinate are kept, an infinite one is gated unless r is infinite too.
 __global__ void __launch_bounds__(256) seed_init_kernel(DevScene sc, DevOptions o, int start_level, int n,
                                                         const double* __restrict__ xyz,
                                                         const int32_t* __restrict__ meas_off,
-                                                        const int32_t* __restrict__ meas_img, DevBatch b) {
+                                                        const int32_t* __restrict__ meas_img, SeedSphere sphere,
+                                                        DevBatch b) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float c[3] = {(float)xyz[3 * i], (float)xyz[3 * i + 1], (float)xyz[3 * i + 2]};
     int32_t* row = b.images + (size_t)i * b.max_images;
     int nimg = 0, why = 0;
     const int m0 = meas_off[i], m1 = meas_off[i + 1];
-    if (m1 - m0 < o.MIN_IMAGES_PER_PATCH) why = 10;
+    bool gated = false;
+    if (sphere.on) {
+        const double dx = xyz[3 * i] - sphere.c[0], dy = xyz[3 * i + 1] - sphere.c[1], dz = xyz[3 * i + 2] - sphere.c[2];
+        const double dist = sqrt((dx * dx + dy * dy) + dz * dz);
+        gated = dist > sphere.r;
+    }
+    if (gated) why = 13;
+    else if (m1 - m0 < o.MIN_IMAGES_PER_PATCH) why = 10;
     else {
         const float s = __int_as_float((127 - start_level) << 23);
         const int margin = 2;  // cSize, Scene.cpp:91,143
@@ -224,10 +235,11 @@ __global__ void __launch_bounds__(256) seed_init_kernel(DevScene sc, DevOptions 
 }
 
 void launch_seed_init(const DevScene& sc, const DevOptions& o, int start_level, int n, const double* xyz,
-                      const int32_t* meas_off, const int32_t* meas_img, const DevBatch& b, hipStream_t st) {
+                      const int32_t* meas_off, const int32_t* meas_img, const SeedSphere& sphere, const DevBatch& b,
+                      hipStream_t st) {
     if (n <= 0) return;
     hipLaunchKernelGGL(seed_init_kernel, dim3((n + 255) / 256), dim3(256), 0, st, sc, o, start_level, n, xyz, meas_off,
-                       meas_img, b);
+                       meas_img, sphere, b);
 }
 
 // |centre - xyz| > 2 * scale -> drop (Scene.cpp:171)

@@ -46,8 +46,16 @@ void launch_objective_lane(const DevScene& sc, const DevOptions& o, const DevBat
                            int32_t* ngrabs_out, hipStream_t st);
 void launch_inccs(const DevScene& sc, const DevOptions& o, const DevBatch& b, int ref_idx, int robust, float* out,
                   hipStream_t st);
+// The scene-centre sphere of Scene::initPatches (reference src/hpmvs/Scene.cpp:118-121), passed to seed_init_kernel by value.
+// on == 0: no gate.  Kept out of dev_types.h like RegTree above.
+struct SeedSphere {
+    double c[3];
+    double r;
+    int32_t on;
+};
 void launch_seed_init(const DevScene& sc, const DevOptions& o, int start_level, int n, const double* xyz,
-                      const int32_t* meas_off, const int32_t* meas_img, const DevBatch& b, hipStream_t st);
+                      const int32_t* meas_off, const int32_t* meas_img, const SeedSphere& sphere, const DevBatch& b,
+                      hipStream_t st);
 void launch_drift_gate(int n, const double* xyz, const DevBatch& b, hipStream_t st);
 // CellProcessor::extend / ::branch candidates (mode 0 / 1): parents -> out (n * N patches), and the gates after optimize
 int expand_fanout(int mode);

@@ -457,10 +457,49 @@ static int list_stride(size_t n_views, size_t n_patches, size_t longest_input) {
     return (int)m;
 }
 
+// Scene::getSceneCenter (src/hpmvs/Scene.cpp:210-239) over hpmvs_scene_center, which reads zAxis_ and center_ alone
+bool Scene::getSceneCenter(Eigen::Vector3d& center, double& radius) const {
+    std::vector<hpmvs_camera> cams(cameras_.size());
+    if (!cams.empty()) memset(cams.data(), 0, sizeof(hpmvs_camera) * cams.size());
+    for (size_t i = 0; i < cameras_.size(); i++) {
+        for (int k = 0; k < 4; k++) cams[i].center[k] = cameras_[i].center_[k];
+        for (int k = 0; k < 3; k++) cams[i].zaxis[k] = cameras_[i].zAxis_[k];
+    }
+    double c[3], r = 0.0;
+    int valid = 0;
+    if (hpmvs_scene_center(cams.data(), (int)cams.size(), c, &r, &valid) != HPMVS_OK) {
+        std::cerr << "getSceneCenter: " << hpmvs_last_error() << std::endl;
+        return false;
+    }
+    if (!valid) return false;
+    center = Eigen::Vector3d(c[0], c[1], c[2]);
+    radius = r;
+    return true;
+}
+
 bool Scene::initPatches(const NVM_Model& model, const HpmvsOptions& options, std::vector<Ppatch3d>& out) const {
+    // Scene.cpp:105-109: the sphere only with FILTER_SCENE_CENTER, and only when getSceneCenter has a valid one
+    Eigen::Vector3d sceneCenter;
+    double sceneRadius = 0.0;
+    if (options.FILTER_SCENE_CENTER && getSceneCenter(sceneCenter, sceneRadius)) {
+        const double sphere[4] = {sceneCenter[0], sceneCenter[1], sceneCenter[2], sceneRadius};
+        return initPatchesGated(model, options, out, sphere, nullptr);
+    }
+    return initPatchesGated(model, options, out, nullptr, nullptr);
+}
+
+bool Scene::initPatches(const NVM_Model& model, const HpmvsOptions& options, std::vector<Ppatch3d>& out,
+                        const Eigen::Vector3d& center, double radius, std::vector<int>* stage) const {
+    const double sphere[4] = {center[0], center[1], center[2], radius};
+    return initPatchesGated(model, options, out, sphere, stage);
+}
+
+bool Scene::initPatchesGated(const NVM_Model& model, const HpmvsOptions& options, std::vector<Ppatch3d>& out,
+                             const double* sphere, std::vector<int>* stage) const {
     hpmvs_scene* dev = deviceScene();
     if (!dev) return false;
     const size_t n = model.points.size();
+    if (stage) stage->clear();
     if (n == 0) return true;
     const PinnedAlloc<char> pin(true);  // (this entry stages whatever the batch size: pinned arrays are used in place)
     PVec<double> xyz(3 * n, pin);
@@ -491,11 +530,14 @@ bool Scene::initPatches(const NVM_Model& model, const HpmvsOptions& options, std
     b.n = (int32_t)n; b.max_images = stride;
     b.center = center.data(); b.normal = normal.data(); b.scale = scale.data(); b.n_images = nimg.data();
     b.images = images.data(); b.ok = ok.data(); b.color = color.data(); b.ncc = ncc.data();
-    if (hpmvs_init_patches_batch(dev, &o, options.START_LEVEL, (int)n, xyz.data(), off.data(),
-                                 img.empty() ? nullptr : img.data(), &b, 0, nullptr) != HPMVS_OK) {
+    PVec<int32_t> stages(pin);
+    if (stage) { stages.assign(n, 0); b.stage = stages.data(); }
+    if (hpmvs_init_patches_sphere_batch(dev, &o, options.START_LEVEL, (int)n, xyz.data(), off.data(),
+                                        img.empty() ? nullptr : img.data(), sphere, &b, 0, nullptr) != HPMVS_OK) {
         std::cerr << "initPatches: " << hpmvs_last_error() << std::endl;
         return false;
     }
+    if (stage) stage->assign(stages.begin(), stages.end());
     for (size_t i = 0; i < n; i++) {
         if (!ok[i]) continue;
         Ppatch3d p(new Patch3d);

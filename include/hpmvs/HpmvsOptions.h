@@ -15,8 +15,8 @@ public:
     float NCC_ALPHA_1, NCC_ALPHA_2;                      // filterImagesNCC thresholds before / after BOBYQA
     // ---- read by the seed loop (Scene::initPatches)
     int START_LEVEL;
+    bool FILTER_SCENE_CENTER;                            // --only_sphere: skip NVM points outside Scene::getSceneCenter's sphere
     // ---- read only by the scheduler side of the reference (octree, depth tests, threading, output)
-    bool FILTER_SCENE_CENTER;
     int PATCH_INIT_MAXLEVEL, MAX_TREE_LEVEL, PATCH_FINAL_MINLEVEL;
     int NR_OPTIMIZATION_THREADS;
     float DEPTH_TEST_FACTOR;

@@ -39,7 +39,19 @@ public:
     // The seed loop of Scene::initPatches (src/hpmvs/Scene.cpp:112-178) as ONE batched GPU call: seed
     // construction, optimize(), drift gate.  Survivors are appended to `out` in point order; inserting
     // them into the octree / depth maps (Scene.cpp:183-199) is seedTree below.
+    // With options.FILTER_SCENE_CENTER (--only_sphere) the points outside getSceneCenter's sphere are skipped first, on the
+    // device, as Scene.cpp:105-121 does; without a valid centre nothing is gated.
     bool initPatches(const NVM_Model& model, const HpmvsOptions& options, std::vector<Ppatch3d>& out) const;
+    // The same loop behind a sphere of the caller's own (a region of interest): points with |xyz - center| > radius are
+    // skipped first, whatever FILTER_SCENE_CENTER says.  stage: the per-point stage codes of hpmvs_init_patches_sphere_batch
+    // (include/hpmvs_amd.h; 13 = outside the sphere), one per model point.
+    bool initPatches(const NVM_Model& model, const HpmvsOptions& options, std::vector<Ppatch3d>& out,
+                     const Eigen::Vector3d& center, double radius, std::vector<int>* stage = nullptr) const;
+    // Scene::getSceneCenter (src/hpmvs/Scene.cpp:210-239) over hpmvs_scene_center: the point closest to every camera's optical
+    // axis and the largest distance from it to a camera centre.  False without a valid centre (no camera; also one camera or
+    // parallel axes, where the reference aborts or returns its QR's leftovers).  Host code, float64; equal to the reference's
+    // to solver accuracy, not bit for bit (include/hpmvs_amd.h).
+    bool getSceneCenter(Eigen::Vector3d& center, double& radius) const;
     // The second half of Scene::initPatches (src/hpmvs/Scene.cpp:183-199) as ONE batched GPU call (hpmvs_seed_tree_batch):
     // getBoundingBox, the root Branch, scale_3dx_ = max(scale_3dx_, width / (1 << PATCH_INIT_MAXLEVEL + 1)) written to every
     // patch, the octree the sequential patchTree_.add loop builds -- as the leaf tables the level calls read, not as pointers --
@@ -120,6 +132,9 @@ public:
     // device launches; opaque, owned by the scene
     void* combiner() const;
 private:
+    // the one implementation under both initPatches: sphere = cx cy cz r, or null for no gate
+    bool initPatchesGated(const NVM_Model& model, const HpmvsOptions& options, std::vector<Ppatch3d>& out, const double* sphere,
+                          std::vector<int>* stage) const;
     mutable hpmvs_scene* dev_;
     mutable void* combiner_ = nullptr;
     mutable std::mutex mu_;

@@ -27,6 +27,10 @@
  *   hpmvs_undistort,         <- Image::undistort, src/hpmvs/Image.cpp:68-146 (run by Image::load for
  *   hpmvs_scene_set_view_distorted  k1 != 0, :50-53), before the pyramid.
  *   hpmvs_init_patches_batch <- the seed loop of Scene::initPatches, src/hpmvs/Scene.cpp:112-178.
+ *   hpmvs_init_patches_sphere_batch <- the same loop with the scene-centre gate of --only_sphere
+ *                               (options.FILTER_SCENE_CENTER), src/hpmvs/Scene.cpp:105-121.
+ *   hpmvs_scene_center       <- Scene::getSceneCenter, src/hpmvs/Scene.cpp:210-239 (TriangulateMidpoint,
+ *                               include/hpmvs/Triangulation.hpp:28-53).
  *   hpmvs_expand_batch       <- the candidate loops of CellProcessor::extend / ::branch,
  *                               src/hpmvs/CellProcessor.cpp:84-142 and :210-262.
  *   hpmvs_regularize_batch   <- CellProcessor::regularize, src/hpmvs/CellProcessor.cpp:309-367.
@@ -127,6 +131,24 @@ void hpmvs_default_options(hpmvs_options *o);
 int hpmvs_camera_from_nvm(double f, const double q_wxyz[4], const double c[3], int width, int height,
                           int max_level, hpmvs_camera *out);
 
+/* Host-side Scene::getSceneCenter (reference src/hpmvs/Scene.cpp:210-239): the sphere --only_sphere
+ * (options.FILTER_SCENE_CENTER) keeps NVM points in.  Pure host code in float64, usable without a GPU.
+ *   d_i = (double)zaxis normalised, o_i = (double)center[0..2] / (double)center[3];
+ *   A = sum_i (I - d_h d_h^T), b = sum_i (I - d_h d_h^T) (o_i, 1) as 4x4 / 4, in camera order (TriangulateMidpoint,
+ *   include/hpmvs/Triangulation.hpp:35-45); A x = b; center = x[0..2] / x[3]; radius = max_i |center - o_i| (the reference's
+ *   live line takes the maximum, Scene.cpp:233, not the median).
+ * The system is solved by Householder QR with column pivoting, the method of the reference's Eigen::ColPivHouseholderQR but
+ * not Eigen's code: the centre equals the reference's to solver accuracy -- about 64 * 2^-52 * |A^-1| (|A| |x| + |b|),
+ * 4e-13 for three cameras 30 from the origin -- not bit for bit.  An NVM point within that distance of the sphere's surface
+ * can therefore fall on the other side than in a particular Eigen build.
+ * *valid = 1 and HPMVS_OK when center[3] and *radius are set.  *valid = 0, still HPMVS_OK, with zeros in both, for
+ *   n == 0 (the reference returns false),
+ *   n == 1 (a departure: the reference aborts there, CHECK_GE(origins.size(), 2)),
+ *   a numerically rank-deficient system: a diagonal entry of R with |R_kk| <= 64 * 2^-52 * |R_00|, which is all optical
+ *   axes parallel to about 1e-7 rad (the reference returns whatever its QR yields), or a result that is not finite.
+ * HPMVS_ERR_ARG for NULL pointers or n < 0. */
+int hpmvs_scene_center(const hpmvs_camera *cams, int n, double center[3], double *radius, int *valid);
+
 /* ---- scene (HBM-resident, immutable after commit; shared read-only by all callers) ------- */
 int hpmvs_scene_create(int n_views, int device, hpmvs_scene **out);
 /* Level-0 interleaved u8 RGB (row-major, 3*(y*W+x)+c: reference Image.h:93-105).  The pyramid is
@@ -180,6 +202,20 @@ int hpmvs_optimize_batch(const hpmvs_scene *s, const hpmvs_options *o, hpmvs_pat
 int hpmvs_init_patches_batch(const hpmvs_scene *s, const hpmvs_options *o, int start_level, int n_points,
                              const double *xyz, const int32_t *meas_off, const int32_t *meas_img,
                              hpmvs_patch_batch *b, int on_device, void *stream);
+/* The same loop behind the scene-centre gate of --only_sphere (reference src/hpmvs/Scene.cpp:118-121): a point with
+ * |xyz - (cx, cy, cz)| > r is skipped before every other test,
+ *   stage 13 = outside the scene sphere; it wins over 10, 11 and 100, which the reference tests afterwards.
+ * The distance is float64 on the float64 xyz, sqrt((dx*dx + dy*dy) + dz*dz) without contraction, and the comparison is
+ * `dist > r`: a point on the sphere is kept, a NaN coordinate is not gated (it goes on as in hpmvs_init_patches_batch), an
+ * infinite one is gated.  Given (centre, radius) the gate is exact; hpmvs_scene_center's values equal the reference's to solver
+ * accuracy only (see there).  A gated row comes back like every row rejected before optimize(): ok 0, n_images 0, centre
+ * (float)xyz with w = 1, normal 0, scale 0; it costs what a stage-10 row costs.
+ * sphere[4] = cx cy cz r is ALWAYS a host pointer, whatever on_device says.  NULL: no gate, which is
+ * hpmvs_init_patches_batch itself (one implementation).  r = +inf gates nothing.  HPMVS_ERR_ARG for a centre that is not
+ * finite and for a NaN or negative radius. */
+int hpmvs_init_patches_sphere_batch(const hpmvs_scene *s, const hpmvs_options *o, int start_level, int n_points,
+                                    const double *xyz, const int32_t *meas_off, const int32_t *meas_img,
+                                    const double sphere[4], hpmvs_patch_batch *b, int on_device, void *stream);
 
 /* Frontier expansion: the candidate loops of CellProcessor::extend (reference
  * src/hpmvs/CellProcessor.cpp:84-178) and CellProcessor::branch (:210-262) for a whole frontier of
