@@ -77,6 +77,7 @@ EXPORTS = [
     "hpmvs_regularize_batch", "hpmvs_filter_batch", "hpmvs_seed_tree_batch", "hpmvs_octree_locate_batch",
     "hpmvs_octree_insert_batch", "hpmvs_octree_route_batch",
     "hpmvs_scene_center", "hpmvs_init_patches_sphere_batch",
+    "hpmvs_jpeg_info", "hpmvs_jpeg_decode", "hpmvs_scene_set_view_jpeg", "hpmvs_jpeg_decode_timed",
 ]
 
 _lib = None
@@ -109,6 +110,10 @@ def lib():
     L.hpmvs_undistort_map.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]
     L.hpmvs_scene_set_view_distorted.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                  C.POINTER(Camera), C.c_float, C.c_float]
+    L.hpmvs_jpeg_info.argtypes = [C.c_char_p, C.c_size_t] + [C.POINTER(C.c_int)] * 5
+    L.hpmvs_jpeg_decode.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int]
+    L.hpmvs_jpeg_decode_timed.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_float)]
+    L.hpmvs_scene_set_view_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(Camera), C.c_float, C.c_float]
     L.hpmvs_optimize_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(PatchBatch), C.c_int, C.c_void_p]
     L.hpmvs_init_patches_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.POINTER(PatchBatch), C.c_int, C.c_void_p]
@@ -228,6 +233,29 @@ def undistort_map(w: int, h: int, f: float, k1: float, device: int = 0) -> np.nd
     return xy
 
 
+def jpeg_info(data):
+    """(width, height, components, h_samp, v_samp) of a JPEG file held in a bytes-like object.  Host code; needs no GPU.  Raises
+    for a file hpmvs_jpeg_decode would refuse (HPMVS_ERR_UNSUPPORTED = -5, or -2 for a malformed or truncated one)."""
+    data = bytes(data)
+    v = [C.c_int() for _ in range(5)]
+    _chk(lib().hpmvs_jpeg_info(data, len(data), *[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def jpeg_decode(data, device: int = 0, on_device: bool = False):
+    """Baseline JPEG file (bytes-like) -> uint8 [H, W, 3] with libjpeg's default pixels: entropy decoding on the host, everything
+    behind it on the GPU.  A numpy array, or with on_device a torch tensor on the device (the pixels never visit the host)."""
+    data = bytes(data)
+    w, h = jpeg_info(data)[:2]
+    if on_device:
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=f"cuda:{device}")
+        _chk(lib().hpmvs_jpeg_decode(device, data, len(data), out.data_ptr(), out.numel(), 1))
+        return out
+    out = np.empty((h, w, 3), dtype=np.uint8)
+    _chk(lib().hpmvs_jpeg_decode(device, data, len(data), out.ctypes.data, out.nbytes, 0))
+    return out
+
+
 class Scene:
     """HBM-resident scene: Scene::addCameras + extractCoVisiblilty state the path reads
     (reference include/hpmvs/Scene.h:69-71)."""
@@ -241,10 +269,19 @@ class Scene:
         self.cameras = []       # the hpmvs_camera structs of the views (scene_center(scene.cameras))
         _chk(L.hpmvs_scene_create(self.n_views, device, C.byref(self.h)))
         for i, v in enumerate(synth_scene.views):
+            rgb = v.rgb
+            if isinstance(rgb, (bytes, bytearray)):  # a JPEG file as VisualSFM names it: decoded (and undistorted) in HBM
+                data = bytes(rgb)
+                w, h = jpeg_info(data)[:2]
+                cam = camera_from_nvm(v.f, v.q, v.c, w, h, synth_scene.max_level)
+                self.view_levels.append(int(cam.n_levels))
+                self.cameras.append(cam)
+                _chk(L.hpmvs_scene_set_view_jpeg(self.h, i, data, len(data), C.byref(cam), float(v.f),
+                                                 float(getattr(v, "k1", 0.0))))
+                continue
             cam = camera_from_nvm(v.f, v.q, v.c, v.width, v.height, synth_scene.max_level)
             self.view_levels.append(int(cam.n_levels))
             self.cameras.append(cam)
-            rgb = v.rgb
             if isinstance(rgb, np.ndarray):
                 rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
                 ptr, on_device = rgb.ctypes.data, 0

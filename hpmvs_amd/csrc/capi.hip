@@ -350,10 +350,56 @@ int hpmvs_scene_create(int n_views, int device, hpmvs_scene** out) {
 // Image::undistort's parameters (reference Image.h:80: float f_, k1_): k1 finite, f finite and positive
 static bool undistort_args_ok(float f, float k1) { return std::isfinite(k1) && std::isfinite(f) && f > 0.0f; }
 
+// ---- baseline JPEG (jpeg.hpp: the host parses and entropy-decodes, kernel_jpeg.hip does the rest)
+static int jpeg_fail(int code, const std::string& msg) { return fail(code == jpg::kErrUnsupported ? HPMVS_ERR_UNSUPPORTED : HPMVS_ERR_ARG, msg); }
+
+// Coefficients of a decoded frame -> interleaved RGB at the device address d_rgb (3 W H bytes), on the null stream of the
+// current device; returns after the kernels have run.  The two working buffers (quantiser tables + coefficients, 2 bytes
+// per sample; sample planes, 1 byte per sample) live for this call only: nothing is held between calls, so concurrent
+// calls share nothing and a many-view upload accumulates nothing.
+// ms (diagnostics, nullable): [1] coefficient upload, [2] IDCT kernel, [3] RGB kernel, from HIP events.
+static int jpeg_frame_to_device(const jpg::Frame& fr, uint8_t* d_rgb, float* ms = nullptr) {
+    jpg::Planes P;
+    const size_t plane_bytes = jpg::make_planes(fr, &P);
+    const size_t q_bytes = sizeof(uint16_t) * 3 * 64, coef_bytes = fr.coef.size() * sizeof(int16_t);
+    uint16_t q[3 * 64] = {};
+    for (int c = 0; c < fr.ncomp; c++) memcpy(q + 64 * c, fr.q[c], sizeof(uint16_t) * 64);
+    uint8_t *d_coef = nullptr, *d_planes = nullptr;
+    struct Free { uint8_t*& a; uint8_t*& b; ~Free() { if (a) hipFree(a); if (b) hipFree(b); } } free_on_exit{d_coef, d_planes};
+    HIPCHK(hipMalloc((void**)&d_coef, q_bytes + coef_bytes));
+    HIPCHK(hipMalloc((void**)&d_planes, plane_bytes));
+    hipEvent_t ev[4] = {};
+    struct Events { hipEvent_t* e; ~Events() { for (int k = 0; k < 4; k++) if (e[k]) hipEventDestroy(e[k]); } } events{ev};
+    if (ms) {
+        for (int k = 0; k < 4; k++) HIPCHK(hipEventCreate(&ev[k]));
+        HIPCHK(hipEventRecord(ev[0], nullptr));
+    }
+    HIPCHK(hipMemcpy(d_coef, q, q_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_coef + q_bytes, fr.coef.data(), coef_bytes, hipMemcpyHostToDevice));
+    JpegBlocks B;
+    B.n_blocks = (uint32_t)fr.n_blocks;
+    B.first1 = fr.ncomp == 3 ? (uint32_t)(fr.c[1].off / 64) : B.n_blocks;
+    B.first2 = fr.ncomp == 3 ? (uint32_t)(fr.c[2].off / 64) : B.n_blocks;
+    B.bx0 = fr.c[0].bx;
+    B.bx12 = fr.ncomp == 3 ? fr.c[1].bx : fr.c[0].bx;
+    if (ms) HIPCHK(hipEventRecord(ev[1], nullptr));
+    launch_jpeg_idct((const uint16_t*)d_coef, (const int16_t*)(d_coef + q_bytes), B, P, d_planes, nullptr);
+    HIPCHK(hipGetLastError());
+    if (ms) HIPCHK(hipEventRecord(ev[2], nullptr));
+    launch_jpeg_rgb(d_planes, P, d_rgb, nullptr);
+    HIPCHK(hipGetLastError());
+    if (ms) HIPCHK(hipEventRecord(ev[3], nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    if (ms)
+        for (int k = 0; k < 3; k++) HIPCHK(hipEventElapsedTime(&ms[1 + k], ev[k], ev[k + 1]));
+    return HPMVS_OK;
+}
+
 // hpmvs_scene_set_view and, for k1 != 0, hpmvs_scene_set_view_distorted: level 0 is the raw view undistorted on the GPU
+// (jf: hpmvs_scene_set_view_jpeg -- the raw level 0 is decoded on the device from the frame's coefficients; rgb_l0 is unused)
 static int set_view(hpmvs_scene* s, int view, int width, int height, const uint8_t* rgb_l0, int rgb_on_device,
-                    const hpmvs_camera* cam, float f, float k1) {
-    if (!s || !cam || !rgb_l0) return fail(HPMVS_ERR_ARG, "scene_set_view: null argument");
+                    const hpmvs_camera* cam, float f, float k1, const jpg::Frame* jf = nullptr) {
+    if (!s || !cam || (!rgb_l0 && !jf)) return fail(HPMVS_ERR_ARG, "scene_set_view: null argument");
     if (s->committed) return fail(HPMVS_ERR_STATE, "scene_set_view: scene already committed");
     if (view < 0 || view >= s->n_views || width < 2 || height < 2) return fail(HPMVS_ERR_ARG, "scene_set_view: bad view/size");
     if (cam->n_levels < 1 || cam->n_levels > HPMVS_MAX_LEVELS) return fail(HPMVS_ERR_ARG, "scene_set_view: bad n_levels");
@@ -379,11 +425,11 @@ static int set_view(hpmvs_scene* s, int view, int width, int height, const uint8
     uint8_t* raw_copy = nullptr;
     struct FreeRaw { uint8_t*& p; ~FreeRaw() { if (p) hipFree(p); } } free_raw{raw_copy};
     if (k1 != 0.0f) {
-        if (rgb_on_device) {
+        if (rgb_on_device && !jf) {
             raw = rgb_l0;
         } else {
             HIPCHK(hipMalloc((void**)&raw_copy, (size_t)width * height * 3));
-            HIPCHK(hipMemcpy(raw_copy, rgb_l0, (size_t)width * height * 3, hipMemcpyHostToDevice));
+            if (!jf) HIPCHK(hipMemcpy(raw_copy, rgb_l0, (size_t)width * height * 3, hipMemcpyHostToDevice));
             raw = raw_copy;
         }
     }
@@ -405,11 +451,15 @@ static int set_view(hpmvs_scene* s, int view, int width, int height, const uint8
     for (int l = 0; l < levels; l++) {
         uint8_t* d = slab + off[l];
         const size_t nb = (size_t)w * h * 3;
+        if (l == 0 && jf) {  // decoded straight into level 0, or into the raw copy the undistortion reads
+            const int rc = jpeg_frame_to_device(*jf, raw_copy ? raw_copy : d);
+            if (rc != HPMVS_OK) return rc;
+        }
         if (l == 0 && raw) {
             launch_undistort(raw, w, h, f, k1, d, nullptr);
             HIPCHK(hipGetLastError());
         } else if (l == 0) {
-            HIPCHK(hipMemcpy(d, rgb_l0, nb, rgb_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+            if (!jf) HIPCHK(hipMemcpy(d, rgb_l0, nb, rgb_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
         } else {
             launch_half_resize(V.pix[l - 1], V.w[l - 1], V.h[l - 1], d, nullptr);
             HIPCHK(hipGetLastError());
@@ -437,6 +487,66 @@ int hpmvs_scene_set_view_distorted(hpmvs_scene* s, int view, int width, int heig
                                    int rgb_on_device, const hpmvs_camera* cam, float f, float k1) {
     if (!undistort_args_ok(f, k1)) return fail(HPMVS_ERR_ARG, "scene_set_view_distorted: f must be finite and > 0, k1 finite");
     return set_view(s, view, width, height, rgb_raw, rgb_on_device, cam, f, k1);
+}
+
+int hpmvs_jpeg_info(const uint8_t* bytes, size_t n, int* width, int* height, int* components, int* h_samp, int* v_samp) {
+    if (!bytes || !width || !height || !components || !h_samp || !v_samp) return fail(HPMVS_ERR_ARG, "jpeg_info: null argument");
+    jpg::Frame fr;
+    std::string err;
+    const int rc = jpg::decode_file(bytes, n, fr, false, &err);
+    if (rc != jpg::kOk) return jpeg_fail(rc, err);
+    *width = fr.W; *height = fr.H; *components = fr.ncomp; *h_samp = fr.hmax; *v_samp = fr.vmax;
+    return HPMVS_OK;
+}
+
+int hpmvs_jpeg_decode(int device, const uint8_t* bytes, size_t n, uint8_t* rgb, size_t cap, int rgb_on_device) {
+    if (!bytes || !rgb) return fail(HPMVS_ERR_ARG, "jpeg_decode: null argument");
+    jpg::Frame fr;
+    std::string err;
+    const int rc = jpg::decode_file(bytes, n, fr, true, &err);
+    if (rc != jpg::kOk) return jpeg_fail(rc, err);
+    const size_t nb = (size_t)3 * fr.W * fr.H;
+    if (cap < nb) return fail(HPMVS_ERR_ARG, "jpeg_decode: output buffer smaller than 3 * width * height");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(HPMVS_ERR_NODEVICE, "no HIP device visible");
+    if (device < 0 || device >= ndev) return fail(HPMVS_ERR_ARG, "jpeg_decode: bad device index");
+    HIPCHK(hipSetDevice(device));
+    if (rgb_on_device) return jpeg_frame_to_device(fr, rgb);
+    uint8_t* d_rgb = nullptr;
+    struct Free { uint8_t*& a; ~Free() { if (a) hipFree(a); } } free_on_exit{d_rgb};
+    HIPCHK(hipMalloc((void**)&d_rgb, nb));
+    const int rd = jpeg_frame_to_device(fr, d_rgb);
+    if (rd != HPMVS_OK) return rd;
+    HIPCHK(hipMemcpy(rgb, d_rgb, nb, hipMemcpyDeviceToHost));
+    return HPMVS_OK;
+}
+
+int hpmvs_jpeg_decode_timed(int device, const uint8_t* bytes, size_t n, uint8_t* rgb_device, size_t cap, float* ms) {
+    if (!bytes || !rgb_device || !ms) return fail(HPMVS_ERR_ARG, "jpeg_decode_timed: null argument");
+    jpg::Frame fr;
+    std::string err;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = jpg::decode_file(bytes, n, fr, true, &err);
+    ms[0] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rc != jpg::kOk) return jpeg_fail(rc, err);
+    if (cap < (size_t)3 * fr.W * fr.H) return fail(HPMVS_ERR_ARG, "jpeg_decode_timed: output buffer smaller than 3 * width * height");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(HPMVS_ERR_NODEVICE, "no HIP device visible");
+    if (device < 0 || device >= ndev) return fail(HPMVS_ERR_ARG, "jpeg_decode_timed: bad device index");
+    HIPCHK(hipSetDevice(device));
+    return jpeg_frame_to_device(fr, rgb_device, ms);
+}
+
+int hpmvs_scene_set_view_jpeg(hpmvs_scene* s, int view, const uint8_t* bytes, size_t n, const hpmvs_camera* cam, float f, float k1) {
+    if (!s || !bytes || !cam) return fail(HPMVS_ERR_ARG, "scene_set_view_jpeg: null argument");
+    if (!undistort_args_ok(f, k1)) return fail(HPMVS_ERR_ARG, "scene_set_view_jpeg: f must be finite and > 0, k1 finite");
+    if (s->committed) return fail(HPMVS_ERR_STATE, "scene_set_view: scene already committed");
+    if (view < 0 || view >= s->n_views) return fail(HPMVS_ERR_ARG, "scene_set_view_jpeg: bad view");
+    jpg::Frame fr;
+    std::string err;
+    const int rc = jpg::decode_file(bytes, n, fr, true, &err);
+    if (rc != jpg::kOk) return jpeg_fail(rc, err);
+    return set_view(s, view, fr.W, fr.H, nullptr, 0, cam, f, k1, &fr);
 }
 
 int hpmvs_scene_set_covis(hpmvs_scene* s, int view, const int32_t* ids, int n) {

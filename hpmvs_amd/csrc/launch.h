@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dev_types.h"
+#include "jpeg.hpp"
 #include "seed_tree.hpp"
 
 namespace hpmvs {
@@ -155,6 +156,17 @@ int launch_octree_insert(const float* root, const unsigned long long* keys, cons
                          const float* points, const float* add_width, const OctreeInsertScratch& s, const OctreeInsertOut& out,
                          hipStream_t st);
 void launch_octree_route(int n_trees, const float* roots, int n, const float* points, int32_t* tree, hipStream_t st);
+
+// baseline JPEG behind the host's entropy decoder (kernel_jpeg.hip, jpeg.hpp, include/hpmvs_amd.h: hpmvs_jpeg_decode).  q: [3][64]
+// quantiser steps in natural order (unused tables zero), coef: the components' [blocks_y][blocks_x][64] int16 one behind the
+// other, 16-byte aligned; component c's blocks start at first<c> (first1 = first2 = n_blocks for grayscale).
+struct JpegBlocks {
+    uint32_t n_blocks, first1, first2;
+    int32_t bx0, bx12;  // blocks per row: luma, chroma
+};
+void launch_jpeg_idct(const uint16_t* q, const int16_t* coef, const JpegBlocks& B, const jpg::Planes& P, uint8_t* planes, hipStream_t st);
+// planes -> interleaved u8 RGB [H][W][3]: exactly W x H pixels are written
+void launch_jpeg_rgb(const uint8_t* planes, const jpg::Planes& P, uint8_t* rgb, hipStream_t st);
 
 // refined-patch records of the multi-GPU exchange (include/hpmvs_amd.h: hpmvs_record, 192 bytes)
 void launch_pack_records(const DevBatch& b, void* records, hipStream_t st);

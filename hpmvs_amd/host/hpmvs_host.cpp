@@ -215,16 +215,48 @@ void Image::init(const mo3d::NVM_Camera* cam, const int maxLevel) {
 void Image::setPixels(int width, int height, const uint8_t* rgb) {
     width_ = width; height_ = height;
     rgb_.assign(rgb, rgb + (size_t)width * height * 3);
+    jpeg_.clear();
     raw_ = false;
+}
+bool Image::setJpeg(const uint8_t* bytes, size_t n) {
+    int w = 0, h = 0, comps = 0, hs = 0, vs = 0;
+    if (hpmvs_jpeg_info(bytes, n, &w, &h, &comps, &hs, &vs) != HPMVS_OK) {
+        std::cerr << "hpmvs: " << (path_.empty() ? std::string("image") : path_) << ": " << hpmvs_last_error() << std::endl;
+        return false;
+    }
+    jpeg_.assign(bytes, bytes + n);
+    rgb_.clear();
+    width_ = w; height_ = h;
+    raw_ = true;  // as the camera recorded it: undistorted on upload when k1 != 0
+    return true;
+}
+const std::vector<uint8_t>& Image::pixels() const {
+    if (rgb_.empty() && !jpeg_.empty()) {
+        std::vector<uint8_t> px((size_t)width_ * height_ * 3);
+        if (hpmvs_jpeg_decode(0, jpeg_.data(), jpeg_.size(), px.data(), px.size(), 0) == HPMVS_OK) rgb_.swap(px);
+        else std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl;
+    }
+    return rgb_;
 }
 void Image::setRawPixels(int width, int height, const uint8_t* rgb) {
     setPixels(width, height, rgb);
     raw_ = true;
 }
 bool Image::load() {
-    if (!rgb_.empty()) return true;  // pixels were handed over with setPixels / setRawPixels
+    if (!rgb_.empty() || !jpeg_.empty()) return true;  // handed over with setPixels / setRawPixels / setJpeg
     // raw pixels: the undistortion of Image.cpp:50-53 runs on the GPU when the scene is uploaded (Scene::deviceScene)
     std::ifstream in(path_.c_str(), std::ios::binary);
+    if (in.get() == 0xFF && in.get() == 0xD8) {  // JPEG by its first bytes, whatever the file is called
+        in.seekg(0, std::ios::end);
+        const std::streamoff len = in.tellg();
+        if (!in || len < 4) return false;
+        std::vector<uint8_t> file((size_t)len);
+        in.seekg(0);
+        in.read((char*)file.data(), len);
+        return in && setJpeg(file.data(), file.size());
+    }
+    in.clear();
+    in.seekg(0);
     std::string magic;
     int w = 0, h = 0, maxv = 0;
     in >> magic >> w >> h >> maxv;
@@ -568,7 +600,10 @@ hpmvs_scene* Scene::deviceScene() const {
         hc.fsum = c.kMat_[0](0, 0) + c.kMat_[0](1, 1);
         hc.n_levels = c.getLevels();
         const Image& im = images_[i];
-        const int rc = im.isRaw() && im.getK1() != 0
+        const int rc = im.isJpeg()   // decoded, undistorted and reduced in HBM: the pixels never visit the host
+                           ? hpmvs_scene_set_view_jpeg(s, (int)i, im.jpegBytes().data(), im.jpegBytes().size(), &hc, im.getFocal(),
+                                                       im.getK1())
+                       : im.isRaw() && im.getK1() != 0
                            ? hpmvs_scene_set_view_distorted(s, (int)i, im.getWidth(), im.getHeight(), im.pixels().data(), 0, &hc,
                                                             im.getFocal(), im.getK1())
                            : hpmvs_scene_set_view(s, (int)i, im.getWidth(), im.getHeight(), im.pixels().data(), 0, &hc);

@@ -1,10 +1,12 @@
 // mo3d::Image -- the level-0 pixels of one view (reference include/hpmvs/Image.h:50-87).  The reference
 // loads a JPEG through CImg, undistorts it when the camera's radial coefficient k1 (NVM field r) is not 0
 // and builds the pyramid on the host (src/hpmvs/Image.cpp:41-146); here the caller hands over interleaved
-// u8 RGB (file decoding is I/O outside the path) and both the undistortion and the pyramid run on the GPU
-// when the scene is uploaded (Scene::deviceScene: hpmvs_scene_set_view_distorted for raw pixels).
+// u8 RGB, or the view is a baseline JPEG file as VisualSFM's NVM names it, whose bytes are kept and decoded on
+// the GPU (hpmvs_scene_set_view_jpeg); both the undistortion and the pyramid run on the GPU when the scene is
+// uploaded (Scene::deviceScene: hpmvs_scene_set_view_distorted for raw pixels).
 #ifndef HPMVS_IMAGE_H_
 #define HPMVS_IMAGE_H_
+#include <cstddef>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -15,7 +17,14 @@ public:
     Image() : f_(1.0f), k1_(0.0f), maxLevel_(0), width_(0), height_(0), raw_(false) {}
     virtual ~Image() {}
     void init(const mo3d::NVM_Camera* cam, const int maxLevel = 1);
-    bool load();  // binary PPM (P6) only; the pixels are kept raw (as the camera recorded them)
+    // The file's first bytes decide: FF D8 is a JPEG, "P6" a binary PPM (the reference and CImg go by the extension).  A PPM's
+    // pixels are kept raw (as the camera recorded them).  Of a JPEG the file's bytes are kept and width and height are taken
+    // from hpmvs_jpeg_info, which refuses what the decoder would refuse (include/hpmvs_amd.h); no pixel is decoded here.
+    bool load();
+    // the same for a JPEG file the caller holds in memory; false (and the image unchanged) for a file that is refused
+    bool setJpeg(const uint8_t* bytes, size_t n);
+    bool isJpeg() const { return !jpeg_.empty(); }
+    const std::vector<uint8_t>& jpegBytes() const { return jpeg_; }
     // pixels taken as given: already undistorted (or k1 == 0); k1 is NOT applied to them
     void setPixels(int width, int height, const uint8_t* rgb_interleaved);
     // pixels as the camera recorded them: undistorted with f and k1 on upload when k1 != 0
@@ -26,9 +35,11 @@ public:
     inline int getWidth(int level = 0) const { return width_ >> level; }
     inline int getHeight(int level = 0) const { return height_ >> level; }
     int levels() const { return maxLevel_ + 1; }
-    const std::vector<uint8_t>& pixels() const { return rgb_; }
+    // level-0 pixels; of a JPEG image they are decoded on first use (hpmvs_jpeg_decode on device 0; empty when that fails)
+    const std::vector<uint8_t>& pixels() const;
 private:
-    std::vector<uint8_t> rgb_;
+    mutable std::vector<uint8_t> rgb_;
+    std::vector<uint8_t> jpeg_;  // the file, when the view is a JPEG
     std::string path_;
     float f_, k1_;
     int maxLevel_, width_, height_;

@@ -26,6 +26,8 @@
  *                               (CImg get_resize_halfXY, thirdLibs/cimg/CImg.h:21189-21203).
  *   hpmvs_undistort,         <- Image::undistort, src/hpmvs/Image.cpp:68-146 (run by Image::load for
  *   hpmvs_scene_set_view_distorted  k1 != 0, :50-53), before the pyramid.
+ *   hpmvs_jpeg_decode,       <- Image::load's CImg / libjpeg read of the view, src/hpmvs/Image.cpp:46
+ *   hpmvs_scene_set_view_jpeg   (thirdLibs/cimg/CImg.h:36920-36934).
  *   hpmvs_init_patches_batch <- the seed loop of Scene::initPatches, src/hpmvs/Scene.cpp:112-178.
  *   hpmvs_init_patches_sphere_batch <- the same loop with the scene-centre gate of --only_sphere
  *                               (options.FILTER_SCENE_CENTER), src/hpmvs/Scene.cpp:105-121.
@@ -57,6 +59,7 @@ extern "C" {
 #define HPMVS_ERR_ARG (-2)     /* bad argument */
 #define HPMVS_ERR_STATE (-3)   /* scene not committed / already committed */
 #define HPMVS_ERR_NODEVICE (-4) /* no gfx950 device visible: there is NO CPU fallback */
+#define HPMVS_ERR_UNSUPPORTED (-5) /* a well-formed input of a kind that is not handled (JPEG decoding: see hpmvs_jpeg_decode) */
 
 #define HPMVS_MAX_LEVELS 8
 #define HPMVS_MAX_IMAGES 256 /* images attached to one patch (reference: unbounded vector<int>); overflow => stage 100.  Lists of up to
@@ -182,6 +185,38 @@ int hpmvs_undistort_map(int device, int w, int h, float f, float k1, float *xy);
  * hpmvs_scene_set_view. */
 int hpmvs_scene_set_view_distorted(hpmvs_scene *s, int view, int width, int height, const uint8_t *rgb_raw,
                                    int rgb_on_device, const hpmvs_camera *cam, float f, float k1);
+
+/* ---- baseline JPEG views (what VisualSFM's NVM files name) ---------------------------------- */
+/* Image::load of the reference reads a view through CImg and libjpeg with the library's defaults (JDCT_ISLOW, fancy
+ * upsampling, the integer YCbCr tables); these entries give the same pixels byte for byte.  The host parses the markers
+ * and decodes the entropy data of the one scan into int16 coefficients, on the calling thread (callers parallelise over
+ * views, as the reference's loop over cameras does); dequantisation, the 8x8 IDCT, chroma interpolation and the colour
+ * conversion run on the GPU (kernel_jpeg.hip).
+ * Decoded: 8-bit baseline or extended-sequential Huffman files (SOF0, SOF1) with 8-bit quantisation tables, one component
+ *   (grayscale, written as R = G = B) or three as YCbCr with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1, all components in
+ *   one scan, with or without restart intervals, 8 to 65535 pixels on a side and fewer than 4 Gi samples in all.
+ * HPMVS_ERR_UNSUPPORTED: progressive, arithmetic-coded, lossless or hierarchical frames; 12-bit samples; four components;
+ *   data libjpeg would take for RGB-coded (Adobe APP14 with transform 0, or component ids 'R','G','B', without JFIF); other
+ *   sampling factors; more than one scan; 16-bit quantisation tables; an image under 8 pixels on a side.
+ * HPMVS_ERR_ARG: anything malformed, and a truncated file (libjpeg would pad it with grey and warn; here it is refused).
+ * hpmvs_last_error names the reason.  The file bytes are always host memory; every read of them is bounds checked. */
+/* Pure host code, usable without a GPU.  It walks the whole file, entropy data included, and so returns what the decoder
+ * would.  h_samp, v_samp: the luma sampling factors (1,1 / 2,1 / 2,2; 1,1 for grayscale). */
+int hpmvs_jpeg_info(const uint8_t *bytes, size_t n, int *width, int *height, int *components, int *h_samp, int *v_samp);
+/* rgb: width x height interleaved u8 RGB, 3*(y*W+x)+c, host memory or (rgb_on_device != 0) device memory on `device`;
+ * exactly 3*W*H bytes are written.  HPMVS_ERR_ARG for NULL pointers and for cap < 3*W*H; arguments and the file are
+ * checked before the device is looked for (HPMVS_ERR_NODEVICE).  Working buffers (2 bytes of coefficients and 1 byte of
+ * sample planes per sample) live for the call only. */
+int hpmvs_jpeg_decode(int device, const uint8_t *bytes, size_t n, uint8_t *rgb, size_t cap, int rgb_on_device);
+/* diagnostics (tools/jpeg_scale.py): hpmvs_jpeg_decode to a device buffer, with the time of its stages in ms[4]: host parse
+ * and entropy decode (wall clock, this thread), coefficient upload, IDCT kernel, RGB kernel (HIP events) */
+int hpmvs_jpeg_decode_timed(int device, const uint8_t *bytes, size_t n, uint8_t *rgb_device, size_t cap, float *ms);
+/* hpmvs_scene_set_view for a view given as JPEG file bytes: level 0 is decoded in HBM (the pixels never visit the host),
+ * undistorted there when k1 != 0 (as hpmvs_scene_set_view_distorted does, and with its rules for f and k1, which hold for
+ * k1 == 0 too), and the pyramid is built from it.  Width and height are the file's (hpmvs_jpeg_info).  Calls for different
+ * views of one scene are as independent of each other as those of hpmvs_scene_set_view; nothing is kept between calls. */
+int hpmvs_scene_set_view_jpeg(hpmvs_scene *s, int view, const uint8_t *bytes, size_t n, const hpmvs_camera *cam, float f,
+                              float k1);
 
 /* ---- the hot path ------------------------------------------------------------------------- */
 /* Full optimize() for every patch of the batch.  `stream` is a hipStream_t (NULL = default
