@@ -57,6 +57,11 @@ class OctreeIndex(C.Structure):
                 ("branch_key", C.c_void_p), ("leaf_key", C.c_void_p)]
 
 
+class OctreePartitionInfo(C.Structure):
+    _fields_ = [("n_trees", C.c_int32), ("n_orphans", C.c_int32), ("n_splits", C.c_int32), ("stop", C.c_int32),
+                ("histogram", C.c_int32 * 22)]
+
+
 class SeedTreeInfo(C.Structure):
     _fields_ = [("root_center", C.c_float * 3), ("root_width", C.c_float), ("scale_floor", C.c_float), ("n_rows", C.c_int32),
                 ("n_leaves", C.c_int32)]
@@ -75,7 +80,7 @@ EXPORTS = [
     "hpmvs_host_alloc", "hpmvs_host_free", "hpmvs_last_staging",
     "hpmvs_undistort", "hpmvs_undistort_map", "hpmvs_scene_set_view_distorted",
     "hpmvs_regularize_batch", "hpmvs_filter_batch", "hpmvs_seed_tree_batch", "hpmvs_octree_locate_batch",
-    "hpmvs_octree_insert_batch", "hpmvs_octree_route_batch",
+    "hpmvs_octree_insert_batch", "hpmvs_octree_route_batch", "hpmvs_octree_partition",
     "hpmvs_scene_center", "hpmvs_init_patches_sphere_batch",
     "hpmvs_jpeg_info", "hpmvs_jpeg_decode", "hpmvs_scene_set_view_jpeg", "hpmvs_jpeg_decode_timed",
 ]
@@ -152,6 +157,8 @@ def lib():
     L.hpmvs_octree_locate_batch.argtypes = [C.c_void_p, C.POINTER(OctreeIndex), C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
     L.hpmvs_octree_insert_batch.argtypes = [C.c_void_p, C.POINTER(OctreeIndex), C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
     L.hpmvs_octree_route_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.hpmvs_octree_partition.argtypes = [C.c_void_p, C.POINTER(OctreeIndex), C.c_int, C.c_int, C.POINTER(OctreePartitionInfo)] + \
+        [C.c_void_p] * 9 + [C.c_int, C.c_void_p]
     _lib = L
     return L
 
@@ -690,3 +697,52 @@ def octree_route_batch(scene: Scene, roots, points) -> np.ndarray:
     tree = np.zeros(len(pts), np.int32)
     _chk(lib().hpmvs_octree_route_batch(scene.h, len(rt), rt.ctypes.data, len(pts), pts.ctypes.data, tree.ctypes.data, 0, None))
     return tree
+
+
+MAX_SUBTREES = 4096   # HPMVS_MAX_SUBTREES: the largest min_trees
+PARTITION_STOP = ("the root alone", "the list reached min_trees", "the largest subtree is below min_split_leaves")
+PARTITION_OUTPUTS = ("root_key", "root_cell", "tree_first", "tree_leaves", "leaf_order", "leaf_tree", "leaf_sub_key", "branch_tree",
+                     "branch_sub_key")
+
+
+@dataclass
+class OctreePartition:
+    n_trees: int
+    n_orphans: int                 # nonempty leaves in no subtree
+    n_splits: int                  # iterations of getSubTrees' while loop that cut a subtree
+    stop: int                      # index into PARTITION_STOP
+    histogram: np.ndarray          # [22] int32 cellHistogram: nonempty leaves by depth below the root
+    root_key: np.ndarray           # [cap] uint64 the subtree roots in the reference's list order, 0 from n_trees on
+    root_cell: np.ndarray          # [cap, 4] float32 c_, width_
+    tree_first: np.ndarray         # [cap] int32 subtree k's nonempty leaves: leaf_order[tree_first[k] : tree_first[k] + tree_leaves[k]]
+    tree_leaves: np.ndarray        # [cap] int32
+    leaf_order: np.ndarray         # [n_leaves] int32 indices into the leaf keys given, in Leaf_iterator order
+    leaf_tree: np.ndarray          # [n_leaves] int32 -1: an orphan
+    leaf_sub_key: np.ndarray       # [n_leaves] uint64 the key re-based on its subtree's root, 0 for an orphan
+    branch_tree: np.ndarray        # [n_branches] int32 -1: a root or a branch above the roots
+    branch_sub_key: np.ndarray     # [n_branches] uint64
+
+
+def partition_capacity(min_trees: int) -> int:
+    """Entries of the root outputs of hpmvs_octree_partition: the list cannot end longer."""
+    return max(8, int(min_trees) + 6)
+
+
+def octree_partition(scene: Scene, root_center, root_width, branch_key, leaf_key, min_trees: int = 100,
+                     min_split_leaves: int = 100) -> OctreePartition:
+    """getSubTrees(tree, list, min_trees) of the reference's main (src/main.cpp:50-96) and DynOctTree::cellHistogram for an octree
+    given as path keys in any order, as ONE call (include/hpmvs_amd.h: hpmvs_octree_partition).  min_split_leaves is the
+    reference's constant 100.  HpmvsError when the keys are no tree, min_trees > MAX_SUBTREES or min_split_leaves < 1."""
+    bk = np.ascontiguousarray(branch_key, dtype=np.uint64).reshape(-1)
+    lk = np.ascontiguousarray(leaf_key, dtype=np.uint64).reshape(-1)
+    t = _octree_index(root_center, root_width, bk, lk)
+    cap, nb, nl = partition_capacity(min_trees), len(bk), len(lk)
+    info = OctreePartitionInfo()
+    r = OctreePartition(0, 0, 0, 0, np.zeros(22, np.int32), np.zeros(cap, np.uint64), np.zeros((cap, 4), np.float32),
+                        np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(nl, np.int32), np.zeros(nl, np.int32),
+                        np.zeros(nl, np.uint64), np.zeros(nb, np.int32), np.zeros(nb, np.uint64))
+    _chk(lib().hpmvs_octree_partition(scene.h, C.byref(t), int(min_trees), int(min_split_leaves), C.byref(info),
+                                      *[getattr(r, k).ctypes.data for k in PARTITION_OUTPUTS], 0, None))
+    r.n_trees, r.n_orphans, r.n_splits, r.stop = info.n_trees, info.n_orphans, info.n_splits, info.stop
+    r.histogram[:] = info.histogram[:]
+    return r

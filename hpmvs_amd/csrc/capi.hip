@@ -2190,6 +2190,77 @@ int hpmvs_octree_insert_batch(const hpmvs_scene* s, const hpmvs_octree_index* t,
     HIPCHK(hipGetLastError());
     return c.finish();   // (waits in both forms: the scratch is freed when this call returns)
 }
+// getSubTrees(tree, list, min_trees) and cellHistogram (src/main.cpp:50-96, doctree.h:493-523) for the tree t
+// (kernel_octree_partition.hip: leaf kernel, sort by aligned key, the loop on one wavefront, assignment).  The scratch is the
+// call's own; the one read-back after the table's verdict is the device record.
+static_assert(sizeof(hpmvs_octree_partition_info) == 4 * kPartitionInts && HPMVS_MAX_SUBTREES == octree::kMaxSubtrees &&
+              HPMVS_MAX_TREE_DEPTH == octree::kMaxDepth, "hpmvs_octree_partition_info is the device record");
+int hpmvs_octree_partition(const hpmvs_scene* s, const hpmvs_octree_index* t, int min_trees, int min_split_leaves,
+                           hpmvs_octree_partition_info* info, uint64_t* root_key, float* root_cell, int32_t* tree_first,
+                           int32_t* tree_leaves, int32_t* leaf_order, int32_t* leaf_tree, uint64_t* leaf_sub_key, int32_t* branch_tree,
+                           uint64_t* branch_sub_key, int on_device, void* stream) {
+    const char* who = "octree_partition";
+    OctreeLayout L;
+    int rc = octree_index_check(s, t, 0, nullptr, who, &L);
+    if (rc) return rc;
+    if (!info) return fail(HPMVS_ERR_ARG, "octree_partition: info missing");
+    if (min_trees > HPMVS_MAX_SUBTREES) return fail(HPMVS_ERR_ARG, "octree_partition: min_trees exceeds HPMVS_MAX_SUBTREES");
+    if (min_split_leaves < 1) return fail(HPMVS_ERR_ARG, "octree_partition: min_split_leaves must be >= 1");
+    const size_t nb = (size_t)t->n_branches, nl = (size_t)t->n_leaves;
+    const int cap = min_trees + 6 > 8 ? min_trees + 6 : 8;
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    Call c(s, on_device, st);
+    const unsigned long long* dbk = (const unsigned long long*)c.in(t->branch_key, nb);
+    const unsigned long long* dlk = (const unsigned long long*)c.in(t->leaf_key, nl);
+    OctreePartitionRoots roots;   // (the kernels write every entry of every output they are given: no zero fill)
+    roots.root_key = (unsigned long long*)c.arr(root_key, (size_t)cap, Call::kCopyBack);
+    roots.root_cell = c.arr(root_cell, 4 * (size_t)cap, Call::kCopyBack);
+    roots.tree_first = c.arr(tree_first, (size_t)cap, Call::kCopyBack);
+    roots.tree_leaves = c.arr(tree_leaves, (size_t)cap, Call::kCopyBack);
+    int32_t* dorder = c.arr(leaf_order, nl, Call::kCopyBack);
+    OctreePartitionKeys out;
+    out.leaf_tree = c.arr(leaf_tree, nl, Call::kCopyBack);
+    out.leaf_sub_key = (unsigned long long*)c.arr(leaf_sub_key, nl, Call::kCopyBack);
+    out.branch_tree = c.arr(branch_tree, nb, Call::kCopyBack);
+    out.branch_sub_key = (unsigned long long*)c.arr(branch_sub_key, nb, Call::kCopyBack);
+    OctreePartitionScratch S;
+    memset(&S, 0, sizeof(S));
+    S.temp_bytes = octree_partition_temp_bytes((int)nl);
+    if (S.temp_bytes == (size_t)-1) return fail(HPMVS_ERR_HIP, "octree_partition: rocPRIM size query failed");
+    S.root_slots = octree::table_slots((size_t)cap);
+    // one block: the record and the root table (zeroed), two 8-byte and two 4-byte arrays per leaf, then rocPRIM's temporary storage
+    const size_t o_rk = reg_align(4 * kPartitionInts), o_rv = o_rk + 8 * (size_t)S.root_slots, o_ka = reg_align(o_rv + 4 * (size_t)S.root_slots);
+    const size_t o_temp = reg_align(o_ka + 24 * nl);
+    char* blk = (char*)c.scratch(o_temp + S.temp_bytes);
+    if (!blk) return c.error();
+    S.info = (int32_t*)blk;
+    S.root_keys = (unsigned long long*)(blk + o_rk); S.root_vals = (int32_t*)(blk + o_rv);
+    S.key_a = (unsigned long long*)(blk + o_ka); S.key_b = S.key_a + nl;
+    S.val_a = (int32_t*)(S.key_b + nl); S.val_b = S.val_a + nl;
+    S.temp = blk + o_temp;
+    if ((rc = c.begin(st))) return rc;
+    // the scene lock is held from here on: the workspace is this call's until its last kernel has been enqueued
+    std::lock_guard<std::recursive_mutex> lk(s->mu);
+    if ((rc = service_quiesce(s))) return rc;
+    int32_t* q;
+    int slot;
+    if ((rc = acquire_workspace(s, &q, &slot, st))) return rc;
+    struct Release { const hpmvs_scene* s; int slot; hipStream_t st; ~Release() { hipEventRecord(s->slot_done[slot], st); s->slot_used[slot] = true; } } rel{s, slot, st};
+    char* w = (char*)q;
+    if ((rc = octree_table_build(t, dbk, dlk, L, w, st, who))) return rc;
+    HIPCHK(hipMemsetAsync(blk, 0, o_ka, st));
+    const float root[4] = {t->root_center[0], t->root_center[1], t->root_center[2], t->root_width};
+    if (launch_octree_partition(root, (unsigned long long*)(w + L.o_keys), (int32_t*)(w + L.o_vals), (uint32_t)L.slots, dbk, (int)nb, dlk, (int)nl,
+                                min_trees, min_split_leaves, cap, S, roots, dorder, out, st))
+        return fail(HPMVS_ERR_HIP, "octree_partition: rocPRIM sort failed");
+    HIPCHK(hipGetLastError());
+    int32_t h[kPartitionInts];
+    HIPCHK(hipMemcpyAsync(h, S.info, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    memcpy(info, h, sizeof(*info));
+    return c.finish();   // (waits in both forms: the scratch is freed when this call returns)
+}
 // distributeBorderCell's search (CellProcessor.cpp:487-498, 533-540): the first root in list order that contains the point.  The
 // roots are a host array in both forms, like an hpmvs_octree_index: they are checked here and travel in the call's scratch.
 int hpmvs_octree_route_batch(const hpmvs_scene* s, int n_trees, const float* roots, int n, const float* points, int32_t* tree, int on_device,

@@ -157,6 +157,35 @@ int launch_octree_insert(const float* root, const unsigned long long* keys, cons
                          hipStream_t st);
 void launch_octree_route(int n_trees, const float* roots, int n, const float* points, int32_t* tree, hipStream_t st);
 
+// the split into subtrees (kernel_octree_partition.hip, include/hpmvs_amd.h: hpmvs_octree_partition).  launch_octree_partition
+// reads the table launch_octree_build made and enqueues the leaf kernel, the sort, the one-wavefront loop and the assignment on
+// st; != 0: the rocPRIM call failed.  info: the call's device record, zeroed by the caller -- the hpmvs_octree_partition_info the
+// host reads.  root_keys / root_vals: the final roots as a table of their own (key -> list index; root_slots a power of two
+// > 2 cap, keys zeroed by the caller).  Every output is nullable; what is given is written in every entry ([cap] the roots').
+constexpr int kPartitionTrees = 0, kPartitionOrphans = 1, kPartitionSplits = 2, kPartitionStop = 3, kPartitionHistogram = 4,
+              kPartitionInts = 4 + 22;
+struct OctreePartitionRoots {
+    unsigned long long* root_key; float* root_cell; int32_t* tree_first; int32_t* tree_leaves;
+};
+struct OctreePartitionKeys {
+    int32_t* leaf_tree; unsigned long long* leaf_sub_key; int32_t* branch_tree; unsigned long long* branch_sub_key;
+};
+struct OctreePartitionScratch {
+    int32_t* info;                       // [kPartitionInts]
+    unsigned long long *key_a, *key_b;   // [n_leaves] each: the aligned keys, unsorted and sorted
+    int32_t *val_a, *val_b;              // [n_leaves] each (val_b stands in for a leaf_order that is not asked for)
+    unsigned long long* root_keys;       // [root_slots]
+    int32_t* root_vals;                  // [root_slots]
+    uint32_t root_slots;
+    void* temp;                          // octree_partition_temp_bytes(n_leaves)
+    size_t temp_bytes;
+};
+size_t octree_partition_temp_bytes(int nl);   // (size_t)-1: the size query failed
+int launch_octree_partition(const float* root, const unsigned long long* keys, const int32_t* vals, uint32_t slots,
+                            const unsigned long long* branch_key, int nb, const unsigned long long* leaf_key, int nl, int min_trees,
+                            int min_split_leaves, int cap, const OctreePartitionScratch& s, const OctreePartitionRoots& roots,
+                            int32_t* leaf_order, const OctreePartitionKeys& out, hipStream_t st);
+
 // baseline JPEG behind the host's entropy decoder (kernel_jpeg.hip, jpeg.hpp, include/hpmvs_amd.h: hpmvs_jpeg_decode).  q: [3][64]
 // quantiser steps in natural order (unused tables zero), coef: the components' [blocks_y][blocks_x][64] int16 one behind the
 // other, 16-byte aligned; component c's blocks start at first<c> (first1 = first2 = n_blocks for grayscale).

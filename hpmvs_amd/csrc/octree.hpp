@@ -2,7 +2,7 @@
 // src/hpmvs/CellProcessor.cpp:122-125, 147-154, include/hpmvs/doctree.h:250-255, 397-419, src/hpmvs/doctree.cpp:30-42).  Written
 // once for the device kernels (kernel_octree.hip, kernel_octree_insert.hip) and for the host restatements the tests compile with
 // g++ (tests/octree_host.cpp, tests/octree_insert_host.cpp).  DESIGN.md §3.11 has the argument; §3.12 the one for inserting a
-// round's border patches in queue order (the second half of this file).
+// round's border patches in queue order (the second part of this file), §3.14 the one for the split into subtrees (the last).
 //
 //   path key                 a sentinel bit, then 3 bits per level (z y x, Branch::at's child test x > c_): the root is 1, a cell
 //                            at depth d has 3 d bits below the sentinel; at most kMaxDepth = 21 levels (kernel_regularize.hip's form)
@@ -252,6 +252,110 @@ inline void insert_sequential(const Cell& root, const Table& t, int n, const flo
         leaf_key[i] = r.key;
         if (r.accepted) A.push_back(Entry{r.key, i});
         else if (blocker && any) blocker[i] = A[rank_pos(best)].owner;
+    }
+}
+
+// ---- the split into subtrees (getSubTrees, reference src/main.cpp:50-96; DynOctTree::getSubTrees, doctree.h:513-523;
+// Branch::nrLeafs, doctree.h:236-247).  The aligned key of a cell -- its path bits without the sentinel, shifted
+// to the top of 63 bits -- orders cells as Leaf_iterator visits them (children 0 .. 7, depth first), and the cells below a key
+// of depth d are the aligned keys in [align(key), align(key) + 8^(kMaxDepth - d)).  The nonempty leaves are prefix-free, so
+// their aligned keys are distinct, and sorted ascending they ARE the Leaf_iterator order: the leaves of any subtree are one
+// contiguous range of that order, and nrLeafs of any cell is two binary searches in it.
+constexpr int kMaxSubtrees = 4096;                     // HPMVS_MAX_SUBTREES: the largest min_trees
+constexpr int kMaxSubtreeList = kMaxSubtrees + 7;      // the list while it is cut: below min_trees, minus one, plus eight
+constexpr int kStopRoot = 0, kStopEnough = 1, kStopSmall = 2;   // hpmvs_octree_partition_info::stop
+
+HPMVS_OT_FN uint64_t aligned_key(uint64_t key) {
+    const int d = key_depth(key);
+    return (key ^ (1ull << (3 * d))) << (3 * (kMaxDepth - d));
+}
+HPMVS_OT_FN uint64_t aligned_span(uint64_t key) { return 1ull << (3 * (kMaxDepth - key_depth(key))); }
+// the first position of the ascending a[0 .. n - 1] whose entry is not below v
+HPMVS_OT_FN int32_t lower_bound(const uint64_t* a, int32_t n, uint64_t v) {
+    int32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int32_t mid = lo + (hi - lo) / 2;
+        if (a[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+// the range of a cell's nonempty leaves in the sorted aligned leaf keys: its first position, and Branch::nrLeafs
+HPMVS_OT_FN int32_t first_leaf(const uint64_t* sorted, int32_t n, uint64_t key) { return lower_bound(sorted, n, aligned_key(key)); }
+HPMVS_OT_FN int32_t nr_leafs(const uint64_t* sorted, int32_t n, uint64_t key) {
+    const uint64_t lo = aligned_key(key);
+    return lower_bound(sorted, n, lo + aligned_span(key)) - lower_bound(sorted, n, lo);
+}
+// child idx of a cut cell: true when it is a BRANCH (it becomes a subtree, empty or not; a LEAF child enters none), *count its
+// nrLeafs -- computed once, here: no subtree changes while the list is cut
+HPMVS_OT_FN bool split_child(const Table& t, const uint64_t* sorted, int32_t n, uint64_t picked, unsigned idx, uint64_t* key, int32_t* count) {
+    *key = (picked << 3) | idx;
+    *count = nr_leafs(sorted, n, *key);
+    return find(t, *key) == kBranch;
+}
+// main.cpp:67-75 as a maximum: the larger count first, then the LOWER list index (nrLeafs > maxLeafs is strict).  0 is below
+// every entry: maxLeafs = -1 of the empty list.
+HPMVS_OT_FN uint64_t split_rank(int32_t count, uint32_t index) { return ((uint64_t)(uint32_t)(count + 1) << 32) | (uint64_t)(0xffffffffu - index); }
+HPMVS_OT_FN int32_t rank_count(uint64_t rank) { return (int32_t)(rank >> 32) - 1; }
+HPMVS_OT_FN uint32_t rank_index(uint64_t rank) { return 0xffffffffu - (uint32_t)rank; }
+// where entry i of the list goes when entry m is replaced by its n_new branch children, which come FIRST (main.cpp:81-88)
+HPMVS_OT_FN int32_t split_position(int32_t i, int32_t m, int32_t n_new) { return i < m ? i + n_new : i + n_new - 1; }
+// the cell of a key by the chain Cell(parent, idx) from the root
+HPMVS_OT_FN Cell key_cell(const Cell& root, uint64_t key) {
+    Cell b = root;
+    for (int d = key_depth(key) - 1; d >= 0; d--) b = child(b, (unsigned)(key >> (3 * d)) & 7u);
+    return b;
+}
+// a key re-based on its ancestor of depth root_depth: the sentinel, then the bits below that depth
+HPMVS_OT_FN uint64_t sub_key(uint64_t key, int root_depth) {
+    const int below = 3 * (key_depth(key) - root_depth);
+    return (1ull << below) | (key & ((1ull << below) - 1));
+}
+// the subtree a key lies in: the value of the PROPER ancestor that is in `roots` (key -> list index; the final roots never
+// nest, so at most one is), -1 when none is -- an orphan leaf, a root itself, or a branch above the roots
+HPMVS_OT_FN int32_t owner_tree(const Table& roots, uint64_t key, int* root_depth) {
+    int d = key_depth(key);
+    for (uint64_t a = key >> 3; a != 0; a >>= 3) {
+        d--;
+        const int32_t v = find(roots, a);
+        if (v >= 0) { *root_depth = d; return v; }
+    }
+    *root_depth = 0;
+    return -1;
+}
+
+struct Split {
+    int32_t n_trees, n_splits, stop;
+};
+// getSubTrees(tree, list, min_trees) on one thread, over the table and the sorted aligned keys of the nl nonempty leaves.
+// list_key / list_count: [max(8, min_trees + 6)], the subtree roots in the reference's list order and their nrLeafs.
+// min_split_leaves: the reference's 100 (main.cpp:78).  The loop ends: every cut takes one branch out of the list for good.
+inline Split partition_sequential(const Table& t, const uint64_t* sorted, int32_t nl, int min_trees, int min_split_leaves,
+                                  uint64_t* list_key, int32_t* list_count) {
+    Split r{1, 0, kStopRoot};
+    list_key[0] = kRootKey;
+    list_count[0] = nl;
+    if (min_trees < 2) return r;
+    uint64_t rank = split_rank(list_count[0], 0);   // "do a first split", whatever the root holds
+    while (true) {
+        const int32_t m = (int32_t)rank_index(rank);
+        uint64_t new_key[8];
+        int32_t new_count[8], n_new = 0;
+        for (unsigned idx = 0; idx < 8; idx++)
+            if (split_child(t, sorted, nl, list_key[m], idx, &new_key[n_new], &new_count[n_new])) n_new++;
+        std::vector<uint64_t> key(list_key, list_key + r.n_trees);
+        std::vector<int32_t> count(list_count, list_count + r.n_trees);
+        for (int32_t i = 0; i < r.n_trees; i++)
+            if (i != m) { list_key[split_position(i, m, n_new)] = key[i]; list_count[split_position(i, m, n_new)] = count[i]; }
+        for (int32_t k = 0; k < n_new; k++) { list_key[k] = new_key[k]; list_count[k] = new_count[k]; }
+        r.n_trees += n_new - 1;
+        if (r.n_trees >= min_trees) { r.stop = kStopEnough; return r; }
+        rank = 0;
+        for (int32_t i = 0; i < r.n_trees; i++) {
+            const uint64_t x = split_rank(list_count[i], (uint32_t)i);
+            if (x > rank) rank = x;
+        }
+        if (rank_count(rank) < min_split_leaves) { r.stop = kStopSmall; return r; }
+        r.n_splits++;
     }
 }
 

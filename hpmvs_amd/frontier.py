@@ -936,3 +936,51 @@ def insert_border(scene: api.Scene, tree: Octree, border: api.Batch, priority, r
     keys = r.leaf_key[acc]
     return BorderResult(acc, keys, np.array([tree.node_level(int(k)) for k in keys], np.int32), np.zeros(len(acc), np.float32),
                         priority[acc].copy(), r)
+
+
+# ---- the split into subtrees (reference src/main.cpp:50-96, CellProcessor.cpp:422-455) --------------
+
+@dataclass
+class Partition:
+    trees: list                    # Octree per subtree in the reference's list order: each equals tree.subtree(root_key[t])
+    root_key: np.ndarray           # [len(trees)] uint64 the roots' path keys in `tree`
+    orphans: np.ndarray            # uint64 keys of the nonempty leaves of `tree` in no subtree: no CellProcessor ever sees them
+    queues: list                   # queues[t]: [(priority = node_level * 10, leaf key in trees[t])] in Leaf_iterator order
+    histogram: np.ndarray          # [22] int32 cellHistogram: nonempty leaves of `tree` by depth below its root
+    stop: int                      # api.PARTITION_STOP
+    arrays: api.OctreePartition    # the call's arrays (leaf_order / leaf_tree: into tree.leaf_table())
+
+
+def partition_from_arrays(tree: Octree, branch_key, leaf_key, rows, P: api.OctreePartition) -> Partition:
+    """The host half of partition(): the subtrees as Octree objects in ONE pass over hpmvs_octree_partition's arrays P for the
+    key arrays it was given (rows[i]: what `tree` keeps for leaf_key[i])."""
+    n = P.n_trees
+    trees = []
+    for t in range(n):
+        sub = Octree(P.root_cell[t, :3], P.root_cell[t, 3], tree.root_level + key_depth(int(P.root_key[t])))
+        trees.append(sub)
+    for j in np.nonzero(P.branch_tree >= 0)[0]:
+        trees[P.branch_tree[j]].branches.add(int(P.branch_sub_key[j]))
+    queues = [[] for _ in range(n)]
+    for i in P.leaf_order:                                     # Leaf_iterator order: initFromTree's pushes, tree by tree
+        t = P.leaf_tree[i]
+        if t < 0:
+            continue
+        key = int(P.leaf_sub_key[i])
+        trees[t].leaves[key] = rows[i]
+        trees[t]._count(key, +1)
+        queues[t].append((trees[t].node_level(key) * 10, key))
+    orphans = np.asarray(leaf_key, np.uint64)[P.leaf_tree < 0]
+    return Partition(trees, P.root_key[:n].copy(), orphans, queues, P.histogram.copy(), P.stop, P)
+
+
+def partition(scene: api.Scene, tree: Octree, min_trees: int = 100, min_split_leaves: int = 100) -> Partition:
+    """getSubTrees(patchTree_, subTrees, FLAGS_subtrees) of the reference's main, and the initFromTree that seeds each
+    CellProcessor's queue, as ONE hpmvs_octree_partition: the subtrees in the reference's list order (the order route_border
+    takes), re-rooted with root_level = the depth of the cut plus tree.root_level, the rows of `tree` carried over; they can be
+    handed to route_border and extend_level_tree as they are.  min_split_leaves: the reference's 100.  `tree` is not changed.
+    Leaves in no subtree (Partition.orphans) are reference behaviour: they stay in the tree, and nothing extends them."""
+    bk = tree.branch_keys()
+    lk, rows, _, _ = tree.leaf_table()
+    P = api.octree_partition(scene, tree.root_center, tree.root_width, bk, lk, min_trees, min_split_leaves)
+    return partition_from_arrays(tree, bk, lk, rows, P)

@@ -756,6 +756,38 @@ bool Scene::octreeRoute(const std::vector<float>& roots, const std::vector<float
     }
     return true;
 }
+bool Scene::octreePartition(const OctreeIndex& tree, int minTrees, OctreePartition& out, int minSplitLeaves) const {
+    hpmvs_scene* dev = deviceScene();
+    if (!dev) return false;
+    hpmvs_octree_index t;
+    for (int k = 0; k < 3; k++) t.root_center[k] = tree.rootCenter[k];
+    t.root_width = tree.rootWidth;
+    t.n_branches = (int32_t)tree.branchKeys.size(); t.n_leaves = (int32_t)tree.leafKeys.size();
+    t.branch_key = tree.branchKeys.data(); t.leaf_key = tree.leafKeys.data();
+    if (minTrees > HPMVS_MAX_SUBTREES) { std::cerr << "hpmvs: octreePartition: minTrees exceeds HPMVS_MAX_SUBTREES" << std::endl; return false; }
+    const size_t cap = (size_t)(minTrees + 6 > 8 ? minTrees + 6 : 8);   // the list cannot end longer
+    const size_t nb = tree.branchKeys.size(), nl = tree.leafKeys.size();
+    std::vector<uint64_t> rootKey(cap), leafSubKey(nl), branchSubKey(nb);
+    std::vector<float> rootCell(4 * cap);
+    std::vector<int32_t> treeFirst(cap), treeLeaves(cap), leafOrder(nl), leafTree(nl), branchTree(nb);
+    hpmvs_octree_partition_info info;
+    if (hpmvs_octree_partition(dev, &t, minTrees, minSplitLeaves, &info, rootKey.data(), rootCell.data(), treeFirst.data(), treeLeaves.data(),
+                               leafOrder.data(), leafTree.data(), leafSubKey.data(), branchTree.data(), branchSubKey.data(), 0,
+                               nullptr) != HPMVS_OK) {
+        std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl;
+        return false;
+    }
+    const size_t n = (size_t)info.n_trees;
+    out.nTrees = info.n_trees; out.nOrphans = info.n_orphans; out.nSplits = info.n_splits; out.stop = info.stop;
+    out.histogram.assign(info.histogram, info.histogram + HPMVS_MAX_TREE_DEPTH + 1);
+    out.rootKey.assign(rootKey.begin(), rootKey.begin() + n);
+    out.rootCell.assign(rootCell.begin(), rootCell.begin() + 4 * n);
+    out.treeFirst.assign(treeFirst.begin(), treeFirst.begin() + n);
+    out.treeLeaves.assign(treeLeaves.begin(), treeLeaves.begin() + n);
+    out.leafOrder.swap(leafOrder); out.leafTree.swap(leafTree); out.leafSubKey.swap(leafSubKey);
+    out.branchTree.swap(branchTree); out.branchSubKey.swap(branchSubKey);
+    return true;
+}
 bool Scene::levelSupport(const Patch3d* const* patches, size_t n, int minLevel, std::vector<int>& support) const {
     support.assign(n, 0);
     hpmvs_scene* dev = deviceScene();

@@ -27,6 +27,19 @@ struct OctreeIndex {
     std::vector<uint64_t> branchKeys;
     std::vector<uint64_t> leafKeys;
 };
+// The split of a DynOctTree into subtrees (include/hpmvs_amd.h: hpmvs_octree_partition); the roots' vectors hold nTrees entries.
+struct OctreePartition {
+    int nTrees, nOrphans, nSplits, stop;   // stop 0: the root alone; 1: the list reached minTrees; 2: the largest subtree is too small
+    std::vector<int32_t> histogram;        // [22] cellHistogram: nonempty leaves by depth below the root
+    std::vector<uint64_t> rootKey;         // the subtree roots in the reference's list order
+    std::vector<float> rootCell;           // [nTrees][4] c_, width_
+    std::vector<int32_t> treeFirst, treeLeaves;   // subtree k's leaves: leafOrder[treeFirst[k] .. treeFirst[k] + treeLeaves[k] - 1]
+    std::vector<int32_t> leafOrder;        // [leaves] indices into OctreeIndex::leafKeys in Leaf_iterator order
+    std::vector<int32_t> leafTree;         // [leaves] -1: an orphan
+    std::vector<uint64_t> leafSubKey;      // [leaves] the key re-based on the subtree's root, 0 for an orphan
+    std::vector<int32_t> branchTree;       // [branches] -1: a root or a branch above the roots
+    std::vector<uint64_t> branchSubKey;    // [branches]
+};
 
 class Scene {
 public:
@@ -119,6 +132,13 @@ public:
     bool octreeInsert(const OctreeIndex& tree, const std::vector<float>& points /*[n][3]*/, const std::vector<float>& addWidth /*[n]*/,
                       OctreeInsertion& out) const;
     bool octreeRoute(const std::vector<float>& roots /*[t][4]*/, const std::vector<float>& points /*[n][3]*/, std::vector<int32_t>& out) const;
+    // getSubTrees(scene.patchTree_, subTrees, FLAGS_subtrees) of the reference's main (src/main.cpp:50-96) and
+    // DynOctTree::cellHistogram as ONE batched GPU call (hpmvs_octree_partition): the subtree roots in the reference's list order
+    // (the order octreeRoute takes), every key's subtree and its key re-based on that root, and the Leaf_iterator order that
+    // initFromTree seeds each CellProcessor's queue in.  minSplitLeaves is the reference's constant 100.  Nonempty leaves in no
+    // subtree (nOrphans) are reference behaviour: they stay in the tree, nothing extends them.  False (and
+    // hpmvs_last_error) when the keys are no tree, minTrees > HPMVS_MAX_SUBTREES or minSplitLeaves < 1.
+    bool octreePartition(const OctreeIndex& tree, int minTrees, OctreePartition& out, int minSplitLeaves = 100) const;
     std::map<std::string, int> dict_;
     std::vector<Camera> cameras_;
     std::vector<Image> images_;

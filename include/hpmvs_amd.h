@@ -42,6 +42,7 @@
  *   hpmvs_octree_locate_batch <- the tree look-ups of CellProcessor::extend, src/hpmvs/CellProcessor.cpp:122-125, 147-154.
  *   hpmvs_octree_route_batch, <- CellProcessor::distributeBorderCell and ::processBorderCellQueue,
  *   hpmvs_octree_insert_batch    src/hpmvs/CellProcessor.cpp:487-540 (the root search and the addConditional loop).
+ *   hpmvs_octree_partition    <- getSubTrees, src/main.cpp:50-96, and DynOctTree::cellHistogram, doctree.h:493-511.
  *   hpmvs_camera_from_nvm    <- Camera::init, src/hpmvs/Camera.cpp:34-81.
  */
 #ifndef HPMVS_AMD_H
@@ -481,6 +482,53 @@ int hpmvs_octree_insert_batch(const hpmvs_scene *s, const hpmvs_octree_index *t,
                               int32_t *blocker /*[n], nullable*/, int on_device, void *stream);
 int hpmvs_octree_route_batch(const hpmvs_scene *s, int n_trees, const float *roots /*[n_trees][4]: c_, width_*/, int n,
                              const float *points /*[n][3]*/, int32_t *tree /*[n]*/, int on_device, void *stream);
+
+/* The split of the octree into subtrees that main() makes between initPatches and the first level (reference src/main.cpp:50-96,
+ * getSubTrees(scene.patchTree_, subTrees, FLAGS_subtrees); DynOctTree::getSubTrees, doctree.h:513-523; Branch::nrLeafs,
+ * doctree.h:236-247), and DynOctTree::cellHistogram (doctree.h:493-511), for a tree given as path keys:
+ *   min_trees < 2      the list is the root alone (root_key[0] = 1): every key lies in tree 0 under its own key, no orphans
+ *   else               a first split, whatever the tree holds: the BRANCH children of the root in child order 0 .. 7, empty
+ *                      ones included; a child that is a LEAF enters no subtree.  Then, while the list is shorter than
+ *                      min_trees: nrLeafs (NONEMPTY leaves) of every entry, the FIRST entry with the largest count; the loop
+ *                      ends when that count is below min_split_leaves (also on an empty list); else that entry's BRANCH children
+ *                      in child order come first in the new list, then all other entries in their old order.
+ * min_split_leaves is the reference's constant 100 (main.cpp:78); smaller values let small trees go through the loop.
+ *   info               n_trees; n_orphans: nonempty leaves in no subtree (they stay in the tree and in its PLY files, but no
+ *                      CellProcessor ever sees them: reference behaviour); n_splits; stop; histogram
+ *   root_key[k]        the roots in the reference's list order -- the order distributeBorderCell searches and
+ *                      hpmvs_octree_route_batch takes; root_cell[k]: c_ x y z, width_ by the chain Cell(parent, idx).  A
+ *                      subtree's rootLevel_ is the depth of its root_key
+ *   leaf_order         indices into t->leaf_key in Leaf_iterator order (children 0 .. 7, depth first); the nonempty leaves of
+ *                      subtree k are leaf_order[tree_first[k] .. tree_first[k] + tree_leaves[k] - 1], in the order initFromTree
+ *                      (CellProcessor.cpp:422-455) pushes them
+ *   leaf_tree[i]       the subtree whose root is a PROPER ancestor of t->leaf_key[i], -1 for an orphan; leaf_sub_key[i]: the key
+ *                      re-based on that root (the sentinel, then the bits below the root's depth), 0 where the tree is -1
+ *   branch_tree[j],    the same for t->branch_key[j]: a root itself and the branches above the roots are -1 / 0
+ *   branch_sub_key[j]
+ * cap = max(8, min_trees + 6): the list cannot end longer; entries from n_trees on come back 0.  Every array output is nullable;
+ * info is always a host structure.  The key arrays may be in ANY order, as for hpmvs_octree_locate_batch, and are checked as
+ * there: HPMVS_ERR_ARG before any output is written for keys that are no tree, a root that is not finite or has no positive
+ * width, min_trees > HPMVS_MAX_SUBTREES and min_split_leaves < 1.  The empty tree is valid (min_trees >= 2: no subtree at all).
+ * The list is cut by ONE wavefront with the list in LDS (kernel_octree_partition.hip); scratch of 24 n_leaves bytes plus the
+ * sort's and at most 192 KB for the roots is the call's own.  Host or device pointers as for the other octree calls; the call is
+ * host-synchronous in both forms, and the only read-back besides the table's verdict is the info record. */
+#define HPMVS_MAX_SUBTREES 4096
+typedef struct {
+    int32_t n_trees;
+    int32_t n_orphans;     /* nonempty leaves in no subtree */
+    int32_t n_splits;      /* iterations of the while loop that cut a subtree */
+    int32_t stop;          /* 0: min_trees < 2, the root alone; 1: the list reached min_trees; 2: the largest subtree is below
+                              min_split_leaves (or the list is empty) */
+    int32_t histogram[HPMVS_MAX_TREE_DEPTH + 1];   /* cellHistogram: nonempty leaves by depth below t's root */
+} hpmvs_octree_partition_info;
+int hpmvs_octree_partition(const hpmvs_scene *s, const hpmvs_octree_index *t, int min_trees, int min_split_leaves,
+                           hpmvs_octree_partition_info *info,
+                           uint64_t *root_key      /*[cap]*/,  float *root_cell /*[cap][4]: c_, width_*/,
+                           int32_t *tree_first     /*[cap]*/,  int32_t *tree_leaves /*[cap]*/,
+                           int32_t *leaf_order     /*[n_leaves]: indices into t->leaf_key in Leaf_iterator order*/,
+                           int32_t *leaf_tree      /*[n_leaves]*/,   uint64_t *leaf_sub_key   /*[n_leaves]*/,
+                           int32_t *branch_tree    /*[n_branches]*/, uint64_t *branch_sub_key /*[n_branches]*/,
+                           int on_device, void *stream);
 
 /* Host-pointer calls and pinned memory.  An array of a host-pointer call (on_device = 0) that lies in pinned host memory
  * mapped into the GPU's address space -- hipHostMalloc / hipHostRegister, torch's pin_memory(), hpmvs_host_alloc below --
