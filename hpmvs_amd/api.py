@@ -57,6 +57,11 @@ class OctreeIndex(C.Structure):
                 ("branch_key", C.c_void_p), ("leaf_key", C.c_void_p)]
 
 
+class ExtendTreeKeysStruct(C.Structure):
+    _fields_ = [("skip", C.c_void_p), ("pre_inside", C.c_void_p), ("pre_key", C.c_void_p), ("border", C.c_void_p),
+                ("post_key", C.c_void_p)]
+
+
 class OctreePartitionInfo(C.Structure):
     _fields_ = [("n_trees", C.c_int32), ("n_orphans", C.c_int32), ("n_splits", C.c_int32), ("stop", C.c_int32),
                 ("histogram", C.c_int32 * 22)]
@@ -80,7 +85,7 @@ EXPORTS = [
     "hpmvs_host_alloc", "hpmvs_host_free", "hpmvs_last_staging",
     "hpmvs_undistort", "hpmvs_undistort_map", "hpmvs_scene_set_view_distorted",
     "hpmvs_regularize_batch", "hpmvs_filter_batch", "hpmvs_seed_tree_batch", "hpmvs_octree_locate_batch",
-    "hpmvs_octree_insert_batch", "hpmvs_octree_route_batch", "hpmvs_octree_partition",
+    "hpmvs_octree_insert_batch", "hpmvs_octree_route_batch", "hpmvs_octree_partition", "hpmvs_extend_tree_batch",
     "hpmvs_scene_center", "hpmvs_init_patches_sphere_batch",
     "hpmvs_jpeg_info", "hpmvs_jpeg_decode", "hpmvs_scene_set_view_jpeg", "hpmvs_jpeg_decode_timed",
 ]
@@ -156,6 +161,8 @@ def lib():
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.hpmvs_octree_locate_batch.argtypes = [C.c_void_p, C.POINTER(OctreeIndex), C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
     L.hpmvs_octree_insert_batch.argtypes = [C.c_void_p, C.POINTER(OctreeIndex), C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+    L.hpmvs_extend_tree_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(OctreeIndex), C.POINTER(PatchBatch), C.c_float,
+                                          C.POINTER(PatchBatch), C.POINTER(ExtendTreeKeysStruct), C.c_int, C.c_void_p]
     L.hpmvs_octree_route_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.hpmvs_octree_partition.argtypes = [C.c_void_p, C.POINTER(OctreeIndex), C.c_int, C.c_int, C.POINTER(OctreePartitionInfo)] + \
         [C.c_void_p] * 9 + [C.c_int, C.c_void_p]
@@ -664,6 +671,45 @@ def octree_locate_batch(scene: Scene, root_center, root_width, branch_key, leaf_
     _chk(lib().hpmvs_octree_locate_batch(scene.h, C.byref(t), n, pts.ctypes.data, None if aw is None else aw.ctypes.data,
                                          *[getattr(r, k).ctypes.data for k in OCTREE_OUTPUTS], 0, None))
     return r
+
+
+EXTEND_TREE_KEYS = ("skip", "pre_inside", "pre_key", "border", "post_key")
+
+
+@dataclass
+class ExtendTreeKeys:
+    skip: np.ndarray               # [6 n] uint8 pre-gated by the tree (CellProcessor.cpp:124): built, not refined, stage 20
+    pre_inside: np.ndarray         # [6 n] uint8 root.contains(centre before optimize)
+    pre_key: np.ndarray            # [6 n] uint64 inside: addConditional's target leaf (0: refused); outside: 0
+    border: np.ndarray             # [6 n] uint8 refined (ok != 0) and outside the root (:147)
+    post_key: np.ndarray           # [6 n] uint64 refined and inside: the target leaf (0: refused); else 0
+
+    def c_struct(self) -> ExtendTreeKeysStruct:
+        k = ExtendTreeKeysStruct()
+        for name in EXTEND_TREE_KEYS:
+            setattr(k, name, _ptr(getattr(self, name)))
+        return k
+
+
+def extend_tree_batch(scene: Scene, parents: Batch, width, root_center, root_width, branch_key, leaf_key,
+                      options: Options | None = None):
+    """The candidate steps of one extend level against the real octree as ONE hpmvs_extend_tree_batch (include/hpmvs_amd.h):
+    the six candidates of every parent built, looked up in the tree given as path keys, refined unless the tree pre-gates them,
+    gated, and the refined ones looked up again.  `width`: the leaf width of the level, an exact level width of the tree
+    (HpmvsError otherwise, as when the keys are no tree).  Returns (out: Batch of 6 n candidates, ExtendTreeKeys)."""
+    o = options or default_options()
+    bk = np.ascontiguousarray(branch_key, dtype=np.uint64).reshape(-1)
+    lk = np.ascontiguousarray(leaf_key, dtype=np.uint64).reshape(-1)
+    t = _octree_index(root_center, root_width, bk, lk)
+    N = 6 * parents.n
+    out = Batch(np.zeros((N, 4), np.float32), np.zeros((N, 4), np.float32), np.zeros(N, np.float32), np.zeros(N, np.int32),
+                np.full((N, parents.max_images), -1, np.int32))
+    keys = ExtendTreeKeys(np.zeros(N, np.uint8), np.zeros(N, np.uint8), np.zeros(N, np.uint64), np.zeros(N, np.uint8),
+                          np.zeros(N, np.uint64))
+    pb, ob, kb = parents.c_struct(), out.c_struct(), keys.c_struct()
+    _chk(lib().hpmvs_extend_tree_batch(scene.h, C.byref(o), C.byref(t), C.byref(pb), float(np.float32(width)), C.byref(ob),
+                                       C.byref(kb), 0, None))
+    return out, keys
 
 
 @dataclass

@@ -2061,9 +2061,10 @@ int hpmvs_seed_tree_batch(hpmvs_scene* s, hpmvs_patch_batch* b, int patch_init_m
 // look-up table lives in a launch workspace: [1 KB counter block, untouched] [verdict] [keys] [values]; the arrays go through
 // Call.  The verdict of the check kernel is read back before the kernel that uses the table is enqueued: a refused table
 // writes nothing.
-struct OctreeLayout { size_t slots, o_hdr, o_keys, o_vals; };
+struct OctreeLayout { size_t slots, o_hdr, o_keys, o_vals, bytes; };
+// own: the table goes into a buffer of the call's own (L->bytes of it, no counter block ahead of the verdict) instead of a workspace
 static int octree_index_check(const hpmvs_scene* s, const hpmvs_octree_index* t, int n, const float* points, const std::string& who,
-                              OctreeLayout* L) {
+                              OctreeLayout* L, bool own = false) {
     if (hpmvs_device_count() <= 0) return fail(HPMVS_ERR_NODEVICE, who + ": no HIP device visible");
     if (!s || !t) return fail(HPMVS_ERR_ARG, who + ": null scene / octree");
     if (!s->committed) return fail(HPMVS_ERR_STATE, who + ": scene not committed");
@@ -2076,13 +2077,15 @@ static int octree_index_check(const hpmvs_scene* s, const hpmvs_octree_index* t,
     const size_t nk = (size_t)t->n_branches + (size_t)t->n_leaves;
     if (nk > ((size_t)1 << 29)) return fail(HPMVS_ERR_ARG, who + ": the octree does not fit the launch workspace");
     L->slots = octree::table_slots(nk);
-    L->o_hdr = kQueueSlotBytes;
+    L->o_hdr = own ? 0 : kQueueSlotBytes;
     L->o_keys = reg_align(L->o_hdr + 16);
     L->o_vals = reg_align(L->o_keys + 8 * L->slots);
-    if (reg_align(L->o_vals + 4 * L->slots) > s->ws_bytes) return fail(HPMVS_ERR_ARG, who + ": the octree does not fit the launch workspace");
+    L->bytes = reg_align(L->o_vals + 4 * L->slots);
+    if (!own && L->bytes > s->ws_bytes) return fail(HPMVS_ERR_ARG, who + ": the octree does not fit the launch workspace");
     return HPMVS_OK;
 }
-// builds and checks the table in the workspace w (the caller holds it); host-synchronous up to the verdict
+// builds and checks the table in the buffer w it is given, laid out by L (a workspace the caller holds, or memory of the call's
+// own); host-synchronous up to the verdict
 static int octree_table_build(const hpmvs_octree_index* t, const unsigned long long* dbk, const unsigned long long* dlk, const OctreeLayout& L,
                               char* w, hipStream_t st, const std::string& who) {
     int32_t* verdict = (int32_t*)(w + L.o_hdr);
@@ -2138,6 +2141,73 @@ int hpmvs_octree_locate_batch(const hpmvs_scene* s, const hpmvs_octree_index* t,
     launch_octree_locate(root, (unsigned long long*)(w + L.o_keys), (int32_t*)(w + L.o_vals), (uint32_t)L.slots, n, dpts, daw, out, st);
     HIPCHK(hipGetLastError());
     return c.finish();
+}
+// One extend level's candidate steps against the real tree (CellProcessor.cpp:84-178; kernel_extend_tree.hip): expand_init, the pre
+// look-up, the refinement, the gates, the post look-up.  The table is built once and must outlive the refinement launch, which
+// takes a workspace itself (on one stream: the very one a look-up call would hold), so it lives in memory of this call's own.
+// Two Calls: the keys and the table first, so that the table's verdict is in before a batch array is declared -- an output in
+// pinned host memory is cleared in place by begin().
+int hpmvs_extend_tree_batch(const hpmvs_scene* s, const hpmvs_options* o, const hpmvs_octree_index* t, const hpmvs_patch_batch* parents,
+                            float width, hpmvs_patch_batch* out, const hpmvs_extend_tree_keys* keys, int on_device, void* stream) {
+    const char* who = "extend_tree_batch";
+    int rc = check_batch(s, o, parents);
+    if (rc) return rc;
+    if ((rc = check_batch_shape(s, o, out))) return rc;
+    OctreeLayout L;
+    if ((rc = octree_index_check(s, t, 0, nullptr, who, &L, true))) return rc;
+    const int N = expand_fanout(HPMVS_EXPAND_EXTEND);
+    if (out->n != parents->n * N) return fail(HPMVS_ERR_ARG, "extend_tree_batch: out->n must be 6 * parents->n");
+    if (out->max_images != parents->max_images) return fail(HPMVS_ERR_ARG, "extend_tree_batch: max_images mismatch");
+    if (parents->n > 0 && (!out->center || !out->normal || !out->scale || !out->n_images || !out->images || !out->ok))
+        return fail(HPMVS_ERR_ARG, "extend_tree_batch: missing array");
+    if (!std::isfinite(width) || octree::level_depth(t->root_width, width) < 0)
+        return fail(HPMVS_ERR_ARG, "extend_tree_batch: width is not the width of a level of the tree");
+    const size_t nb = (size_t)t->n_branches, nl = (size_t)t->n_leaves, n = (size_t)parents->n, nc = n * N;
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    Call ck(s, on_device, st);
+    const unsigned long long* dbk = (const unsigned long long*)ck.in(t->branch_key, nb);
+    const unsigned long long* dlk = (const unsigned long long*)ck.in(t->leaf_key, nl);
+    // the table, then cell_width of expand_init / expand_gate: `width` for every parent (mode 0 reads no cell_center)
+    char* w = (char*)ck.scratch(L.bytes + sizeof(float) * n);
+    if (!w) return ck.error();
+    float* dcw = (float*)(w + L.bytes);
+    if ((rc = ck.begin(st))) return rc;
+    if ((rc = octree_table_build(t, dbk, dlk, L, w, st, who))) return rc;
+    if (n == 0) return ck.finish();
+    Call c(s, on_device, st);
+    const DevBatch P = c.batch(parents, Call::kRead), D = c.batch(out, Call::kCreate);
+    ExtendTreeOut K;
+    memset(&K, 0, sizeof(K));
+    if (keys) {   // (the two kernels write every entry of what they are given: no zero fill)
+        K.skip = c.arr(keys->skip, nc, Call::kCopyBack);
+        K.pre_inside = c.arr(keys->pre_inside, nc, Call::kCopyBack);
+        K.pre_key = (unsigned long long*)c.arr(keys->pre_key, nc, Call::kCopyBack);
+        K.border = c.arr(keys->border, nc, Call::kCopyBack);
+        K.post_key = (unsigned long long*)c.arr(keys->post_key, nc, Call::kCopyBack);
+    }
+    if ((rc = c.begin(st))) return rc;
+    const DevOptions d = make_dev_options(o);
+    const float root[4] = {t->root_center[0], t->root_center[1], t->root_center[2], t->root_width};
+    const unsigned long long* tk = (const unsigned long long*)(w + L.o_keys);
+    const int32_t* tv = (const int32_t*)(w + L.o_vals);
+    uint32_t wbits;
+    memcpy(&wbits, &width, 4);
+    {
+        std::lock_guard<std::recursive_mutex> lk(s->mu);
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)dcw, (int)wbits, n, st));
+        launch_expand_init(dev_scene(s), HPMVS_EXPAND_EXTEND, parents->n, P, nullptr, dcw, nullptr, D, st);
+        HIPCHK(hipGetLastError());
+        launch_extend_tree_pre(root, tk, tv, (uint32_t)L.slots, (int)nc, width, D, K, st);
+        HIPCHK(hipGetLastError());
+        if ((rc = enqueue_refinement(s, d, D, st))) return rc;
+        launch_expand_gate(HPMVS_EXPAND_EXTEND, parents->n, P, nullptr, dcw, D, st);
+        HIPCHK(hipGetLastError());
+        launch_extend_tree_post(root, tk, tv, (uint32_t)L.slots, (int)nc, width, D, K, st);
+        HIPCHK(hipGetLastError());
+    }
+    if ((rc = c.finish())) return rc;
+    return ck.finish();   // (waits in both forms: the table is freed when this call returns)
 }
 // CellProcessor::processBorderCellQueue's insertion loop (CellProcessor.cpp:500-531): addConditional(points[i], add_width[i]) for
 // i = 0 .. n - 1 IN THAT ORDER against the tree t, which stays the caller's (kernel_octree_insert.hip: static kernel, stable sort by

@@ -138,6 +138,19 @@ void launch_octree_build(const unsigned long long* branch_key, int nb, const uns
 void launch_octree_locate(const float* root, const unsigned long long* keys, const int32_t* vals, uint32_t slots, int n,
                           const float* points, const float* add_width, const OctreeLocateOut& out, hipStream_t st);
 
+// the look-ups of CellProcessor::extend around the refinement of one expansion call (kernel_extend_tree.hip, include/hpmvs_amd.h:
+// hpmvs_extend_tree_batch), against the table launch_octree_build made.  n: candidates (out.n); `width` the level's leaf width.
+// The pre kernel goes between launch_expand_init and the refinement (it reads out.center and sets out.n_images of a skipped
+// candidate to -20), the post kernel behind launch_expand_gate (it reads out.center / out.ok).  Every output is nullable; what is
+// given is written in every entry.
+struct ExtendTreeOut {
+    uint8_t* skip; uint8_t* pre_inside; unsigned long long* pre_key; uint8_t* border; unsigned long long* post_key;
+};
+void launch_extend_tree_pre(const float* root, const unsigned long long* keys, const int32_t* vals, uint32_t slots, int n, float width,
+                            const DevBatch& out, const ExtendTreeOut& k, hipStream_t st);
+void launch_extend_tree_post(const float* root, const unsigned long long* keys, const int32_t* vals, uint32_t slots, int n, float width,
+                             const DevBatch& out, const ExtendTreeOut& k, hipStream_t st);
+
 // a round's border patches (kernel_octree_insert.hip, include/hpmvs_amd.h: hpmvs_octree_route_batch, hpmvs_octree_insert_batch).
 // launch_octree_insert reads the table launch_octree_build made and enqueues static kernel, sort and replay on st; != 0: the
 // rocPRIM call failed.  Every entry of every output is written (blocker is nullable).  roots: [n_trees][4] c_, width_ on the device.

@@ -149,6 +149,47 @@ HPMVS_OT_FN uint64_t add_target(const Located& leaf, const float* p, float add_w
     return key;
 }
 
+// ---- the two look-ups CellProcessor::extend makes per candidate (CellProcessor.cpp:122-125 before optimize, :147-154 after),
+// against the tree as the level finds it.  `width` is the level's leaf width, add_width = extend_add_width(width).
+struct ExtendPre {
+    bool inside;        // getRoot()->contains(p)
+    bool skip;          // inside, and the leaf at p is nonempty or narrower than `width` (:124): the candidate is never refined
+    uint64_t pre_key;   // inside: addConditional's target at add_width, 0 where it refuses; outside: 0
+};
+HPMVS_OT_FN ExtendPre extend_pre(const Cell& root, const Table& t, const float* p, float width, float add_width) {
+    ExtendPre r;
+    r.inside = contains(root, p);
+    r.skip = false;
+    r.pre_key = 0;
+    if (!r.inside) return r;
+    const Located l = locate(root, t, p);
+    r.skip = l.index != kAbsent || l.cell.w < width;
+    r.pre_key = add_target(l, p, add_width);
+    return r;
+}
+struct ExtendPost {
+    bool border;        // !getRoot()->contains(p) (:147): handed to borderCellFn_
+    uint64_t post_key;  // not border: addConditional's target, 0 where it refuses; border: 0
+};
+HPMVS_OT_FN ExtendPost extend_post(const Cell& root, const Table& t, const float* p, float add_width) {
+    ExtendPost r;
+    r.border = !contains(root, p);
+    r.post_key = r.border ? 0 : add_target(locate(root, t, p), p, add_width);
+    return r;
+}
+// cell->width_ * 0.9: a double product, narrowed by addConditional's float parameter
+HPMVS_OT_FN float extend_add_width(float width) { return (float)((double)width * 0.9); }
+// the depth d >= 1 whose cells have width_ == width under the root (the chain Cell(parent, idx) makes), -1 when there is none
+HPMVS_OT_FN int level_depth(float root_width, float width) {
+    float w = root_width;
+    int d = 0;
+    while (w > width && d < kMaxDepth) {
+        w = (float)((double)w / 2.0);
+        d++;
+    }
+    return (w == width && d >= 1) ? d : -1;
+}
+
 // ---- a round's border patches, inserted in queue order (CellProcessor::processBorderCellQueue, CellProcessor.cpp:500-531): a
 // loop of addConditional(p_i, a_i) with a width of its own per patch, so that an earlier insertion changes what a later one
 // finds.  Against the tree as the round finds it:

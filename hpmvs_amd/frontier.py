@@ -42,7 +42,7 @@ Stage codes as in hpmvs_expand_batch, plus 20 = leaf already taken (no refinemen
 viewBlockTest / pixelFreeTests threshold, 26 = addConditional found the refined patch's leaf taken.
 
 `extend_level_tree` / `filter_extend_level_tree` are the same walk against the REAL octree (`Octree`: branch keys + nonempty leaf
-keys, looked up on the device by hpmvs_octree_locate_batch): the pre-gate sees leaves of any depth, addConditional splits, and a
+keys, looked up on the device inside ONE hpmvs_extend_tree_batch per level): the pre-gate sees leaves of any depth, addConditional splits, and a
 candidate that ends outside the tree's root is a border candidate, stage 27.
 """
 from __future__ import annotations
@@ -134,22 +134,27 @@ class _GridKeys:
     def post(self, center, refined):
         return [self.key(center[t], self.width) if refined[t] else None for t in range(len(center))], None
 
+    def candidates(self, scene, parents, width, o):
+        """Two hpmvs_expand_batch calls: everything skipped (constructed only) for the centres before optimize -> their cells,
+        then the refinement of those whose cell is free when the level starts."""
+        n = parents.n
+        N = 6 * n
+        cc = np.zeros((n, 3), np.float32)
+        widths = np.full(n, width, np.float32)
+        pre = api.expand_batch(scene, api.EXPAND_EXTEND, parents, cc, widths, np.ones(N, np.uint8), options=o)
+        pre_key, skip = self.pre(pre.center)
+        out = api.expand_batch(scene, api.EXPAND_EXTEND, parents, cc, widths, skip, options=o)
+        refined = (out.stage == 0) & (skip == 0)
+        post_key, border = self.post(out.center, refined)
+        return out, pre_key, post_key, skip, refined, border
+
 
 def _candidates(scene, parents, width, keys, o):
-    """The candidate steps of a level: the six candidates of every parent before optimize and their leaves (`pre_key`), ONE
-    hpmvs_expand_batch over those whose leaf is free when the level starts, the refined ones' leaves (`post_key`) and, on the
-    real tree, the refined ones that left the root (`border`, else None).  `keys`: _GridKeys or _TreeKeys."""
-    n = parents.n
-    N = 6 * n
-    cc = np.zeros((n, 3), np.float32)
-    widths = np.full(n, width, np.float32)
-    # the candidates before optimize (everything skipped: constructed only) -> their leaves
-    pre = api.expand_batch(scene, api.EXPAND_EXTEND, parents, cc, widths, np.ones(N, np.uint8), options=o)
-    pre_key, skip = keys.pre(pre.center)
-    out = api.expand_batch(scene, api.EXPAND_EXTEND, parents, cc, widths, skip, options=o)
-    refined = (out.stage == 0) & (skip == 0)
-    post_key, border = keys.post(out.center, refined)
-    return out, pre_key, post_key, skip, refined, border
+    """The candidate steps of a level, the keys object's business as a whole: the six candidates of every parent before optimize
+    and their leaves (`pre_key`), the refinement of those whose leaf is free when the level starts (`skip`: the others), the
+    refined ones' leaves (`post_key`) and, on the real tree, the refined ones that left the root (`border`, else None).
+    `keys`: _GridKeys (two hpmvs_expand_batch calls) or _TreeKeys (ONE hpmvs_extend_tree_batch)."""
+    return keys.candidates(scene, parents, width, o)
 
 
 def _walk(queue, pre_key, post_key, refined, n_images, reads, writes, ev_cells, occupied, min_images, stage, counts, gates, apply,
@@ -832,15 +837,15 @@ REFUSED = 0   # no path key: what addConditional's refusal maps to; in `occupied
 
 
 class _TreeKeys:
-    """The candidates' leaves in the real tree: two hpmvs_octree_locate_batch calls per level.  Within a level every parent has
-    the same width w, an exact level width of the tree, so addConditional(0.9 w) ends at the depth d* of width w: whatever the
-    tree as the level finds it decides is static (a nonempty leaf, or structure finer than w: never refined / REFUSED), and
-    whatever the level's own insertions decide is equality of the d*-prefix of the point -- the walk's pre_key / post_key."""
+    """The candidates' leaves in the real tree: ONE hpmvs_extend_tree_batch per level builds, looks up, refines and looks up
+    again.  Within a level every parent has the same width w, an exact level width of the tree, so addConditional(0.9 w) ends at
+    the depth d* of width w: whatever the tree as the level finds it decides is static (a nonempty leaf, or structure finer than
+    w: never refined / REFUSED), and whatever the level's own insertions decide is equality of the d*-prefix of the point -- the
+    walk's pre_key / post_key."""
 
     def __init__(self, scene, tree: Octree, width):
         self.scene, self.tree = scene, tree
         self.width = np.float32(width)
-        self.add_width = np.float32(float(self.width) * 0.9)     # cell->width_ * 0.9, narrowed by addConditional's float parameter
         w, d = tree.root_width, 0
         while w > self.width and d < MAX_TREE_DEPTH:
             w = np.float32(float(w) / 2.0); d += 1
@@ -848,22 +853,16 @@ class _TreeKeys:
             raise ValueError("extend_level_tree: `width` is not the width of a level of the tree")
         self.index = (tree.branch_keys(), tree.leaf_table()[0])
 
-    def _locate(self, points):
+    def candidates(self, scene, parents, width, o):
         t = self.tree
-        return api.octree_locate_batch(self.scene, t.root_center, t.root_width, self.index[0], self.index[1], points, self.add_width)
-
-    def pre(self, center):
-        r = self._locate(center)
-        inside = r.inside != 0
-        skip = inside & ((r.leaf_index >= 0) | (r.leaf_width < self.width))            # CellProcessor.cpp:124
+        out, k = api.extend_tree_batch(scene, parents, self.width, t.root_center, t.root_width, self.index[0], self.index[1], options=o)
+        N = out.n
+        refined = (out.stage == 0) & (k.skip == 0)
+        border = refined & (k.border != 0)                                              # CellProcessor.cpp:147
         # an outside candidate is never pre-gated: a key that nothing else can hold
-        return [int(r.target_key[t]) if inside[t] else ("outside", t) for t in range(len(center))], skip.astype(np.uint8)
-
-    def post(self, center, refined):
-        r = self._locate(center)
-        border = refined & (r.inside == 0)                                              # CellProcessor.cpp:147
-        key = [None if not refined[t] else ("border", t) if border[t] else int(r.target_key[t]) for t in range(len(center))]
-        return key, border
+        pre_key = [int(k.pre_key[t]) if k.pre_inside[t] else ("outside", t) for t in range(N)]
+        post_key = [None if not refined[t] else ("border", t) if border[t] else int(k.post_key[t]) for t in range(N)]
+        return out, pre_key, post_key, k.skip, refined, border
 
 
 def _insert_accepted(tree: Octree, L: LevelResult, rows):
@@ -874,8 +873,8 @@ def _insert_accepted(tree: Octree, L: LevelResult, rows):
 def extend_level_tree(scene: api.Scene, parents: api.Batch, width: float, tree: Octree, margin: float = 1.0, abs_int: int = 0,
                       options=None, sequential: bool = True, events=None, event_cell=(), rows=None) -> LevelResult:
     """extend_level against the scheduler's real octree (or a subtree of it): CellProcessor::extend over `parents`, the leaves
-    of ONE node level (all of width `width`), in the scheduler's order.  The walk is extend_level's; the keys come from
-    hpmvs_octree_locate_batch (_TreeKeys).  Stage codes as extend_level's, where 20 is the pre-gate (a nonempty leaf of any
+    of ONE node level (all of width `width`), in the scheduler's order.  The walk is extend_level's; the candidates and their keys come
+    from ONE hpmvs_extend_tree_batch (_TreeKeys).  Stage codes as extend_level's, where 20 is the pre-gate (a nonempty leaf of any
     depth, or structure finer than `width`, inside the root), 26 addConditional's refusal, and 27 = BORDER: a candidate that
     passed every gate but lies outside tree's root.  Border candidates are returned in LevelResult.border (queue order) for the
     scheduler to route (processBorderCellQueue); they are not inserted and write no depths.  The accepted candidates are

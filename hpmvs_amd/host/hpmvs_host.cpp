@@ -895,16 +895,19 @@ inline bool for_write_cells(const RawFootprints& F, size_t i, Fn&& fn) {
 struct FlatSet {
     std::vector<uint64_t> t;
     size_t mask = 0, n = 0;
+    bool ones = false;   // the key of all ones (a depth-21 path key whose child bits are all set): k + 1 would be the free mark
     FlatSet() { t.assign(1024, 0); mask = 1023; }
     static inline size_t mix(uint64_t k) { k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33; return (size_t)k; }
-    void clear() { if (n) { if (t.size() > 4096 && 8 * n < t.size()) { t.assign(t.size() / 2, 0); mask = t.size() - 1; } else std::fill(t.begin(), t.end(), 0); n = 0; } }
-    bool empty() const { return n == 0; }
+    void clear() { ones = false; if (n) { if (t.size() > 4096 && 8 * n < t.size()) { t.assign(t.size() / 2, 0); mask = t.size() - 1; } else std::fill(t.begin(), t.end(), 0); n = 0; } }
+    bool empty() const { return n == 0 && !ones; }
     bool has(uint64_t k) const {
+        if (k == ~(uint64_t)0) return ones;
         if (!n) return false;
-        k += 1;   // (0 marks an empty slot; no key is all ones)
+        k += 1;   // (0 marks an empty slot; the key of all ones is kept beside the table)
         for (size_t i = mix(k) & mask;; i = (i + 1) & mask) { const uint64_t v = t[i]; if (v == k) return true; if (!v) return false; }
     }
     void add(uint64_t k) {
+        if (k == ~(uint64_t)0) { ones = true; return; }
         if (2 * (n + 1) > t.size()) grow();
         k += 1;
         for (size_t i = mix(k) & mask;; i = (i + 1) & mask) { if (t[i] == k) return; if (!t[i]) { t[i] = k; n++; return; } }
@@ -1423,7 +1426,22 @@ size_t PatchOptimizer::optimizeBatch(mo3d::Patch3d* const* patches, size_t n, ui
 int PatchOptimizer::expandBatch(ExpandMode mode, const mo3d::Patch3d* const* parents, const CellRef* cells, size_t n,
                                 const uint8_t* skip, std::vector<mo3d::Patch3d>& candidates,
                                 std::vector<uint8_t>& accepted) {
+    return expandCall(mode, parents, cells, n, skip, nullptr, 0.0f, nullptr, candidates, accepted);
+}
+
+int PatchOptimizer::expandTreeBatch(const mo3d::Patch3d* const* parents, size_t n, float width, const mo3d::OctreeIndex& tree,
+                                    std::vector<mo3d::Patch3d>& candidates, std::vector<uint8_t>& accepted, TreeKeys& keys) {
+    return expandCall(EXTEND, parents, nullptr, n, nullptr, &tree, width, &keys, candidates, accepted);
+}
+
+int PatchOptimizer::expandCall(ExpandMode mode, const mo3d::Patch3d* const* parents, const CellRef* cells, size_t n, const uint8_t* skip,
+                               const mo3d::OctreeIndex* tree, float width, TreeKeys* keys, std::vector<mo3d::Patch3d>& candidates,
+                               std::vector<uint8_t>& accepted) {
     const int N = (mode == EXTEND) ? 6 : 4;
+    if (keys) {
+        keys->skip.assign(n * N, 0); keys->preInside.assign(n * N, 0); keys->border.assign(n * N, 0);
+        keys->preKey.assign(n * N, 0); keys->postKey.assign(n * N, 0);
+    }
     candidates.clear();
     accepted.assign(n * N, 0);
     lastF_.assign(n * N, 0.0);
@@ -1444,8 +1462,8 @@ int PatchOptimizer::expandBatch(ExpandMode mode, const mo3d::Patch3d* const* par
         ps[i] = p.scale_3dx_;
         pnimg[i] = (int32_t)p.images_.size();
         for (size_t k = 0; k < p.images_.size() && k < (size_t)stride; k++) pimg[i * stride + k] = p.images_[k];
-        for (int k = 0; k < 3; k++) cc[3 * i + k] = cells[i].c[k];
-        cw[i] = cells[i].width;
+        for (int k = 0; k < 3; k++) cc[3 * i + k] = cells ? cells[i].c[k] : 0.0f;
+        cw[i] = cells ? cells[i].width : width;
     }
     PVec<float> center(4 * m, pin), normal(4 * m, pin), scale(m, pin), color(3 * m, pin), ncc(m, pin);
     PVec<int32_t> nimg(m, pin), images(m * stride, -1, pin), evals(m, pin);
@@ -1466,7 +1484,25 @@ int PatchOptimizer::expandBatch(ExpandMode mode, const mo3d::Patch3d* const* par
     if (skip) memcpy(skp.data(), skip, m);
     ob.images = images.data(); ob.ok = accp.data(); ob.color = color.data(); ob.ncc = ncc.data();
     ob.fmin = fmin.data(); ob.nevals = evals.data();
-    if (hpmvs_expand_batch(dev, &o, (int)mode, &pb, cc.data(), cw.data(), skip ? skp.data() : nullptr, &ob, 0, nullptr) != HPMVS_OK) {
+    int rc;
+    if (tree) {   // the level against the real octree: the tree decides the skip flags on the device
+        PVec<uint8_t> ksk(m, pin), kin(m, pin), kbo(m, pin);
+        PVec<uint64_t> kpre(m, pin), kpost(m, pin);
+        hpmvs_octree_index t;
+        for (int k = 0; k < 3; k++) t.root_center[k] = tree->rootCenter[k];
+        t.root_width = tree->rootWidth;
+        t.n_branches = (int32_t)tree->branchKeys.size(); t.n_leaves = (int32_t)tree->leafKeys.size();
+        t.branch_key = tree->branchKeys.data(); t.leaf_key = tree->leafKeys.data();
+        const hpmvs_extend_tree_keys kk = {ksk.data(), kin.data(), kpre.data(), kbo.data(), kpost.data()};
+        rc = hpmvs_extend_tree_batch(dev, &o, &t, &pb, width, &ob, &kk, 0, nullptr);
+        if (rc == HPMVS_OK) {
+            keys->skip.assign(ksk.begin(), ksk.end()); keys->preInside.assign(kin.begin(), kin.end()); keys->border.assign(kbo.begin(), kbo.end());
+            keys->preKey.assign(kpre.begin(), kpre.end()); keys->postKey.assign(kpost.begin(), kpost.end());
+        }
+    } else {
+        rc = hpmvs_expand_batch(dev, &o, (int)mode, &pb, cc.data(), cw.data(), skip ? skp.data() : nullptr, &ob, 0, nullptr);
+    }
+    if (rc != HPMVS_OK) {
         std::cerr << "frontier expansion failed: <" << hpmvs_last_error() << ">" << std::endl;
         accepted.assign(m, 0);
         return N;
@@ -1727,11 +1763,14 @@ static int pyramid_levels(const Scene* scene, const char* who) {
 // before the candidates of parent eventCell[j] (non-decreasing).  extendLevel is the case without events.  The candidates' leaves, ONE
 // expandBatch, ONE footprint call over the nodes in queue order (a parent's events, then its refined candidates), the level's conflict
 // graph, then the waves: depthGates over the undecided candidates, the walk in queue order, ONE ordered setDepths.  Events need
-// sequential == true.  `who` names the calling method in the HPMVS_LEVEL_TIMES lines.
+// sequential == true.  `who` names the calling method in the HPMVS_LEVEL_TIMES lines.  With `tree` the level runs against the real octree
+// (extendLevelTree / filterExtendLevelTree): candidates, refinement and the keys of both look-ups come from ONE
+// hpmvs_extend_tree_batch (leafKey and the grid are not used), a refined candidate outside the root is a border candidate (stage 27:
+// no depths, no leaf), and the accepted candidates are entered into `tree`.
 static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, const HpmvsOptions* options, int nLevels,
                        const Patch3d* const* parents, size_t n, const Patch3d* const* events, const size_t* eventCell, size_t nEvents,
                        float width, std::unordered_set<uint64_t>& occupied, float margin, bool absInt, bool sequential,
-                       PatchOptimizer::LeafKeyFn leafKey, void* user, PatchOptimizer::LevelResult& R) {
+                       PatchOptimizer::LeafKeyFn leafKey, void* user, PatchOptimizer::LevelResult& R, OctreeIndex* tree = nullptr) {
     if (!leafKey) leafKey = grid_leaf_key;
     const size_t N = 6, T = n * N;
     R = PatchOptimizer::LevelResult();
@@ -1742,16 +1781,30 @@ static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, 
     for (size_t i = 0; i < n; i++) { cells[i].c = Eigen::Vector3f(0.0f, 0.0f, 0.0f); cells[i].width = width; }
     // the candidates before optimize (everything skipped: constructed only) -> their leaves
     std::vector<uint8_t> skip(T, 0), refined;
-    std::vector<float> pre, widths(n, width);
-    if (!candidate_centers(scene, options, (int)PatchOptimizer::EXTEND, parents, widths.data(), n, pre)) return false;
     std::vector<uint64_t> preKey(T), postKey(T, 0);
-    for (size_t t = 0; t < T; t++) {
-        preKey[t] = leafKey(Eigen::Vector3f(pre[3 * t], pre[3 * t + 1], pre[3 * t + 2]), width, user);
-        skip[t] = occupied.count(preKey[t]) ? 1 : 0;   // level-start occupancy: those are never refined
+    // on the real tree: preIn[t] == 0: the centre before optimize lies outside the root -- never pre-gated, and a leaf that nothing
+    // else can hold (a flag, not a reserved key: every 64-bit word is some grid cell or path key); border[t]: refined and outside
+    std::vector<uint8_t> preIn(T, 1), border(T, 0);
+    double t_pre;
+    if (tree) {   // ONE hpmvs_extend_tree_batch: candidates, the tree's skip flags, refinement, the keys of both look-ups
+        t_pre = level_now();
+        PatchOptimizer::TreeKeys K;
+        po.expandTreeBatch(parents, n, width, *tree, R.candidates, refined, K);
+        if (R.candidates.size() != T) return false;
+        skip.swap(K.skip); preIn.swap(K.preInside); preKey.swap(K.preKey);
+        for (size_t t = 0; t < T; t++)
+            if (refined[t] && !skip[t]) { border[t] = K.border[t]; postKey[t] = K.postKey[t]; }
+    } else {
+        std::vector<float> pre, widths(n, width);
+        if (!candidate_centers(scene, options, (int)PatchOptimizer::EXTEND, parents, widths.data(), n, pre)) return false;
+        for (size_t t = 0; t < T; t++) {
+            preKey[t] = leafKey(Eigen::Vector3f(pre[3 * t], pre[3 * t + 1], pre[3 * t + 2]), width, user);
+            skip[t] = occupied.count(preKey[t]) ? 1 : 0;   // level-start occupancy: those are never refined
+        }
+        t_pre = level_now();
+        po.expandBatch(PatchOptimizer::EXTEND, parents, cells.data(), n, skip.data(), R.candidates, refined);
+        if (R.candidates.size() != T) return false;
     }
-    const double t_pre = level_now();
-    po.expandBatch(PatchOptimizer::EXTEND, parents, cells.data(), n, skip.data(), R.candidates, refined);
-    if (R.candidates.size() != T) return false;
     const double t_ref = level_now();
     // the footprinted nodes in queue order: per parent its events, then its REFINED candidates (the others read and write no map);
     // pending items: t < T a candidate, T + node an event
@@ -1766,7 +1819,7 @@ static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, 
         for (size_t t = N * i; t < N * (i + 1); t++) {
             if (skip[t]) { refined[t] = 0; R.stage[t] = 20; continue; }
             if (refined[t]) {
-                postKey[t] = leafKey(Eigen::Vector3f(R.candidates[t].center_[0], R.candidates[t].center_[1], R.candidates[t].center_[2]), width, user);
+                if (!tree) postKey[t] = leafKey(Eigen::Vector3f(R.candidates[t].center_[0], R.candidates[t].center_[1], R.candidates[t].center_[2]), width, user);
                 fpi[t] = (int)nodes.size(); nodes.push_back(&R.candidates[t]); isEvent.push_back(0);
             }
             pending.push_back(t);
@@ -1823,9 +1876,11 @@ static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, 
         bool anySub = false;
         auto defer = [&](size_t t) {
             deferred.push_back(t);
-            occGuard.add(preKey[t]);
+            if (preIn[t]) occGuard.add(preKey[t]);
             if (refined[t]) {
-                open[(size_t)fpi[t]] = wave; defer_w[(size_t)fpi[t]] = wave;
+                defer_w[(size_t)fpi[t]] = wave;
+                if (border[t]) return;   // writes no depth and occupies no leaf: it only guards what it reads
+                open[(size_t)fpi[t]] = wave;
                 maybeOcc.add(postKey[t]); occGuard.add(postKey[t]);
             }
         };
@@ -1837,8 +1892,8 @@ static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, 
                 else { ops.push_back(nodes[e]); opSub.push_back(1); anySub = true; }
                 continue;
             }
-            if (occupied.count(preKey[t])) { R.stage[t] = 20; continue; }   // its leaf was taken by an earlier candidate
-            if (sequential && maybeOcc.has(preKey[t])) { defer(t); continue; }
+            if (preIn[t] && occupied.count(preKey[t])) { R.stage[t] = 20; continue; }   // its leaf was taken by an earlier candidate
+            if (sequential && preIn[t] && maybeOcc.has(preKey[t])) { defer(t); continue; }
             if (!refined[t]) { R.stage[t] = 1; continue; }                  // failed in optimize or at the scale / drift gates
             if (sequential && reads_hit_dirty((size_t)fpi[t], wave)) { defer(t); continue; }
             const int k = slot[t];
@@ -1847,6 +1902,7 @@ static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, 
             if (!(cv >= MIN)) R.stage[t] = 23;
             else if (!(cb < MIN)) R.stage[t] = 24;
             else if (!(cf >= MIN - 1 && cf * 1.0 / (double)R.candidates[t].images_.size() > 0.75)) R.stage[t] = 25;
+            else if (border[t]) R.stage[t] = 27;   // handed to borderCellFn_: not inserted, no depths
             else if (occupied.count(postKey[t])) R.stage[t] = 26;
             else if (sequential && (maybeOcc.has(postKey[t]) || occGuard.has(postKey[t]) || writes_hit_guard((size_t)fpi[t], wave))) {
                 R.counts[3 * t] = R.counts[3 * t + 1] = R.counts[3 * t + 2] = -1;
@@ -1874,7 +1930,28 @@ static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, 
                      1e3 * (t_pre - t_begin), 1e3 * (t_ref - t_pre), 1e3 * (t_fp - t_ref), 1e3 * (t_graph - t_fp), G.flow_adj.size(), G.anti_adj.size(),
                      1e3 * t_gates, 1e3 * t_walk, 1e3 * t_set);
     std::sort(R.accepted.begin(), R.accepted.end());
+    if (tree) {
+        for (size_t t = 0; t < T; t++) if (R.stage[t] == 27) R.border.push_back(t);
+        for (size_t t : R.accepted) { R.leafKey.push_back(postKey[t]); tree->insertLeaf(postKey[t]); }
+    }
     return true;
+}
+
+// the tree levels' preconditions: a level width of the tree (hpmvs_extend_tree_batch would refuse it, but only for n > 0)
+static bool tree_level_ok(const OctreeIndex& tree, float width, const char* who) {
+    if (tree.levelDepth(width) >= 1) return true;
+    std::cerr << "hpmvs: " << who << ": width is not the width of a level of the tree" << std::endl;
+    return false;
+}
+
+bool PatchOptimizer::extendLevelTree(const mo3d::Patch3d* const* parents, size_t n, float width, mo3d::OctreeIndex& tree, float margin,
+                                     bool absInt, LevelResult& R, bool sequential) {
+    R = LevelResult();
+    const int nLevels = pyramid_levels(scene_p, "extendLevelTree");
+    if (nLevels < 0 || !tree_level_ok(tree, width, "extendLevelTree")) return false;
+    std::unordered_set<uint64_t> occupied{0};   // 0: no path key, addConditional's refusal
+    return walk_level("extendLevelTree", *this, scene_p, options_p, nLevels, parents, n, nullptr, nullptr, 0, width, occupied, margin, absInt,
+                      sequential, nullptr, nullptr, R, &tree);
 }
 
 bool PatchOptimizer::extendLevel(const mo3d::Patch3d* const* parents, size_t n, float width, std::unordered_set<uint64_t>& occupied,
@@ -1927,26 +2004,51 @@ bool PatchOptimizer::filterLevel(mo3d::Patch3d* const* patches, const size_t* ce
     return true;
 }
 
+// the filter half of filterExtendLevel / filterExtendLevelTree: ONE filter call; the kept patches are the parents, the losers the
+// events of their cell (before its candidates).  false for an empty cell or a kept patch that is already expanded.
+static bool filter_for_extend(const Scene* scene, mo3d::Patch3d* const* patches, const size_t* cellStart, size_t nCells,
+                              PatchOptimizer::FilterResult& FR, std::vector<const Patch3d*>& parents, std::vector<const Patch3d*>& losers,
+                              std::vector<size_t>& loserCell, const char* who) {
+    if (cellStart)
+        for (size_t c = 0; c < nCells; c++)
+            if (cellStart[c + 1] == cellStart[c]) { std::cerr << "hpmvs: " << who << ": cell " << c << " is empty" << std::endl; return false; }
+    if (!run_filter(scene, patches, cellStart, nCells, FR, who)) return false;
+    parents.assign(nCells, nullptr);
+    for (size_t i = 0; i < nCells; i++) {
+        parents[i] = patches[(size_t)FR.keep[i]];
+        if (parents[i]->expanded_) { std::cerr << "hpmvs: " << who << ": the kept patch of cell " << i << " is already expanded" << std::endl; return false; }
+        for (size_t r = cellStart[i]; r < cellStart[i + 1]; r++) if (FR.removed[r]) { losers.push_back(patches[r]); loserCell.push_back(i); }
+    }
+    return true;
+}
+
 bool PatchOptimizer::filterExtendLevel(mo3d::Patch3d* const* patches, const size_t* cellStart, size_t nCells, float width,
                                        std::unordered_set<uint64_t>& occupied, float margin, bool absInt, FilterResult& FR, LevelResult& R,
                                        LeafKeyFn leafKey, void* user) {
     R = LevelResult();
     const int nLevels = pyramid_levels(scene_p, "filterExtendLevel");
     if (nLevels < 0) return false;
-    if (cellStart)
-        for (size_t c = 0; c < nCells; c++)
-            if (cellStart[c + 1] == cellStart[c]) { std::cerr << "hpmvs: filterExtendLevel: cell " << c << " is empty" << std::endl; return false; }
-    if (!run_filter(scene_p, patches, cellStart, nCells, FR, "filterExtendLevel")) return false;
-    // the kept patches are the parents, the losers the events of their cell (before its candidates)
-    std::vector<const Patch3d*> parents(nCells), losers;
+    std::vector<const Patch3d*> parents, losers;
     std::vector<size_t> loserCell;
-    for (size_t i = 0; i < nCells; i++) {
-        parents[i] = patches[(size_t)FR.keep[i]];
-        if (parents[i]->expanded_) { std::cerr << "hpmvs: filterExtendLevel: the kept patch of cell " << i << " is already expanded" << std::endl; return false; }
-        for (size_t r = cellStart[i]; r < cellStart[i + 1]; r++) if (FR.removed[r]) { losers.push_back(patches[r]); loserCell.push_back(i); }
-    }
+    if (!filter_for_extend(scene_p, patches, cellStart, nCells, FR, parents, losers, loserCell, "filterExtendLevel")) return false;
     if (!walk_level("filterExtendLevel", *this, scene_p, options_p, nLevels, parents.data(), nCells, losers.data(), loserCell.data(), losers.size(),
                     width, occupied, margin, absInt, true, leafKey, user, R))
+        return false;
+    for (size_t i = 0; i < FR.removed.size(); i++) if (FR.removed[i]) patches[i]->images_.clear();   // images_.clear() (:72)
+    return true;
+}
+
+bool PatchOptimizer::filterExtendLevelTree(mo3d::Patch3d* const* patches, const size_t* cellStart, size_t nCells, float width,
+                                           mo3d::OctreeIndex& tree, float margin, bool absInt, FilterResult& FR, LevelResult& R) {
+    R = LevelResult();
+    const int nLevels = pyramid_levels(scene_p, "filterExtendLevelTree");
+    if (nLevels < 0 || !tree_level_ok(tree, width, "filterExtendLevelTree")) return false;
+    std::vector<const Patch3d*> parents, losers;
+    std::vector<size_t> loserCell;
+    if (!filter_for_extend(scene_p, patches, cellStart, nCells, FR, parents, losers, loserCell, "filterExtendLevelTree")) return false;
+    std::unordered_set<uint64_t> occupied{0};
+    if (!walk_level("filterExtendLevelTree", *this, scene_p, options_p, nLevels, parents.data(), nCells, losers.data(), loserCell.data(),
+                    losers.size(), width, occupied, margin, absInt, true, nullptr, nullptr, R, &tree))
         return false;
     for (size_t i = 0; i < FR.removed.size(); i++) if (FR.removed[i]) patches[i]->images_.clear();   // images_.clear() (:72)
     return true;

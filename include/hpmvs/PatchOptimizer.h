@@ -14,6 +14,7 @@
 namespace mo3d {
 class HpmvsOptions;
 class Scene;
+struct OctreeIndex;
 class PatchOptimizer {
 public:
     PatchOptimizer(const mo3d::HpmvsOptions& options, const mo3d::Scene* scene);
@@ -52,10 +53,22 @@ public:
         std::vector<int> counts;                 // 3 per candidate: the counts at decision time (-1: not reached)
         std::vector<size_t> accepted;            // candidate indices, the reference's order
         int waves = 0;
+        std::vector<size_t> border;              // extendLevelTree: the stage-27 candidates in queue order (the scheduler routes them)
+        std::vector<uint64_t> leafKey;           // extendLevelTree: per entry of `accepted` the path key of the leaf it went into
     };
     typedef uint64_t (*LeafKeyFn)(const Eigen::Vector3f& p, float width, void* user);
     bool extendLevel(const mo3d::Patch3d* const* parents, size_t n, float width, std::unordered_set<uint64_t>& occupied,
                      float margin, bool absInt, LevelResult& out, bool sequential = true, LeafKeyFn leafKey = nullptr, void* user = nullptr);
+    // extendLevel against the scheduler's REAL octree, or a subtree of it (hpmvs_amd.frontier.extend_level_tree: same calls, same
+    // results): `parents` are the leaves of ONE node level, all of width `width` -- an exact level width of the tree
+    // (tree.levelDepth(width) >= 1, false otherwise).  The walk is extendLevel's; the candidates, their refinement and the keys of
+    // both look-ups (CellProcessor.cpp:122-125, 147-154) come from ONE hpmvs_extend_tree_batch.  Stage codes as extendLevel's,
+    // where 20 is the pre-gate (inside the root, in a nonempty leaf of any depth or in structure finer than `width`), 26
+    // addConditional's refusal, and 27 = BORDER: the candidate passed every gate but left the tree's root.  Border candidates
+    // come back in LevelResult::border for the scheduler to route (Scene::octreeRoute / octreeInsert); they are not inserted and
+    // write no depths.  The accepted candidates are entered into `tree` (OctreeIndex::insertLeaf at LevelResult::leafKey).
+    bool extendLevelTree(const mo3d::Patch3d* const* parents, size_t n, float width, mo3d::OctreeIndex& tree, float margin, bool absInt,
+                         LevelResult& out, bool sequential = true);
     // One priority level of CellProcessor::branch (reference src/hpmvs/CellProcessor.cpp:210-307) over the patches of the level's
     // leaves, in the scheduler's order: level-support gate (:221-224), the four diagonal children with Cell::contains before and
     // after optimize (:233-258) as ONE expandBatch, then the depth maps in the reference's order -- per split leaf its patch taken
@@ -128,6 +141,19 @@ public:
     bool filterExtendLevel(mo3d::Patch3d* const* patches, const size_t* cellStart, size_t nCells, float width,
                            std::unordered_set<uint64_t>& occupied, float margin, bool absInt, FilterResult& filter, LevelResult& level,
                            LeafKeyFn leafKey = nullptr, void* user = nullptr);
+    // filterExtendLevel against the real octree: the same walk with extendLevelTree's keys, the filters' losers as events.
+    bool filterExtendLevelTree(mo3d::Patch3d* const* patches, const size_t* cellStart, size_t nCells, float width, mo3d::OctreeIndex& tree,
+                               float margin, bool absInt, FilterResult& filter, LevelResult& level);
+    // The candidate steps of such a level alone, as ONE hpmvs_extend_tree_batch (include/hpmvs_amd.h; the C++ form of
+    // hpmvs_amd.api.extend_tree_batch): expandBatch(EXTEND) with cells = (0, width) and the skip flags decided on the device by
+    // the tree, plus the keys of both look-ups, 6 n entries each.  preKey means something only where preInside is set: a centre
+    // outside the root matches no leaf.  Returns 6; on failure `accepted` is all zero and `candidates` empty.
+    struct TreeKeys {
+        std::vector<uint8_t> skip, preInside, border;
+        std::vector<uint64_t> preKey, postKey;
+    };
+    int expandTreeBatch(const mo3d::Patch3d* const* parents, size_t n, float width, const mo3d::OctreeIndex& tree,
+                        std::vector<mo3d::Patch3d>& candidates, std::vector<uint8_t>& accepted, TreeKeys& keys);
     // diagnostics of the last optimize()/optimizeBatch() call that the reference computes and drops
     // (final mean robust INCC f*, PatchOptimizer.cpp:365,376): one entry per patch
     const std::vector<double>& lastObjective() const { return lastF_; }
@@ -140,6 +166,11 @@ public:
     static size_t pinnedCacheCap();
     static void setPinnedCacheCap(size_t bytes);
 private:
+    // expandBatch's body for both device entries: hpmvs_expand_batch (tree == nullptr), or hpmvs_extend_tree_batch at `width`
+    // against `tree` (mode EXTEND; cells and skip unused, keys filled)
+    int expandCall(ExpandMode mode, const mo3d::Patch3d* const* parents, const CellRef* cells, size_t n, const uint8_t* skip,
+                   const mo3d::OctreeIndex* tree, float width, TreeKeys* keys, std::vector<mo3d::Patch3d>& candidates,
+                   std::vector<uint8_t>& accepted);
     const mo3d::HpmvsOptions* options_p;
     const mo3d::Scene* scene_p;
     std::vector<double> lastF_;

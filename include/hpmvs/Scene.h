@@ -12,6 +12,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <unordered_set>
 #include <vector>
 #include <hpmvs/Camera.h>
 #include <hpmvs/HpmvsOptions.h>
@@ -26,6 +27,24 @@ struct OctreeIndex {
     float rootWidth;
     std::vector<uint64_t> branchKeys;
     std::vector<uint64_t> leafKeys;
+    // Enter a patch into the EMPTY leaf `key` (what addConditional's splits leave behind): the key is appended to leafKeys and
+    // every proper prefix below the root that is not a branch yet to branchKeys, deepest first.  Append only: the vectors keep
+    // their order.  PatchOptimizer::extendLevelTree enters a level's accepted candidates with it.
+    void insertLeaf(uint64_t key) {
+        if (branchSet_.size() != branchKeys.size()) branchSet_ = std::unordered_set<uint64_t>(branchKeys.begin(), branchKeys.end());
+        leafKeys.push_back(key);
+        for (uint64_t k = key >> 3; k > 1; k >>= 3)
+            if (branchSet_.insert(k).second) branchKeys.push_back(k);
+    }
+    // The depth d >= 1 whose cells have width_ == width (rootWidth halved d times, each time in double and narrowed to float, as
+    // Cell(parent, idx) does; at most 21 levels), -1 when there is none: the widths extendLevelTree takes.
+    int levelDepth(float width) const {
+        float w = rootWidth;
+        int d = 0;
+        while (w > width && d < 21) { w = (float)((double)w / 2.0); d++; }
+        return (w == width && d >= 1) ? d : -1;
+    }
+    std::unordered_set<uint64_t> branchSet_;   // insertLeaf's view of branchKeys; rebuilt when branchKeys was changed by hand
 };
 // The split of a DynOctTree into subtrees (include/hpmvs_amd.h: hpmvs_octree_partition); the roots' vectors hold nTrees entries.
 struct OctreePartition {
@@ -107,8 +126,8 @@ public:
     // ONE batched GPU call (hpmvs_octree_locate_batch): root->at(p), getRoot()->contains(p) and the leaf
     // DynOctTree::addConditional(p, addWidth) would put p in.  OctreeIndex names the tree by path keys (sentinel bit, 3 bits per
     // level z y x, root = 1): every Branch below the root and the nonempty leaves; addWidth empty: no target keys.  False (and
-    // hpmvs_last_error) when the keys are no tree.  The batched level on top of it is not here yet: PatchOptimizer::extendLevel
-    // still takes its per-point LeafKeyFn.
+    // hpmvs_last_error) when the keys are no tree.  The batched level on top of the same look-ups is
+    // PatchOptimizer::extendLevelTree / filterExtendLevelTree (ONE hpmvs_extend_tree_batch per level).
     struct OctreeLocation {
         std::vector<uint8_t> inside;       // [n] root.contains(p)
         std::vector<uint64_t> leafKey;     // [n] path key of the located leaf

@@ -40,6 +40,7 @@
  *   hpmvs_seed_tree_batch    <- the second half of Scene::initPatches, src/hpmvs/Scene.cpp:183-199
  *                               (getBoundingBox, swapRoot, the scale floor, patchTree_.add, setDepths).
  *   hpmvs_octree_locate_batch <- the tree look-ups of CellProcessor::extend, src/hpmvs/CellProcessor.cpp:122-125, 147-154.
+ *   hpmvs_extend_tree_batch   <- CellProcessor::extend's candidate loop with both tree look-ups, src/hpmvs/CellProcessor.cpp:84-154.
  *   hpmvs_octree_route_batch, <- CellProcessor::distributeBorderCell and ::processBorderCellQueue,
  *   hpmvs_octree_insert_batch    src/hpmvs/CellProcessor.cpp:487-540 (the root search and the addConditional loop).
  *   hpmvs_octree_partition    <- getSubTrees, src/main.cpp:50-96, and DynOctTree::cellHistogram, doctree.h:493-511.
@@ -454,6 +455,38 @@ int hpmvs_octree_locate_batch(const hpmvs_scene *s, const hpmvs_octree_index *t,
                               const float *add_width /*[n], nullable*/, uint8_t *inside /*[n]*/, uint64_t *leaf_key /*[n]*/,
                               int32_t *leaf_index /*[n]*/, float *leaf_width /*[n]*/, float *leaf_center /*[n][3]*/,
                               uint64_t *target_key /*[n]*/, int on_device, void *stream);
+
+/* The candidate steps of one extend level against the real octree, in ONE call (reference src/hpmvs/CellProcessor.cpp:84-178): the
+ * six candidates of every parent are built, looked up in the tree t (:122-125), those the tree does not pre-gate are refined and
+ * gated (:127-133), and the refined ones are looked up again (:147-154).  The call equals HPMVS_EXPAND_EXTEND of
+ * hpmvs_expand_batch with cell_center = 0, cell_width = width for every parent and the skip bytes computed on the device, and it
+ * returns the keys of both look-ups; `out` and the keys are byte-identical to the composition hpmvs_expand_batch (everything
+ * skipped) -> hpmvs_octree_locate_batch -> hpmvs_expand_batch (skip) -> hpmvs_octree_locate_batch at add_width.
+ *   width        the leaf width of the level: an exact level width of the tree (root_width halved d >= 1 times, each time in
+ *                double and narrowed to float).  addConditional's width is (float)((double)width * 0.9), so every target below
+ *                lies at that depth d.
+ *   skip[t]      the tree's verdict whatever else stops the candidate: its centre before optimize lies inside the root, in a leaf
+ *                that is nonempty or narrower than width.  Such a candidate is built, not refined, and ends at stage 20.
+ *   pre_key[t]   for a centre inside the root the leaf addConditional would put it in, 0 where it refuses; 0 outside (a centre
+ *                outside the root is never pre-gated and matches no leaf: test pre_inside, not the key)
+ *   border[t]    the candidate was refined (out->ok[t] != 0) and its centre left the root: it goes to the border queue
+ *   post_key[t]  refined and inside: addConditional's target leaf, 0 where it refuses; 0 for every other candidate
+ * Every pointer of keys is nullable, and so is keys; what is given is written in every entry.  parents->n == 0 and the empty tree
+ * are valid.  HPMVS_ERR_ARG before any output is written for what hpmvs_expand_batch refuses (a bad batch, out->n != 6 n), what
+ * hpmvs_octree_locate_batch refuses (keys that are no tree, a bad root), and for a width that is not finite or no level width of
+ * the tree.  The look-up table is built ONCE, in device memory of the call's own (12 bytes per slot, 2 x keys slots; a launch
+ * workspace would be handed to the refinement between the two look-ups), allocated before and freed after the call like
+ * hpmvs_octree_insert_batch's scratch; the call is host-synchronous in both pointer forms. */
+typedef struct {            /* every pointer nullable; [6 * parents->n] each; follow on_device */
+    uint8_t  *skip;         /* 1: pre-gated (CellProcessor.cpp:124): built, not refined, stage 20 */
+    uint8_t  *pre_inside;   /* getRoot()->contains(centre before optimize) */
+    uint64_t *pre_key;      /* inside: addConditional's target leaf at (float)(width * 0.9); else 0 */
+    uint8_t  *border;       /* refined (ok != 0) and outside the root (:147) */
+    uint64_t *post_key;     /* refined and inside: the target leaf, 0 = addConditional refuses; else 0 */
+} hpmvs_extend_tree_keys;
+int hpmvs_extend_tree_batch(const hpmvs_scene *s, const hpmvs_options *o, const hpmvs_octree_index *t,
+                            const hpmvs_patch_batch *parents, float width, hpmvs_patch_batch *out,
+                            const hpmvs_extend_tree_keys *keys, int on_device, void *stream);
 
 /* A round's border patches (reference src/hpmvs/CellProcessor.cpp:487-540): candidates of CellProcessor::extend that passed every
  * gate but left their subtree's root.  distributeBorderCell hands each to the first processor whose root contains it;
