@@ -62,6 +62,11 @@ class ExtendTreeKeysStruct(C.Structure):
                 ("post_key", C.c_void_p)]
 
 
+class OctreeForest(C.Structure):
+    _fields_ = [("n_trees", C.c_int32), ("root", C.c_void_p), ("branch_first", C.c_void_p), ("leaf_first", C.c_void_p),
+                ("branch_key", C.c_void_p), ("leaf_key", C.c_void_p)]
+
+
 class OctreePartitionInfo(C.Structure):
     _fields_ = [("n_trees", C.c_int32), ("n_orphans", C.c_int32), ("n_splits", C.c_int32), ("stop", C.c_int32),
                 ("histogram", C.c_int32 * 22)]
@@ -86,6 +91,7 @@ EXPORTS = [
     "hpmvs_undistort", "hpmvs_undistort_map", "hpmvs_scene_set_view_distorted",
     "hpmvs_regularize_batch", "hpmvs_filter_batch", "hpmvs_seed_tree_batch", "hpmvs_octree_locate_batch",
     "hpmvs_octree_insert_batch", "hpmvs_octree_route_batch", "hpmvs_octree_partition", "hpmvs_extend_tree_batch",
+    "hpmvs_extend_forest_batch",
     "hpmvs_scene_center", "hpmvs_init_patches_sphere_batch",
     "hpmvs_jpeg_info", "hpmvs_jpeg_decode", "hpmvs_scene_set_view_jpeg", "hpmvs_jpeg_decode_timed",
 ]
@@ -163,6 +169,8 @@ def lib():
     L.hpmvs_octree_insert_batch.argtypes = [C.c_void_p, C.POINTER(OctreeIndex), C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
     L.hpmvs_extend_tree_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(OctreeIndex), C.POINTER(PatchBatch), C.c_float,
                                           C.POINTER(PatchBatch), C.POINTER(ExtendTreeKeysStruct), C.c_int, C.c_void_p]
+    L.hpmvs_extend_forest_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(OctreeForest), C.POINTER(PatchBatch), C.c_void_p,
+                                            C.c_float, C.POINTER(PatchBatch), C.POINTER(ExtendTreeKeysStruct), C.c_int, C.c_void_p]
     L.hpmvs_octree_route_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.hpmvs_octree_partition.argtypes = [C.c_void_p, C.POINTER(OctreeIndex), C.c_int, C.c_int, C.POINTER(OctreePartitionInfo)] + \
         [C.c_void_p] * 9 + [C.c_int, C.c_void_p]
@@ -510,6 +518,16 @@ def depth_level(scene: Scene, view: int, level: int) -> np.ndarray:
     return out
 
 
+depth_get_level = depth_level
+
+
+def depth_set_level(scene: Scene, view: int, level: int, data):
+    """One depth map back in, as depth_get_level returned it (shape (cols, rows)): hpmvs_scene_depth_set_level."""
+    m = np.ascontiguousarray(data, dtype=np.float32)
+    if m.size:   # (a 0-row level: nothing to copy)
+        _chk(lib().hpmvs_scene_depth_set_level(scene.h, view, level, m.ctypes.data, m.shape[1], m.shape[0]))
+
+
 def set_depths_batch(scene: Scene, batch: Batch):
     """Scene::setDepths for every patch of the batch with ok != 0 (reference Scene.cpp:351-381)."""
     b = batch.c_struct()
@@ -709,6 +727,49 @@ def extend_tree_batch(scene: Scene, parents: Batch, width, root_center, root_wid
     pb, ob, kb = parents.c_struct(), out.c_struct(), keys.c_struct()
     _chk(lib().hpmvs_extend_tree_batch(scene.h, C.byref(o), C.byref(t), C.byref(pb), float(np.float32(width)), C.byref(ob),
                                        C.byref(kb), 0, None))
+    return out, keys
+
+
+def octree_forest(roots, branch_first, leaf_first, branch_key, leaf_key):
+    """The C structure of a forest (include/hpmvs_amd.h: hpmvs_octree_forest) over contiguous copies of the arrays given:
+    roots [n_trees, 4] (c_, width_), the offsets [n_trees + 1] and the concatenated keys.  Returns (OctreeForest, arrays): keep
+    `arrays` alive while the structure is in use."""
+    rt = np.ascontiguousarray(np.asarray(roots, dtype=np.float32).reshape(-1, 4))
+    bf = np.ascontiguousarray(branch_first, dtype=np.int32).reshape(-1)
+    lf = np.ascontiguousarray(leaf_first, dtype=np.int32).reshape(-1)
+    bk = np.ascontiguousarray(branch_key, dtype=np.uint64).reshape(-1)
+    lk = np.ascontiguousarray(leaf_key, dtype=np.uint64).reshape(-1)
+    if len(bf) != len(rt) + 1 or len(lf) != len(rt) + 1:
+        raise ValueError("octree_forest: branch_first / leaf_first need n_trees + 1 entries")
+    if len(bk) != max(int(bf[-1]), 0) or len(lk) != max(int(lf[-1]), 0):
+        raise ValueError("octree_forest: the last offset must be the number of keys given")
+    f = OctreeForest()
+    f.n_trees = len(rt)
+    f.root, f.branch_first, f.leaf_first = rt.ctypes.data, bf.ctypes.data, lf.ctypes.data
+    f.branch_key, f.leaf_key = bk.ctypes.data, lk.ctypes.data
+    return f, (rt, bf, lf, bk, lk)
+
+
+def extend_forest_batch(scene: Scene, parents: Batch, parent_tree, width, roots, branch_first, leaf_first, branch_key, leaf_key,
+                        options: Options | None = None):
+    """extend_tree_batch for ALL trees of a forest as ONE hpmvs_extend_forest_batch (include/hpmvs_amd.h): tree k has the root
+    roots[k] (c_, width_) and the keys branch_key[branch_first[k]:branch_first[k + 1]] / leaf_key[leaf_first[k]:leaf_first[k + 1]],
+    relative to its own root; parent_tree[i] names the tree of parent i, in any order.  Rows 6 i .. 6 i + 5 equal what
+    extend_tree_batch returns for that tree alone.  HpmvsError names the offending tree.  Returns (out, ExtendTreeKeys)."""
+    o = options or default_options()
+    f, hold = octree_forest(roots, branch_first, leaf_first, branch_key, leaf_key)
+    pt = np.ascontiguousarray(parent_tree, dtype=np.int32).reshape(-1)
+    if len(pt) != parents.n:
+        raise ValueError("extend_forest_batch: parent_tree needs one entry per parent")
+    N = 6 * parents.n
+    out = Batch(np.zeros((N, 4), np.float32), np.zeros((N, 4), np.float32), np.zeros(N, np.float32), np.zeros(N, np.int32),
+                np.full((N, parents.max_images), -1, np.int32))
+    keys = ExtendTreeKeys(np.zeros(N, np.uint8), np.zeros(N, np.uint8), np.zeros(N, np.uint64), np.zeros(N, np.uint8),
+                          np.zeros(N, np.uint64))
+    pb, ob, kb = parents.c_struct(), out.c_struct(), keys.c_struct()
+    _chk(lib().hpmvs_extend_forest_batch(scene.h, C.byref(o), C.byref(f), C.byref(pb), pt.ctypes.data, float(np.float32(width)),
+                                         C.byref(ob), C.byref(kb), 0, None))
+    del hold
     return out, keys
 
 

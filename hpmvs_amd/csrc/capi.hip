@@ -2209,6 +2209,127 @@ int hpmvs_extend_tree_batch(const hpmvs_scene* s, const hpmvs_options* o, const 
     if ((rc = c.finish())) return rc;
     return ck.finish();   // (waits in both forms: the table is freed when this call returns)
 }
+// The same level for ALL subtrees of a partition (kernel_extend_forest.hip): one table buffer in which every tree
+// owns a slot range, one device array of {root, table}, and ONE expand_init / refinement / expand_gate for the candidates of all
+// trees.  What the host knows (offsets, roots, which trees have the level) travels in one header block behind the verdict words;
+// the keys' verdict and parent_tree's come back in ONE read-back, before a batch array is declared.
+int hpmvs_extend_forest_batch(const hpmvs_scene* s, const hpmvs_options* o, const hpmvs_octree_forest* f, const hpmvs_patch_batch* parents,
+                              const int32_t* parent_tree, float width, hpmvs_patch_batch* out, const hpmvs_extend_tree_keys* keys,
+                              int on_device, void* stream) {
+    const std::string who = "extend_forest_batch";
+    if (hpmvs_device_count() <= 0) return fail(HPMVS_ERR_NODEVICE, who + ": no HIP device visible");
+    int rc = check_batch(s, o, parents);
+    if (rc) return rc;
+    if ((rc = check_batch_shape(s, o, out))) return rc;
+    if (!f) return fail(HPMVS_ERR_ARG, who + ": null forest");
+    const int N = expand_fanout(HPMVS_EXPAND_EXTEND);
+    if (out->n != parents->n * N) return fail(HPMVS_ERR_ARG, who + ": out->n must be 6 * parents->n");
+    if (out->max_images != parents->max_images) return fail(HPMVS_ERR_ARG, who + ": max_images mismatch");
+    if (parents->n > 0 && (!out->center || !out->normal || !out->scale || !out->n_images || !out->images || !out->ok))
+        return fail(HPMVS_ERR_ARG, who + ": missing array");
+    if (parents->n > 0 && !parent_tree) return fail(HPMVS_ERR_ARG, who + ": parent_tree missing");
+    if (!std::isfinite(width)) return fail(HPMVS_ERR_ARG, who + ": width is not finite");
+    const int T = f->n_trees;
+    if (T < 0) return fail(HPMVS_ERR_ARG, who + ": negative count");
+    if (T == 0 && parents->n > 0) return fail(HPMVS_ERR_ARG, who + ": parent_tree[0] is outside [0, n_trees): the forest has no tree");
+    if (T > 0 && (!f->root || !f->branch_first || !f->leaf_first)) return fail(HPMVS_ERR_ARG, who + ": root / branch_first / leaf_first missing");
+    if (T == 0) return HPMVS_OK;
+    int32_t bad = octree::forest_offsets_bad(T, f->branch_first);
+    if (bad < 0) bad = octree::forest_offsets_bad(T, f->leaf_first);
+    if (bad >= 0) return fail(HPMVS_ERR_ARG, who + ": tree " + std::to_string(bad) + ": the key offsets must start at 0 and never decrease");
+    const size_t nb = (size_t)f->branch_first[T], nl = (size_t)f->leaf_first[T], n = (size_t)parents->n, nc = n * N;
+    if (nb + nl > ((size_t)1 << 29)) return fail(HPMVS_ERR_ARG, who + ": the forest's keys do not fit one table buffer");
+    if ((nb > 0 && !f->branch_key) || (nl > 0 && !f->leaf_key)) return fail(HPMVS_ERR_ARG, who + ": key arrays missing");
+    for (int k = 0; k < T; k++) {
+        const float* r = f->root + 4 * (size_t)k;
+        if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[2]))
+            return fail(HPMVS_ERR_ARG, who + ": tree " + std::to_string(k) + ": root centre not finite");
+        if (!(r[3] > 0.0f) || !std::isfinite(r[3])) return fail(HPMVS_ERR_ARG, who + ": tree " + std::to_string(k) + ": root width must be finite and > 0");
+    }
+    // the header block as the device reads it: [verdict] [Tree x T] [branch_first] [leaf_first] [has_level]; then the table
+    // buffer and cell_width of expand_init / expand_gate
+    std::vector<uint64_t> slot_first((size_t)T + 1);
+    octree::forest_slots(T, f->branch_first, f->leaf_first, slot_first.data());
+    const size_t slots = (size_t)slot_first[T];
+    const size_t o_trees = reg_align(sizeof(uint32_t) * kForestWords), o_bf = reg_align(o_trees + sizeof(octree::Tree) * T),
+                 o_lf = reg_align(o_bf + 4 * ((size_t)T + 1)), o_lvl = reg_align(o_lf + 4 * ((size_t)T + 1)), o_keys = reg_align(o_lvl + T),
+                 o_vals = reg_align(o_keys + 8 * slots), o_cw = reg_align(o_vals + 4 * slots), bytes = o_cw + sizeof(float) * n;
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    Call ck(s, on_device, st);
+    const unsigned long long* dbk = (const unsigned long long*)ck.in(f->branch_key, nb);
+    const unsigned long long* dlk = (const unsigned long long*)ck.in(f->leaf_key, nl);
+    const int32_t* dpt = ck.in(parent_tree, n);
+    char* w = (char*)ck.scratch(bytes);
+    if (!w) return ck.error();
+    std::vector<char> hdr(o_keys, 0);
+    for (int v = 0; v < kForestWords; v++) ((uint32_t*)hdr.data())[v] = octree::kForestGood;
+    octree::Tree* ht = (octree::Tree*)(hdr.data() + o_trees);
+    for (int k = 0; k < T; k++) {
+        const float* r = f->root + 4 * (size_t)k;
+        ht[k].root = octree::Cell{{r[0], r[1], r[2]}, r[3]};
+        ht[k].t = octree::Table{(const uint64_t*)(w + o_keys) + slot_first[k], (const int32_t*)(w + o_vals) + slot_first[k],
+                                (uint32_t)(slot_first[k + 1] - slot_first[k])};
+        hdr[o_lvl + k] = octree::level_depth(r[3], width) >= 0 ? 1 : 0;
+    }
+    memcpy(hdr.data() + o_bf, f->branch_first, 4 * ((size_t)T + 1));
+    memcpy(hdr.data() + o_lf, f->leaf_first, 4 * ((size_t)T + 1));
+    uint32_t* verdict = (uint32_t*)w;
+    const octree::Tree* dtrees = (const octree::Tree*)(w + o_trees);
+    float* dcw = (float*)(w + o_cw);
+    if ((rc = ck.begin(st))) return rc;
+    HIPCHK(hipMemcpyAsync(w, hdr.data(), o_keys, hipMemcpyHostToDevice, st));   // (pageable: consumed before it returns)
+    HIPCHK(hipMemsetAsync(w + o_keys, 0, 8 * slots, st));
+    launch_forest_build(T, (const int32_t*)(w + o_bf), (const int32_t*)(w + o_lf), dbk, dlk, (int)(nb + nl), dtrees, verdict, st);
+    HIPCHK(hipGetLastError());
+    launch_forest_parents(T, (const uint8_t*)(w + o_lvl), (int)n, dpt, verdict, st);
+    HIPCHK(hipGetLastError());
+    uint32_t h[kForestWords];
+    HIPCHK(hipMemcpyAsync(h, verdict, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (h[kForestTable] != octree::kForestGood) {
+        const std::string tree = who + ": tree " + std::to_string(octree::finding_tree(h[kForestTable]));
+        const int b = octree::finding_bad(h[kForestTable]);
+        if (b & octree::kBadKey) return fail(HPMVS_ERR_ARG, tree + ": a word is no path key of a cell below the root (a leaf deeper than 21 levels, a branch deeper than 20)");
+        if (b & octree::kBadTwice) return fail(HPMVS_ERR_ARG, tree + ": a key occurs twice (within the branch or leaf keys, or in both)");
+        return fail(HPMVS_ERR_ARG, tree + ": a key's parent prefix is neither a branch nor the root");
+    }
+    if (h[kForestParent] != octree::kForestGood)
+        return fail(HPMVS_ERR_ARG, who + ": parent_tree[" + std::to_string(h[kForestParent]) + "] is outside [0, n_trees)");
+    if (h[kForestLevel] != octree::kForestGood)
+        return fail(HPMVS_ERR_ARG, who + ": tree " + std::to_string(h[kForestLevel]) + ": width is not the width of a level of the tree");
+    if (n == 0) return ck.finish();
+    Call c(s, on_device, st);
+    const DevBatch P = c.batch(parents, Call::kRead), D = c.batch(out, Call::kCreate);
+    ExtendTreeOut K;
+    memset(&K, 0, sizeof(K));
+    if (keys) {   // (the two kernels write every entry of what they are given: no zero fill)
+        K.skip = c.arr(keys->skip, nc, Call::kCopyBack);
+        K.pre_inside = c.arr(keys->pre_inside, nc, Call::kCopyBack);
+        K.pre_key = (unsigned long long*)c.arr(keys->pre_key, nc, Call::kCopyBack);
+        K.border = c.arr(keys->border, nc, Call::kCopyBack);
+        K.post_key = (unsigned long long*)c.arr(keys->post_key, nc, Call::kCopyBack);
+    }
+    if ((rc = c.begin(st))) return rc;
+    const DevOptions d = make_dev_options(o);
+    uint32_t wbits;
+    memcpy(&wbits, &width, 4);
+    {
+        std::lock_guard<std::recursive_mutex> lk(s->mu);
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)dcw, (int)wbits, n, st));
+        launch_expand_init(dev_scene(s), HPMVS_EXPAND_EXTEND, parents->n, P, nullptr, dcw, nullptr, D, st);
+        HIPCHK(hipGetLastError());
+        launch_extend_forest_pre(dtrees, dpt, (int)nc, width, D, K, st);
+        HIPCHK(hipGetLastError());
+        if ((rc = enqueue_refinement(s, d, D, st))) return rc;
+        launch_expand_gate(HPMVS_EXPAND_EXTEND, parents->n, P, nullptr, dcw, D, st);
+        HIPCHK(hipGetLastError());
+        launch_extend_forest_post(dtrees, dpt, (int)nc, width, D, K, st);
+        HIPCHK(hipGetLastError());
+    }
+    if ((rc = c.finish())) return rc;
+    return ck.finish();   // (waits in both forms: the tables are freed when this call returns)
+}
 // CellProcessor::processBorderCellQueue's insertion loop (CellProcessor.cpp:500-531): addConditional(points[i], add_width[i]) for
 // i = 0 .. n - 1 IN THAT ORDER against the tree t, which stays the caller's (kernel_octree_insert.hip: static kernel, stable sort by
 // static leaf, one wavefront per leaf's run).  The scratch is the call's own, sized by n alone.

@@ -151,6 +151,22 @@ void launch_extend_tree_pre(const float* root, const unsigned long long* keys, c
 void launch_extend_tree_post(const float* root, const unsigned long long* keys, const int32_t* vals, uint32_t slots, int n, float width,
                              const DevBatch& out, const ExtendTreeOut& k, hipStream_t st);
 
+// the same for a forest (kernel_extend_forest.hip, include/hpmvs_amd.h: hpmvs_extend_forest_batch).  trees: [n_trees] on the
+// device, every Table pointing at its tree's slot range of one buffer whose keys the caller zeroed; branch_first / leaf_first:
+// [n_trees + 1] on the device; n_keys: all keys of the forest.  verdict: [kForestWords], every word set to octree::kForestGood
+// by the caller and folded with min -- the table's finding (octree::forest_finding), the first parent whose parent_tree names no
+// tree, the lowest tree with a parent and has_level == 0.  The candidate kernels read parent_tree[i / 6] unchecked: launch them
+// only behind a good verdict.
+namespace octree { struct Tree; }
+constexpr int kForestTable = 0, kForestParent = 1, kForestLevel = 2, kForestWords = 4;
+void launch_forest_build(int n_trees, const int32_t* branch_first, const int32_t* leaf_first, const unsigned long long* branch_key,
+                         const unsigned long long* leaf_key, int n_keys, const octree::Tree* trees, uint32_t* verdict, hipStream_t st);
+void launch_forest_parents(int n_trees, const uint8_t* has_level, int n, const int32_t* parent_tree, uint32_t* verdict, hipStream_t st);
+void launch_extend_forest_pre(const octree::Tree* trees, const int32_t* parent_tree, int n, float width, const DevBatch& out,
+                              const ExtendTreeOut& k, hipStream_t st);
+void launch_extend_forest_post(const octree::Tree* trees, const int32_t* parent_tree, int n, float width, const DevBatch& out,
+                               const ExtendTreeOut& k, hipStream_t st);
+
 // a round's border patches (kernel_octree_insert.hip, include/hpmvs_amd.h: hpmvs_octree_route_batch, hpmvs_octree_insert_batch).
 // launch_octree_insert reads the table launch_octree_build made and enqueues static kernel, sort and replay on st; != 0: the
 // rocPRIM call failed.  Every entry of every output is written (blocker is nullable).  roots: [n_trees][4] c_, width_ on the device.

@@ -2,7 +2,8 @@
 // src/hpmvs/CellProcessor.cpp:122-125, 147-154, include/hpmvs/doctree.h:250-255, 397-419, src/hpmvs/doctree.cpp:30-42).  Written
 // once for the device kernels (kernel_octree.hip, kernel_octree_insert.hip) and for the host restatements the tests compile with
 // g++ (tests/octree_host.cpp, tests/octree_insert_host.cpp).  DESIGN.md §3.11 has the argument; §3.12 the one for inserting a
-// round's border patches in queue order (the second part of this file), §3.14 the one for the split into subtrees (the last).
+// round's border patches in queue order (the second part of this file), §3.14 the one for the split into subtrees, §3.15 the one
+// for a forest of subtrees behind one table buffer (the last).
 //
 //   path key                 a sentinel bit, then 3 bits per level (z y x, Branch::at's child test x > c_): the root is 1, a cell
 //                            at depth d has 3 d bits below the sentinel; at most kMaxDepth = 21 levels (kernel_regularize.hip's form)
@@ -398,6 +399,102 @@ inline Split partition_sequential(const Table& t, const uint64_t* sorted, int32_
         if (rank_count(rank) < min_split_leaves) { r.stop = kStopSmall; return r; }
         r.n_splits++;
     }
+}
+
+// ---- a forest: the subtrees of one priority level behind ONE table buffer (hpmvs_extend_forest_batch).  The
+// trees' keys come concatenated (tree k's are [first[k], first[k + 1])), every key relative to its own tree's root.  Tree k owns
+// the slot range [slot_first[k], slot_first[k] + table_slots(its keys)) of the buffer, so equal keys of different trees never
+// meet and find / locate / extend_pre / extend_post work on a tree's Table as they do on a lone one.
+struct Tree {
+    Cell root;
+    Table t;
+};
+// the first slot of every tree, [n_trees + 1]; the last entry is the size of the buffer in slots
+inline void forest_slots(int32_t n_trees, const int32_t* branch_first, const int32_t* leaf_first, uint64_t* slot_first) {
+    slot_first[0] = 0;
+    for (int32_t k = 0; k < n_trees; k++)
+        slot_first[k + 1] = slot_first[k] + table_slots((size_t)(branch_first[k + 1] - branch_first[k]) + (size_t)(leaf_first[k + 1] - leaf_first[k]));
+}
+// offsets as the call takes them: [n_trees + 1], from 0, non-decreasing.  -1 when they are, else the first tree whose range is bad
+inline int32_t forest_offsets_bad(int32_t n_trees, const int32_t* first) {
+    if (first[0] != 0) return 0;
+    for (int32_t k = 0; k < n_trees; k++)
+        if (first[k + 1] < first[k]) return k;
+    return -1;
+}
+// the tree that owns entry i of a concatenated array: the LAST k with first[k] <= i (trees without keys own nothing)
+HPMVS_OT_FN int32_t tree_of(const int32_t* first, int32_t n_trees, int32_t i) {
+    int32_t lo = 0, hi = n_trees;   // first[lo] <= i < first[hi]
+    while (hi - lo > 1) {
+        const int32_t mid = lo + (hi - lo) / 2;
+        if (first[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// The verdict of a forest is ONE word folded with min: the lowest offending tree, and of that tree the finding a lone table's
+// verdict would report first (key, then twice, then orphan).  kForestGood is above every finding.
+constexpr uint32_t kForestGood = 0xffffffffu;
+HPMVS_OT_FN uint32_t forest_finding(int32_t tree, int bad) {
+    return ((uint32_t)tree << 2) | ((bad & kBadKey) ? 0u : (bad & kBadTwice) ? 1u : 2u);
+}
+HPMVS_OT_FN int32_t finding_tree(uint32_t v) { return (int32_t)(v >> 2); }
+HPMVS_OT_FN int finding_bad(uint32_t v) { return 1 << (v & 3u); }
+// entry i of the forest's keys, branches first: i < nb is branch_key[i], else leaf_key[i - nb]
+struct ForestKey {
+    uint64_t key;
+    int32_t tree, index;   // index: of a leaf among its own tree's leaf keys (the table value), kBranch for a branch
+};
+HPMVS_OT_FN ForestKey forest_key(int32_t n_trees, const int32_t* branch_first, const int32_t* leaf_first, const uint64_t* branch_key,
+                                 const uint64_t* leaf_key, int32_t i) {
+    const int32_t nb = branch_first[n_trees];
+    ForestKey r;
+    if (i < nb) {
+        r.key = branch_key[i];
+        r.tree = tree_of(branch_first, n_trees, i);
+        r.index = kBranch;
+    } else {
+        r.key = leaf_key[i - nb];
+        r.tree = tree_of(leaf_first, n_trees, i - nb);
+        r.index = i - nb - leaf_first[r.tree];
+    }
+    return r;
+}
+// the check of one key against the finished tables: kForestGood, or its finding
+HPMVS_OT_FN uint32_t forest_check_key(const Tree* trees, const ForestKey& k) {
+    if (key_form(k.key, k.index == kBranch)) return kForestGood;   // (reported by the build; its parent prefix means nothing)
+    const int bad = key_parentage(trees[k.tree].t, k.key);
+    return bad ? forest_finding(k.tree, bad) : kForestGood;
+}
+// the two look-ups of a candidate through its tree's id
+HPMVS_OT_FN ExtendPre extend_forest_pre(const Tree* trees, int32_t tree, const float* p, float width, float add_width) {
+    return extend_pre(trees[tree].root, trees[tree].t, p, width, add_width);
+}
+HPMVS_OT_FN ExtendPost extend_forest_post(const Tree* trees, int32_t tree, const float* p, float add_width) {
+    return extend_post(trees[tree].root, trees[tree].t, p, add_width);
+}
+// The build and the check on one thread (the device enters keys with a compare-and-swap, one lane per key): keys / vals are the
+// table buffer of slot_first[n_trees] entries, keys zeroed; trees[k].t is pointed at tree k's range.  Returns the verdict word.
+inline uint32_t forest_build_sequential(int32_t n_trees, const float* roots, const int32_t* branch_first, const int32_t* leaf_first,
+                                        const uint64_t* branch_key, const uint64_t* leaf_key, const uint64_t* slot_first, uint64_t* keys,
+                                        int32_t* vals, Tree* trees) {
+    for (int32_t k = 0; k < n_trees; k++) {
+        trees[k].root = Cell{{roots[4 * k], roots[4 * k + 1], roots[4 * k + 2]}, roots[4 * k + 3]};
+        trees[k].t = Table{keys + slot_first[k], vals + slot_first[k], (uint32_t)(slot_first[k + 1] - slot_first[k])};
+    }
+    uint32_t verdict = kForestGood;
+    const int32_t n = n_trees > 0 ? branch_first[n_trees] + leaf_first[n_trees] : 0;
+    for (int32_t i = 0; i < n; i++) {
+        const ForestKey k = forest_key(n_trees, branch_first, leaf_first, branch_key, leaf_key, i);
+        uint32_t v = kForestGood;
+        if (const int form = key_form(k.key, k.index == kBranch)) v = forest_finding(k.tree, form);
+        else if (!insert(keys + slot_first[k.tree], vals + slot_first[k.tree], trees[k.tree].t.slots, k.key, k.index)) v = forest_finding(k.tree, kBadTwice);
+        if (v < verdict) verdict = v;
+    }
+    for (int32_t i = 0; i < n; i++) {
+        const uint32_t v = forest_check_key(trees, forest_key(n_trees, branch_first, leaf_first, branch_key, leaf_key, i));
+        if (v < verdict) verdict = v;
+    }
+    return verdict;
 }
 
 }  // namespace octree

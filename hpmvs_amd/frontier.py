@@ -44,6 +44,10 @@ viewBlockTest / pixelFreeTests threshold, 26 = addConditional found the refined 
 `extend_level_tree` / `filter_extend_level_tree` are the same walk against the REAL octree (`Octree`: branch keys + nonempty leaf
 keys, looked up on the device inside ONE hpmvs_extend_tree_batch per level): the pre-gate sees leaves of any depth, addConditional splits, and a
 candidate that ends outside the tree's root is a border candidate, stage 27.
+
+`extend_level_forest` / `filter_extend_level_forest` run that walk ONCE over the queues of all subtrees of a `partition`, one after
+the other, with ONE hpmvs_extend_forest_batch for the candidates of every tree: the per-tree loop's result in list order, border
+patches delivered between levels.
 """
 from __future__ import annotations
 
@@ -96,6 +100,7 @@ class LevelResult:
     deferred_per_wave: list = field(default_factory=list)
     border: list = field(default_factory=list)   # extend_level_tree: the stage-27 candidates in queue order (the scheduler routes them)
     leaf_key: dict = field(default_factory=dict)  # extend_level_tree: accepted candidate -> path key of the leaf it went into
+    tree: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))   # extend_level_forest: the tree of every candidate
 
 
 MAX_LEVELS = 8                     # HPMVS_MAX_LEVELS
@@ -895,6 +900,91 @@ def filter_extend_level_tree(scene: api.Scene, patches: api.Batch, cell_start, w
     F, L = _filter_extend(scene, patches, cell_start, width, keys, {REFUSED}, expanded, margin, abs_int, options,
                           "filter_extend_level_tree")
     _insert_accepted(tree, L, rows)
+    return F, L
+
+
+# ---- a level over all subtrees at once --------------------------------------------------------------
+
+class _ForestKeys:
+    """_TreeKeys for a list of Octree objects: ONE hpmvs_extend_forest_batch per level serves every tree.  The walk's leaf keys
+    are (tree, key) pairs, so equal sub-keys of two subtrees stay distinct; a refusal stays REFUSED whatever the tree, and
+    "outside" / "border" keep their per-candidate tuples.  A tree with parents must have the level; one without may be rooted
+    anywhere (a subtree rooted below the level is the normal case after getSubTrees)."""
+
+    def __init__(self, scene, trees, parent_tree, width):
+        self.scene, self.trees = scene, list(trees)
+        self.width = np.float32(width)
+        self.parent_tree = np.ascontiguousarray(parent_tree, dtype=np.int32).reshape(-1)
+        n = len(self.trees)
+        if len(self.parent_tree) and (self.parent_tree.min() < 0 or self.parent_tree.max() >= n):
+            raise ValueError("extend_level_forest: a parent's tree is outside the list of trees")
+        if (np.diff(self.parent_tree) < 0).any():
+            raise ValueError("extend_level_forest: parent_tree / cell_tree must not decrease (the queue is the trees' queues in list order)")
+        for k in np.unique(self.parent_tree):
+            w, d = self.trees[k].root_width, 0
+            while w > self.width and d < MAX_TREE_DEPTH:
+                w = np.float32(float(w) / 2.0); d += 1
+            if w != self.width or d < 1:
+                raise ValueError(f"extend_level_forest: `width` is not the width of a level of tree {int(k)}")
+        bk = [t.branch_keys() for t in self.trees]
+        lk = [t.leaf_table()[0] for t in self.trees]
+        self.roots = np.array([[*t.root_center, t.root_width] for t in self.trees], np.float32).reshape(n, 4)
+        self.branch_first = np.concatenate([[0], np.cumsum([len(a) for a in bk])]).astype(np.int32)
+        self.leaf_first = np.concatenate([[0], np.cumsum([len(a) for a in lk])]).astype(np.int32)
+        self.branch_key = np.concatenate(bk + [np.zeros(0, np.uint64)]).astype(np.uint64)
+        self.leaf_key = np.concatenate(lk + [np.zeros(0, np.uint64)]).astype(np.uint64)
+
+    def candidates(self, scene, parents, width, o):
+        out, k = api.extend_forest_batch(scene, parents, self.parent_tree, self.width, self.roots, self.branch_first, self.leaf_first,
+                                         self.branch_key, self.leaf_key, options=o)
+        N = out.n
+        tree = np.repeat(self.parent_tree, 6)
+        pair = lambda t, key: (int(tree[t]), int(key)) if key else REFUSED
+        refined = (out.stage == 0) & (k.skip == 0)
+        border = refined & (k.border != 0)
+        pre_key = [pair(t, k.pre_key[t]) if k.pre_inside[t] else ("outside", t) for t in range(N)]
+        post_key = [None if not refined[t] else ("border", t) if border[t] else pair(t, k.post_key[t]) for t in range(N)]
+        return out, pre_key, post_key, k.skip, refined, border
+
+
+def _insert_accepted_forest(trees, keys: _ForestKeys, L: LevelResult, rows):
+    """The walk's (tree, key) pairs back to the key in the candidate's own tree; the accepted candidates into their trees."""
+    L.tree = np.repeat(keys.parent_tree, 6).astype(np.int32)
+    L.leaf_key = {t: pk[1] for t, pk in L.leaf_key.items()}
+    for k, t in enumerate(L.accepted):
+        trees[L.tree[t]].insert(L.leaf_key[t], rows[k] if rows is not None else ("extend", t))
+
+
+def extend_level_forest(scene: api.Scene, parents: api.Batch, parent_tree, width: float, trees, margin: float = 1.0,
+                        abs_int: int = 0, options=None, sequential: bool = True, rows=None) -> LevelResult:
+    """extend_level_tree for ALL subtrees of a partition in one pass: `parents` are the trees' level queues one after the other
+    (parent_tree non-decreasing, ValueError otherwise), `trees` a list of Octree such as Partition.trees.  The candidates of
+    every tree come from ONE hpmvs_extend_forest_batch (_ForestKeys) and go through ONE walk, whose result over the concatenated
+    queue is the sequential loop's: extend_level_tree on tree 0, then tree 1, and so on, from the same starting maps, with
+    candidate indices mapped through the concatenation (every field but waves / deferred_per_wave, which are the one walk's).
+    LevelResult.tree names every candidate's tree; leaf_key[t] is the key in that tree, where the accepted candidate is inserted.
+    Border candidates (stage 27: outside their OWN tree's root) come back in LevelResult.border for route_border / insert_border:
+    they are delivered between levels, never between the subtrees of one level."""
+    keys = _ForestKeys(scene, trees, parent_tree, width)
+    if len(keys.parent_tree) != parents.n:
+        raise ValueError("extend_level_forest: parent_tree needs one entry per parent")
+    L = _level(scene, parents, width, {REFUSED}, margin, abs_int, options or api.default_options(), keys,
+               _pyramid_levels(scene, "extend_level_forest"), sequential)
+    _insert_accepted_forest(keys.trees, keys, L, rows)
+    return L
+
+
+def filter_extend_level_forest(scene: api.Scene, patches: api.Batch, cell_start, cell_tree, width: float, trees, expanded=None,
+                               margin: float = 1.0, abs_int: int = 0, options=None, rows=None):
+    """filter_extend_level_tree for all subtrees in one pass: cell c (rows cell_start[c] .. cell_start[c + 1] - 1 of `patches`)
+    is a leaf of trees[cell_tree[c]], cell_tree non-decreasing.  The same walk with extend_level_forest's keys, the filters'
+    losers as events.  Returns (FilterResult, LevelResult)."""
+    keys = _ForestKeys(scene, trees, cell_tree, width)
+    if len(keys.parent_tree) != len(np.asarray(cell_start).reshape(-1)) - 1:
+        raise ValueError("filter_extend_level_forest: cell_tree needs one entry per cell")
+    F, L = _filter_extend(scene, patches, cell_start, width, keys, {REFUSED}, expanded, margin, abs_int, options,
+                          "filter_extend_level_forest")
+    _insert_accepted_forest(keys.trees, keys, L, rows)
     return F, L
 
 

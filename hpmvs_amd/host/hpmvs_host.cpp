@@ -1434,9 +1434,15 @@ int PatchOptimizer::expandTreeBatch(const mo3d::Patch3d* const* parents, size_t 
     return expandCall(EXTEND, parents, nullptr, n, nullptr, &tree, width, &keys, candidates, accepted);
 }
 
+int PatchOptimizer::expandForestBatch(const mo3d::Patch3d* const* parents, const int32_t* parentTree, size_t n, float width,
+                                      const mo3d::OctreeForest& forest, std::vector<mo3d::Patch3d>& candidates,
+                                      std::vector<uint8_t>& accepted, TreeKeys& keys) {
+    return expandCall(EXTEND, parents, nullptr, n, nullptr, nullptr, width, &keys, candidates, accepted, &forest, parentTree);
+}
+
 int PatchOptimizer::expandCall(ExpandMode mode, const mo3d::Patch3d* const* parents, const CellRef* cells, size_t n, const uint8_t* skip,
                                const mo3d::OctreeIndex* tree, float width, TreeKeys* keys, std::vector<mo3d::Patch3d>& candidates,
-                               std::vector<uint8_t>& accepted) {
+                               std::vector<uint8_t>& accepted, const mo3d::OctreeForest* forest, const int32_t* parentTree) {
     const int N = (mode == EXTEND) ? 6 : 4;
     if (keys) {
         keys->skip.assign(n * N, 0); keys->preInside.assign(n * N, 0); keys->border.assign(n * N, 0);
@@ -1485,16 +1491,27 @@ int PatchOptimizer::expandCall(ExpandMode mode, const mo3d::Patch3d* const* pare
     ob.images = images.data(); ob.ok = accp.data(); ob.color = color.data(); ob.ncc = ncc.data();
     ob.fmin = fmin.data(); ob.nevals = evals.data();
     int rc;
-    if (tree) {   // the level against the real octree: the tree decides the skip flags on the device
+    if (tree || forest) {   // the level against the real octree: the tree decides the skip flags on the device
         PVec<uint8_t> ksk(m, pin), kin(m, pin), kbo(m, pin);
         PVec<uint64_t> kpre(m, pin), kpost(m, pin);
-        hpmvs_octree_index t;
-        for (int k = 0; k < 3; k++) t.root_center[k] = tree->rootCenter[k];
-        t.root_width = tree->rootWidth;
-        t.n_branches = (int32_t)tree->branchKeys.size(); t.n_leaves = (int32_t)tree->leafKeys.size();
-        t.branch_key = tree->branchKeys.data(); t.leaf_key = tree->leafKeys.data();
         const hpmvs_extend_tree_keys kk = {ksk.data(), kin.data(), kpre.data(), kbo.data(), kpost.data()};
-        rc = hpmvs_extend_tree_batch(dev, &o, &t, &pb, width, &ob, &kk, 0, nullptr);
+        if (forest) {   // all subtrees at once: every candidate is looked up in its parent's tree
+            PVec<int32_t> ptree(parentTree, parentTree + n, pin);
+            mo3d::OctreeForest::Flat flat;
+            forest->flatten(flat);
+            hpmvs_octree_forest f;
+            f.n_trees = (int32_t)forest->trees.size();
+            f.root = flat.root.data(); f.branch_first = flat.branchFirst.data(); f.leaf_first = flat.leafFirst.data();
+            f.branch_key = flat.branchKey.data(); f.leaf_key = flat.leafKey.data();
+            rc = hpmvs_extend_forest_batch(dev, &o, &f, &pb, ptree.data(), width, &ob, &kk, 0, nullptr);
+        } else {
+            hpmvs_octree_index t;
+            for (int k = 0; k < 3; k++) t.root_center[k] = tree->rootCenter[k];
+            t.root_width = tree->rootWidth;
+            t.n_branches = (int32_t)tree->branchKeys.size(); t.n_leaves = (int32_t)tree->leafKeys.size();
+            t.branch_key = tree->branchKeys.data(); t.leaf_key = tree->leafKeys.data();
+            rc = hpmvs_extend_tree_batch(dev, &o, &t, &pb, width, &ob, &kk, 0, nullptr);
+        }
         if (rc == HPMVS_OK) {
             keys->skip.assign(ksk.begin(), ksk.end()); keys->preInside.assign(kin.begin(), kin.end()); keys->border.assign(kbo.begin(), kbo.end());
             keys->preKey.assign(kpre.begin(), kpre.end()); keys->postKey.assign(kpost.begin(), kpost.end());
@@ -1770,7 +1787,8 @@ static int pyramid_levels(const Scene* scene, const char* who) {
 static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, const HpmvsOptions* options, int nLevels,
                        const Patch3d* const* parents, size_t n, const Patch3d* const* events, const size_t* eventCell, size_t nEvents,
                        float width, std::unordered_set<uint64_t>& occupied, float margin, bool absInt, bool sequential,
-                       PatchOptimizer::LeafKeyFn leafKey, void* user, PatchOptimizer::LevelResult& R, OctreeIndex* tree = nullptr) {
+                       PatchOptimizer::LeafKeyFn leafKey, void* user, PatchOptimizer::LevelResult& R, OctreeIndex* tree = nullptr,
+                       OctreeForest* forest = nullptr, const int32_t* parentTree = nullptr) {
     if (!leafKey) leafKey = grid_leaf_key;
     const size_t N = 6, T = n * N;
     R = PatchOptimizer::LevelResult();
@@ -1786,10 +1804,17 @@ static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, 
     // else can hold (a flag, not a reserved key: every 64-bit word is some grid cell or path key); border[t]: refined and outside
     std::vector<uint8_t> preIn(T, 1), border(T, 0);
     double t_pre;
-    if (tree) {   // ONE hpmvs_extend_tree_batch: candidates, the tree's skip flags, refinement, the keys of both look-ups
+    // a forest (extendLevelForest): the keys are relative to each candidate's own tree, so the leaf sets are kept per
+    // tree and selected by the candidate's tree; every other level has the one set
+    const size_t nSets = forest ? forest->trees.size() : 1;
+    std::vector<std::unordered_set<uint64_t>> occForest(forest ? nSets : 0, std::unordered_set<uint64_t>{0});   // 0: addConditional's refusal
+    auto setOf = [&](size_t t) -> size_t { return forest ? (size_t)parentTree[t / N] : 0; };
+    auto occ = [&](size_t t) -> std::unordered_set<uint64_t>& { return forest ? occForest[setOf(t)] : occupied; };
+    if (tree || forest) {   // ONE hpmvs_extend_tree_batch / hpmvs_extend_forest_batch: candidates, skip flags, refinement, the keys of both look-ups
         t_pre = level_now();
         PatchOptimizer::TreeKeys K;
-        po.expandTreeBatch(parents, n, width, *tree, R.candidates, refined, K);
+        if (forest) po.expandForestBatch(parents, parentTree, n, width, *forest, R.candidates, refined, K);
+        else po.expandTreeBatch(parents, n, width, *tree, R.candidates, refined, K);
         if (R.candidates.size() != T) return false;
         skip.swap(K.skip); preIn.swap(K.preInside); preKey.swap(K.preKey);
         for (size_t t = 0; t < T; t++)
@@ -1819,7 +1844,7 @@ static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, 
         for (size_t t = N * i; t < N * (i + 1); t++) {
             if (skip[t]) { refined[t] = 0; R.stage[t] = 20; continue; }
             if (refined[t]) {
-                if (!tree) postKey[t] = leafKey(Eigen::Vector3f(R.candidates[t].center_[0], R.candidates[t].center_[1], R.candidates[t].center_[2]), width, user);
+                if (!tree && !forest) postKey[t] = leafKey(Eigen::Vector3f(R.candidates[t].center_[0], R.candidates[t].center_[1], R.candidates[t].center_[2]), width, user);
                 fpi[t] = (int)nodes.size(); nodes.push_back(&R.candidates[t]); isEvent.push_back(0);
             }
             pending.push_back(t);
@@ -1844,7 +1869,7 @@ static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, 
     // subtraction (`guard`).  For an event, flow lists only candidates, so its tests are those of §3.9: an earlier candidate accepted or
     // deferred that writes its cells, an earlier deferred candidate that reads them.
     std::vector<int> open(nodes.size(), 0), defer_w(nodes.size(), 0);
-    FlatSet maybeOcc, occGuard;
+    std::vector<FlatSet> maybeOcc(nSets), occGuard(nSets);
     auto reads_hit_dirty = [&](size_t i, int wave) {
         for (uint32_t q = G.flow_off[i]; q < G.flow_off[i + 1]; q++) if (open[G.flow_adj[q]] == wave) return true;
         return false;
@@ -1867,7 +1892,7 @@ static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, 
         for (size_t k = 0; k < todo.size(); k++) slot[todo[k]] = (int)k;
         double w1 = level_now();
         t_gates += w1 - w0;
-        maybeOcc.clear(); occGuard.clear();
+        for (size_t k = 0; k < nSets; k++) { maybeOcc[k].clear(); occGuard[k].clear(); }
         const int wave = R.waves;
         const size_t accBefore = R.accepted.size();
         std::vector<size_t> deferred;
@@ -1876,12 +1901,12 @@ static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, 
         bool anySub = false;
         auto defer = [&](size_t t) {
             deferred.push_back(t);
-            if (preIn[t]) occGuard.add(preKey[t]);
+            if (preIn[t]) occGuard[setOf(t)].add(preKey[t]);
             if (refined[t]) {
                 defer_w[(size_t)fpi[t]] = wave;
                 if (border[t]) return;   // writes no depth and occupies no leaf: it only guards what it reads
                 open[(size_t)fpi[t]] = wave;
-                maybeOcc.add(postKey[t]); occGuard.add(postKey[t]);
+                maybeOcc[setOf(t)].add(postKey[t]); occGuard[setOf(t)].add(postKey[t]);
             }
         };
         for (size_t t : pending) {
@@ -1892,8 +1917,8 @@ static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, 
                 else { ops.push_back(nodes[e]); opSub.push_back(1); anySub = true; }
                 continue;
             }
-            if (preIn[t] && occupied.count(preKey[t])) { R.stage[t] = 20; continue; }   // its leaf was taken by an earlier candidate
-            if (sequential && preIn[t] && maybeOcc.has(preKey[t])) { defer(t); continue; }
+            if (preIn[t] && occ(t).count(preKey[t])) { R.stage[t] = 20; continue; }   // its leaf was taken by an earlier candidate
+            if (sequential && preIn[t] && maybeOcc[setOf(t)].has(preKey[t])) { defer(t); continue; }
             if (!refined[t]) { R.stage[t] = 1; continue; }                  // failed in optimize or at the scale / drift gates
             if (sequential && reads_hit_dirty((size_t)fpi[t], wave)) { defer(t); continue; }
             const int k = slot[t];
@@ -1903,12 +1928,12 @@ static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, 
             else if (!(cb < MIN)) R.stage[t] = 24;
             else if (!(cf >= MIN - 1 && cf * 1.0 / (double)R.candidates[t].images_.size() > 0.75)) R.stage[t] = 25;
             else if (border[t]) R.stage[t] = 27;   // handed to borderCellFn_: not inserted, no depths
-            else if (occupied.count(postKey[t])) R.stage[t] = 26;
-            else if (sequential && (maybeOcc.has(postKey[t]) || occGuard.has(postKey[t]) || writes_hit_guard((size_t)fpi[t], wave))) {
+            else if (occ(t).count(postKey[t])) R.stage[t] = 26;
+            else if (sequential && (maybeOcc[setOf(t)].has(postKey[t]) || occGuard[setOf(t)].has(postKey[t]) || writes_hit_guard((size_t)fpi[t], wave))) {
                 R.counts[3 * t] = R.counts[3 * t + 1] = R.counts[3 * t + 2] = -1;
                 defer(t);
             } else {
-                occupied.insert(postKey[t]);
+                occ(t).insert(postKey[t]);
                 R.stage[t] = 0;
                 R.accepted.push_back(t);
                 ops.push_back(&R.candidates[t]); opSub.push_back(0);
@@ -1930,11 +1955,42 @@ static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, 
                      1e3 * (t_pre - t_begin), 1e3 * (t_ref - t_pre), 1e3 * (t_fp - t_ref), 1e3 * (t_graph - t_fp), G.flow_adj.size(), G.anti_adj.size(),
                      1e3 * t_gates, 1e3 * t_walk, 1e3 * t_set);
     std::sort(R.accepted.begin(), R.accepted.end());
-    if (tree) {
+    if (tree || forest) {
         for (size_t t = 0; t < T; t++) if (R.stage[t] == 27) R.border.push_back(t);
-        for (size_t t : R.accepted) { R.leafKey.push_back(postKey[t]); tree->insertLeaf(postKey[t]); }
+        for (size_t t : R.accepted) { R.leafKey.push_back(postKey[t]); (forest ? forest->trees[setOf(t)] : *tree).insertLeaf(postKey[t]); }
+    }
+    if (forest) {
+        R.tree.resize(T);
+        for (size_t t = 0; t < T; t++) R.tree[t] = parentTree[t / N];
     }
     return true;
+}
+
+// the forest levels' preconditions: parentTree names trees of the forest and does not decrease (the queue is the trees' queues in
+// list order), and `width` is a level width of every tree that has a parent
+static bool forest_level_ok(const OctreeForest& forest, const int32_t* parentTree, size_t n, float width, const char* who) {
+    for (size_t i = 0; i < n; i++) {
+        const int32_t k = parentTree[i];
+        if (k < 0 || (size_t)k >= forest.trees.size() || (i && k < parentTree[i - 1])) {
+            std::cerr << "hpmvs: " << who << ": the trees of the parents must be trees of the forest and must not decrease" << std::endl;
+            return false;
+        }
+        if ((i == 0 || k != parentTree[i - 1]) && forest.trees[(size_t)k].levelDepth(width) < 1) {
+            std::cerr << "hpmvs: " << who << ": width is not the width of a level of tree " << k << std::endl;
+            return false;
+        }
+    }
+    return true;
+}
+
+bool PatchOptimizer::extendLevelForest(const mo3d::Patch3d* const* parents, const int32_t* parentTree, size_t n, float width,
+                                       mo3d::OctreeForest& forest, float margin, bool absInt, LevelResult& R, bool sequential) {
+    R = LevelResult();
+    const int nLevels = pyramid_levels(scene_p, "extendLevelForest");
+    if (nLevels < 0 || (n && !parentTree) || !forest_level_ok(forest, parentTree, n, width, "extendLevelForest")) return false;
+    std::unordered_set<uint64_t> unused;
+    return walk_level("extendLevelForest", *this, scene_p, options_p, nLevels, parents, n, nullptr, nullptr, 0, width, unused, margin, absInt,
+                      sequential, nullptr, nullptr, R, nullptr, &forest, parentTree);
 }
 
 // the tree levels' preconditions: a level width of the tree (hpmvs_extend_tree_batch would refuse it, but only for n > 0)
@@ -2049,6 +2105,22 @@ bool PatchOptimizer::filterExtendLevelTree(mo3d::Patch3d* const* patches, const 
     std::unordered_set<uint64_t> occupied{0};
     if (!walk_level("filterExtendLevelTree", *this, scene_p, options_p, nLevels, parents.data(), nCells, losers.data(), loserCell.data(),
                     losers.size(), width, occupied, margin, absInt, true, nullptr, nullptr, R, &tree))
+        return false;
+    for (size_t i = 0; i < FR.removed.size(); i++) if (FR.removed[i]) patches[i]->images_.clear();   // images_.clear() (:72)
+    return true;
+}
+
+bool PatchOptimizer::filterExtendLevelForest(mo3d::Patch3d* const* patches, const size_t* cellStart, const int32_t* cellTree, size_t nCells,
+                                             float width, mo3d::OctreeForest& forest, float margin, bool absInt, FilterResult& FR, LevelResult& R) {
+    R = LevelResult();
+    const int nLevels = pyramid_levels(scene_p, "filterExtendLevelForest");
+    if (nLevels < 0 || (nCells && !cellTree) || !forest_level_ok(forest, cellTree, nCells, width, "filterExtendLevelForest")) return false;
+    std::vector<const Patch3d*> parents, losers;
+    std::vector<size_t> loserCell;
+    if (!filter_for_extend(scene_p, patches, cellStart, nCells, FR, parents, losers, loserCell, "filterExtendLevelForest")) return false;
+    std::unordered_set<uint64_t> unused;
+    if (!walk_level("filterExtendLevelForest", *this, scene_p, options_p, nLevels, parents.data(), nCells, losers.data(), loserCell.data(),
+                    losers.size(), width, unused, margin, absInt, true, nullptr, nullptr, R, nullptr, &forest, cellTree))
         return false;
     for (size_t i = 0; i < FR.removed.size(); i++) if (FR.removed[i]) patches[i]->images_.clear();   // images_.clear() (:72)
     return true;

@@ -15,6 +15,7 @@ namespace mo3d {
 class HpmvsOptions;
 class Scene;
 struct OctreeIndex;
+struct OctreeForest;
 class PatchOptimizer {
 public:
     PatchOptimizer(const mo3d::HpmvsOptions& options, const mo3d::Scene* scene);
@@ -55,6 +56,7 @@ public:
         int waves = 0;
         std::vector<size_t> border;              // extendLevelTree: the stage-27 candidates in queue order (the scheduler routes them)
         std::vector<uint64_t> leafKey;           // extendLevelTree: per entry of `accepted` the path key of the leaf it went into
+        std::vector<int32_t> tree;               // extendLevelForest: per candidate its tree (empty for the other levels)
     };
     typedef uint64_t (*LeafKeyFn)(const Eigen::Vector3f& p, float width, void* user);
     bool extendLevel(const mo3d::Patch3d* const* parents, size_t n, float width, std::unordered_set<uint64_t>& occupied,
@@ -69,6 +71,16 @@ public:
     // write no depths.  The accepted candidates are entered into `tree` (OctreeIndex::insertLeaf at LevelResult::leafKey).
     bool extendLevelTree(const mo3d::Patch3d* const* parents, size_t n, float width, mo3d::OctreeIndex& tree, float margin, bool absInt,
                          LevelResult& out, bool sequential = true);
+    // extendLevelTree for ALL subtrees of a partition in one pass (hpmvs_amd.frontier.extend_level_forest: same calls, same results;
+    // DESIGN.md §3.15): `parents` are the trees' level queues one after the other -- parentTree[i] names the tree of parent i and must
+    // not decrease (false otherwise, as for a tree with a parent of which `width` is no level width; a tree without parents may be
+    // rooted anywhere).  The candidates of every tree come from ONE hpmvs_extend_forest_batch and go through the ONE walk, whose
+    // result over the concatenated queue is the sequential loop's: extendLevelTree on tree 0, then tree 1, and so on, from the same
+    // maps.  LevelResult::tree names every candidate's tree, leafKey is the key in that tree, where the accepted candidate is
+    // entered.  Border candidates (27: outside their OWN tree's root) are delivered by the scheduler between levels, never between
+    // the subtrees of one level.
+    bool extendLevelForest(const mo3d::Patch3d* const* parents, const int32_t* parentTree, size_t n, float width, mo3d::OctreeForest& forest,
+                           float margin, bool absInt, LevelResult& out, bool sequential = true);
     // One priority level of CellProcessor::branch (reference src/hpmvs/CellProcessor.cpp:210-307) over the patches of the level's
     // leaves, in the scheduler's order: level-support gate (:221-224), the four diagonal children with Cell::contains before and
     // after optimize (:233-258) as ONE expandBatch, then the depth maps in the reference's order -- per split leaf its patch taken
@@ -144,6 +156,9 @@ public:
     // filterExtendLevel against the real octree: the same walk with extendLevelTree's keys, the filters' losers as events.
     bool filterExtendLevelTree(mo3d::Patch3d* const* patches, const size_t* cellStart, size_t nCells, float width, mo3d::OctreeIndex& tree,
                                float margin, bool absInt, FilterResult& filter, LevelResult& level);
+    // filterExtendLevelTree for all subtrees in one pass: cell c is a leaf of forest.trees[cellTree[c]], cellTree non-decreasing.
+    bool filterExtendLevelForest(mo3d::Patch3d* const* patches, const size_t* cellStart, const int32_t* cellTree, size_t nCells, float width,
+                                 mo3d::OctreeForest& forest, float margin, bool absInt, FilterResult& filter, LevelResult& level);
     // The candidate steps of such a level alone, as ONE hpmvs_extend_tree_batch (include/hpmvs_amd.h; the C++ form of
     // hpmvs_amd.api.extend_tree_batch): expandBatch(EXTEND) with cells = (0, width) and the skip flags decided on the device by
     // the tree, plus the keys of both look-ups, 6 n entries each.  preKey means something only where preInside is set: a centre
@@ -154,6 +169,10 @@ public:
     };
     int expandTreeBatch(const mo3d::Patch3d* const* parents, size_t n, float width, const mo3d::OctreeIndex& tree,
                         std::vector<mo3d::Patch3d>& candidates, std::vector<uint8_t>& accepted, TreeKeys& keys);
+    // The same for a forest, as ONE hpmvs_extend_forest_batch: parentTree[i] names the tree of parent i, in any order; the keys
+    // are relative to the candidate's own tree.
+    int expandForestBatch(const mo3d::Patch3d* const* parents, const int32_t* parentTree, size_t n, float width, const mo3d::OctreeForest& forest,
+                          std::vector<mo3d::Patch3d>& candidates, std::vector<uint8_t>& accepted, TreeKeys& keys);
     // diagnostics of the last optimize()/optimizeBatch() call that the reference computes and drops
     // (final mean robust INCC f*, PatchOptimizer.cpp:365,376): one entry per patch
     const std::vector<double>& lastObjective() const { return lastF_; }
@@ -167,10 +186,10 @@ public:
     static void setPinnedCacheCap(size_t bytes);
 private:
     // expandBatch's body for both device entries: hpmvs_expand_batch (tree == nullptr), or hpmvs_extend_tree_batch at `width`
-    // against `tree` (mode EXTEND; cells and skip unused, keys filled)
+    // against `tree` (mode EXTEND; cells and skip unused, keys filled), or hpmvs_extend_forest_batch against `forest` with parentTree
     int expandCall(ExpandMode mode, const mo3d::Patch3d* const* parents, const CellRef* cells, size_t n, const uint8_t* skip,
                    const mo3d::OctreeIndex* tree, float width, TreeKeys* keys, std::vector<mo3d::Patch3d>& candidates,
-                   std::vector<uint8_t>& accepted);
+                   std::vector<uint8_t>& accepted, const mo3d::OctreeForest* forest = nullptr, const int32_t* parentTree = nullptr);
     const mo3d::HpmvsOptions* options_p;
     const mo3d::Scene* scene_p;
     std::vector<double> lastF_;

@@ -46,6 +46,30 @@ struct OctreeIndex {
     }
     std::unordered_set<uint64_t> branchSet_;   // insertLeaf's view of branchKeys; rebuilt when branchKeys was changed by hand
 };
+// The subtrees of one partition as the forest calls take them (include/hpmvs_amd.h: hpmvs_octree_forest): every tree's keys are
+// relative to its own root.  PatchOptimizer::extendLevelForest / filterExtendLevelForest run a level over all of them at once.
+struct OctreeForest {
+    std::vector<OctreeIndex> trees;
+    // The C structure's arrays: the roots, the offsets and the keys one tree after the other.  `flat` keeps them alive.
+    struct Flat {
+        std::vector<float> root;                     // [n_trees][4] c_, width_
+        std::vector<int32_t> branchFirst, leafFirst; // [n_trees + 1]
+        std::vector<uint64_t> branchKey, leafKey;
+    };
+    void flatten(Flat& flat) const {
+        flat = Flat();
+        flat.branchFirst.push_back(0);
+        flat.leafFirst.push_back(0);
+        for (const OctreeIndex& t : trees) {
+            flat.root.insert(flat.root.end(), t.rootCenter, t.rootCenter + 3);
+            flat.root.push_back(t.rootWidth);
+            flat.branchKey.insert(flat.branchKey.end(), t.branchKeys.begin(), t.branchKeys.end());
+            flat.leafKey.insert(flat.leafKey.end(), t.leafKeys.begin(), t.leafKeys.end());
+            flat.branchFirst.push_back((int32_t)flat.branchKey.size());
+            flat.leafFirst.push_back((int32_t)flat.leafKey.size());
+        }
+    }
+};
 // The split of a DynOctTree into subtrees (include/hpmvs_amd.h: hpmvs_octree_partition); the roots' vectors hold nTrees entries.
 struct OctreePartition {
     int nTrees, nOrphans, nSplits, stop;   // stop 0: the root alone; 1: the list reached minTrees; 2: the largest subtree is too small

@@ -41,6 +41,7 @@
  *                               (getBoundingBox, swapRoot, the scale floor, patchTree_.add, setDepths).
  *   hpmvs_octree_locate_batch <- the tree look-ups of CellProcessor::extend, src/hpmvs/CellProcessor.cpp:122-125, 147-154.
  *   hpmvs_extend_tree_batch   <- CellProcessor::extend's candidate loop with both tree look-ups, src/hpmvs/CellProcessor.cpp:84-154.
+ *   hpmvs_extend_forest_batch <- the same for all subtrees of getSubTrees' list at once (one processQueue level each, src/main.cpp).
  *   hpmvs_octree_route_batch, <- CellProcessor::distributeBorderCell and ::processBorderCellQueue,
  *   hpmvs_octree_insert_batch    src/hpmvs/CellProcessor.cpp:487-540 (the root search and the addConditional loop).
  *   hpmvs_octree_partition    <- getSubTrees, src/main.cpp:50-96, and DynOctTree::cellHistogram, doctree.h:493-511.
@@ -487,6 +488,40 @@ typedef struct {            /* every pointer nullable; [6 * parents->n] each; fo
 int hpmvs_extend_tree_batch(const hpmvs_scene *s, const hpmvs_options *o, const hpmvs_octree_index *t,
                             const hpmvs_patch_batch *parents, float width, hpmvs_patch_batch *out,
                             const hpmvs_extend_tree_keys *keys, int on_device, void *stream);
+
+/* The same for ALL subtrees of a partition in one call.  main() never runs a level on one tree: getSubTrees cuts patchTree_ into
+ * at least --subtrees subtrees and every CellProcessor consults its own (reference src/main.cpp:50-96).  A forest is a list
+ * of trees given as CONCATENATED key arrays -- tree k's branch keys are branch_key[branch_first[k] .. branch_first[k + 1] - 1],
+ * likewise its nonempty leaves' -- every key relative to its own tree's root, in any order within a tree (hpmvs_octree_partition's
+ * leaf_sub_key / branch_sub_key, grouped by tree).  parent_tree[i] names the tree parent i extends in.
+ *   CONTRACT     for every tree k, take the parents with parent_tree[i] == k in their given order: the rows 6 i .. 6 i + 5 of `out`
+ *                and of every key array are byte-identical to what hpmvs_extend_tree_batch returns for tree k alone with those
+ *                parents.  The parents of different trees may be interleaved in any order; the returned keys are relative to the
+ *                candidate's own tree.
+ * One expand_init, one refinement launch and one expand_gate serve all trees, so a level of 100 subtrees costs one launch, one
+ * key upload and one verdict, not 100.  n_trees == 0 with parents->n == 0, trees without keys (eight empty leaves), trees without
+ * parents and parents->n == 0 are valid.  HPMVS_ERR_ARG before any output byte is written, with the offending tree's index in
+ * hpmvs_last_error ("tree K"), for whatever hpmvs_extend_tree_batch refuses for a single tree (keys that are no tree, a bad root,
+ * a bad batch), offsets that are not non-decreasing from 0, a parent_tree[i] outside [0, n_trees) (the message names parent i)
+ * and a parent in a tree of which `width` is no level width.  A tree WITHOUT parents may have any root width: a subtree rooted
+ * below the level is the normal case after getSubTrees.  When several trees offend, the lowest index is named.
+ * The look-up tables share ONE buffer of the call's own, tree k owning a power-of-two slot range of it, so equal keys of
+ * different trees never meet.  root / branch_first / leaf_first are HOST arrays in both forms, like an hpmvs_octree_index; the
+ * key arrays and parent_tree follow on_device.  Host-synchronous in both forms; ONE read-back carries every verdict.
+ * Border patches: a candidate that leaves ITS tree's root comes back with border[t] = 1 whichever other tree contains it; the
+ * caller routes and inserts them between levels (hpmvs_octree_route_batch / hpmvs_octree_insert_batch), never between the
+ * subtrees of one level. */
+typedef struct {
+    int32_t n_trees;
+    const float    *root;          /* [n_trees][4]: c_ x y z, width_   -- HOST array in both forms */
+    const int32_t  *branch_first;  /* [n_trees + 1]  HOST */
+    const int32_t  *leaf_first;    /* [n_trees + 1]  HOST */
+    const uint64_t *branch_key;    /* [branch_first[n_trees]]  follows on_device */
+    const uint64_t *leaf_key;      /* [leaf_first[n_trees]]    follows on_device */
+} hpmvs_octree_forest;
+int hpmvs_extend_forest_batch(const hpmvs_scene *s, const hpmvs_options *o, const hpmvs_octree_forest *f,
+                              const hpmvs_patch_batch *parents, const int32_t *parent_tree /*[parents->n], follows on_device*/,
+                              float width, hpmvs_patch_batch *out, const hpmvs_extend_tree_keys *keys, int on_device, void *stream);
 
 /* A round's border patches (reference src/hpmvs/CellProcessor.cpp:487-540): candidates of CellProcessor::extend that passed every
  * gate but left their subtree's root.  distributeBorderCell hands each to the first processor whose root contains it;
