@@ -67,6 +67,11 @@ class OctreeForest(C.Structure):
                 ("branch_key", C.c_void_p), ("leaf_key", C.c_void_p)]
 
 
+class ProcessForestResultStruct(C.Structure):
+    _fields_ = [("support", C.c_void_p), ("removed", C.c_void_p), ("split", C.c_void_p), ("children", C.c_void_p),
+                ("child_key", C.c_void_p), ("n_neighbours", C.c_void_p), ("neighbour_key", C.c_void_p)]
+
+
 class OctreePartitionInfo(C.Structure):
     _fields_ = [("n_trees", C.c_int32), ("n_orphans", C.c_int32), ("n_splits", C.c_int32), ("stop", C.c_int32),
                 ("histogram", C.c_int32 * 22)]
@@ -91,7 +96,7 @@ EXPORTS = [
     "hpmvs_undistort", "hpmvs_undistort_map", "hpmvs_scene_set_view_distorted",
     "hpmvs_regularize_batch", "hpmvs_filter_batch", "hpmvs_seed_tree_batch", "hpmvs_octree_locate_batch",
     "hpmvs_octree_insert_batch", "hpmvs_octree_route_batch", "hpmvs_octree_partition", "hpmvs_extend_tree_batch",
-    "hpmvs_extend_forest_batch",
+    "hpmvs_extend_forest_batch", "hpmvs_process_forest_batch",
     "hpmvs_scene_center", "hpmvs_init_patches_sphere_batch",
     "hpmvs_jpeg_info", "hpmvs_jpeg_decode", "hpmvs_scene_set_view_jpeg", "hpmvs_jpeg_decode_timed",
 ]
@@ -171,6 +176,9 @@ def lib():
                                           C.POINTER(PatchBatch), C.POINTER(ExtendTreeKeysStruct), C.c_int, C.c_void_p]
     L.hpmvs_extend_forest_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(OctreeForest), C.POINTER(PatchBatch), C.c_void_p,
                                             C.c_float, C.POINTER(PatchBatch), C.POINTER(ExtendTreeKeysStruct), C.c_int, C.c_void_p]
+    L.hpmvs_process_forest_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(OctreeForest), C.c_void_p, C.POINTER(PatchBatch),
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PatchBatch),
+                                             C.POINTER(ProcessForestResultStruct), C.c_int, C.c_void_p]
     L.hpmvs_octree_route_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.hpmvs_octree_partition.argtypes = [C.c_void_p, C.POINTER(OctreeIndex), C.c_int, C.c_int, C.POINTER(OctreePartitionInfo)] + \
         [C.c_void_p] * 9 + [C.c_int, C.c_void_p]
@@ -771,6 +779,60 @@ def extend_forest_batch(scene: Scene, parents: Batch, parent_tree, width, roots,
                                          C.byref(ob), C.byref(kb), 0, None))
     del hold
     return out, keys
+
+
+PROCESS_FOREST_OUTPUTS = ("support", "removed", "split", "children", "child_key", "n_neighbours", "neighbour_key")
+
+
+@dataclass
+class ProcessForestResult:
+    candidates: Batch              # the 4 n branch children (stage 20: not built / not refined)
+    flatness: np.ndarray           # [n] float32 flatness_ after the sweep (regularized cells updated, the others as given)
+    support: np.ndarray            # [n] int32 Scene::getLevelSupport of every cell's patch
+    removed: np.ndarray            # [n] uint8 flatness_ > 2.4: the patch was removed
+    split: np.ndarray              # [n] uint8 the leaf was split
+    children: np.ndarray           # [n, 4] uint8 the children that go into the new leaves
+    child_key: np.ndarray          # [n, 4] uint64 the key (in the cell's tree) of the leaf child k went into, 0: none
+    n_neighbours: np.ndarray       # [n] int32 neighbour leaves of the regularized cells, -2: settled
+    neighbour_key: np.ndarray      # [n, 24] uint64 their keys in the cell's tree, first-probe order, 0-padded (None unless asked for)
+
+    def c_struct(self) -> ProcessForestResultStruct:
+        r = ProcessForestResultStruct()
+        for name in PROCESS_FOREST_OUTPUTS:
+            setattr(r, name, _ptr(getattr(self, name)))
+        return r
+
+
+def process_forest_batch(scene: Scene, cells: Batch, cell_tree, cell_key, flatness, final_level, roots, branch_first, leaf_first,
+                         branch_key, leaf_key, leaf_patch_center, options: Options | None = None,
+                         neighbours: bool = False) -> ProcessForestResult:
+    """One regularize / settle sweep of processCell over the cells of ALL trees of a forest, in row order, as ONE
+    hpmvs_process_forest_batch (include/hpmvs_amd.h): cell i is data[0] of the nonempty leaf cell_key[i] of tree cell_tree[i];
+    leaf_patch_center [all leaves, 3] is data[0]->center_ of every nonempty leaf in leaf_key order.  The depth maps of the scene
+    are updated; the keys given are not changed.  HpmvsError names the offending tree or cell; nothing is written then."""
+    o = options or default_options()
+    f, hold = octree_forest(roots, branch_first, leaf_first, branch_key, leaf_key)
+    n = cells.n
+    ct = np.ascontiguousarray(cell_tree, dtype=np.int32).reshape(-1)
+    ck = np.ascontiguousarray(cell_key, dtype=np.uint64).reshape(-1)
+    fl = np.array(flatness, dtype=np.float32).reshape(-1)
+    fin = np.ascontiguousarray(np.asarray(final_level).astype(np.uint8)).reshape(-1)
+    pc = np.ascontiguousarray(np.asarray(leaf_patch_center, dtype=np.float32).reshape(-1, 3))
+    if not len(ct) == len(ck) == len(fl) == len(fin) == n:
+        raise ValueError("process_forest_batch: cell_tree / cell_key / flatness / final_level need one entry per cell")
+    if len(pc) != len(hold[4]):
+        raise ValueError("process_forest_batch: leaf_patch_center needs one row per leaf key")
+    N = 4 * n
+    out = Batch(np.zeros((N, 4), np.float32), np.zeros((N, 4), np.float32), np.zeros(N, np.float32), np.zeros(N, np.int32),
+                np.full((N, cells.max_images), -1, np.int32))
+    r = ProcessForestResult(out, fl, np.zeros(n, np.int32), np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros((n, 4), np.uint8),
+                            np.zeros((n, 4), np.uint64), np.zeros(n, np.int32),
+                            np.zeros((n, REGULARIZE_PROBES), np.uint64) if neighbours else None)
+    cb, ob, rb = cells.c_struct(), out.c_struct(), r.c_struct()
+    _chk(lib().hpmvs_process_forest_batch(scene.h, C.byref(o), C.byref(f), pc.ctypes.data, C.byref(cb), ct.ctypes.data, ck.ctypes.data,
+                                          fl.ctypes.data, fin.ctypes.data, C.byref(ob), C.byref(rb), 0, None))
+    del hold
+    return r
 
 
 @dataclass

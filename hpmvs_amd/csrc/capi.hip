@@ -2209,6 +2209,31 @@ int hpmvs_extend_tree_batch(const hpmvs_scene* s, const hpmvs_options* o, const 
     if ((rc = c.finish())) return rc;
     return ck.finish();   // (waits in both forms: the table is freed when this call returns)
 }
+// what the host can check of a forest with n_trees > 0 whose offset arrays are there: the offsets, the key arrays, the roots
+static int forest_host_check(const std::string& who, const hpmvs_octree_forest* f) {
+    const int T = f->n_trees;
+    int32_t bad = octree::forest_offsets_bad(T, f->branch_first);
+    if (bad < 0) bad = octree::forest_offsets_bad(T, f->leaf_first);
+    if (bad >= 0) return fail(HPMVS_ERR_ARG, who + ": tree " + std::to_string(bad) + ": the key offsets must start at 0 and never decrease");
+    const size_t nb = (size_t)f->branch_first[T], nl = (size_t)f->leaf_first[T];
+    if (nb + nl > ((size_t)1 << 29)) return fail(HPMVS_ERR_ARG, who + ": the forest's keys do not fit one table buffer");
+    if ((nb > 0 && !f->branch_key) || (nl > 0 && !f->leaf_key)) return fail(HPMVS_ERR_ARG, who + ": key arrays missing");
+    for (int k = 0; k < T; k++) {
+        const float* r = f->root + 4 * (size_t)k;
+        if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[2]))
+            return fail(HPMVS_ERR_ARG, who + ": tree " + std::to_string(k) + ": root centre not finite");
+        if (!(r[3] > 0.0f) || !std::isfinite(r[3])) return fail(HPMVS_ERR_ARG, who + ": tree " + std::to_string(k) + ": root width must be finite and > 0");
+    }
+    return HPMVS_OK;
+}
+// the refusal a finding of the forest's tables (octree::forest_finding) stands for
+static int forest_table_fail(const std::string& who, uint32_t finding) {
+    const std::string tree = who + ": tree " + std::to_string(octree::finding_tree(finding));
+    const int b = octree::finding_bad(finding);
+    if (b & octree::kBadKey) return fail(HPMVS_ERR_ARG, tree + ": a word is no path key of a cell below the root (a leaf deeper than 21 levels, a branch deeper than 20)");
+    if (b & octree::kBadTwice) return fail(HPMVS_ERR_ARG, tree + ": a key occurs twice (within the branch or leaf keys, or in both)");
+    return fail(HPMVS_ERR_ARG, tree + ": a key's parent prefix is neither a branch nor the root");
+}
 // The same level for ALL subtrees of a partition (kernel_extend_forest.hip): one table buffer in which every tree
 // owns a slot range, one device array of {root, table}, and ONE expand_init / refinement / expand_gate for the candidates of all
 // trees.  What the host knows (offsets, roots, which trees have the level) travels in one header block behind the verdict words;
@@ -2234,18 +2259,8 @@ int hpmvs_extend_forest_batch(const hpmvs_scene* s, const hpmvs_options* o, cons
     if (T == 0 && parents->n > 0) return fail(HPMVS_ERR_ARG, who + ": parent_tree[0] is outside [0, n_trees): the forest has no tree");
     if (T > 0 && (!f->root || !f->branch_first || !f->leaf_first)) return fail(HPMVS_ERR_ARG, who + ": root / branch_first / leaf_first missing");
     if (T == 0) return HPMVS_OK;
-    int32_t bad = octree::forest_offsets_bad(T, f->branch_first);
-    if (bad < 0) bad = octree::forest_offsets_bad(T, f->leaf_first);
-    if (bad >= 0) return fail(HPMVS_ERR_ARG, who + ": tree " + std::to_string(bad) + ": the key offsets must start at 0 and never decrease");
+    if ((rc = forest_host_check(who, f))) return rc;
     const size_t nb = (size_t)f->branch_first[T], nl = (size_t)f->leaf_first[T], n = (size_t)parents->n, nc = n * N;
-    if (nb + nl > ((size_t)1 << 29)) return fail(HPMVS_ERR_ARG, who + ": the forest's keys do not fit one table buffer");
-    if ((nb > 0 && !f->branch_key) || (nl > 0 && !f->leaf_key)) return fail(HPMVS_ERR_ARG, who + ": key arrays missing");
-    for (int k = 0; k < T; k++) {
-        const float* r = f->root + 4 * (size_t)k;
-        if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[2]))
-            return fail(HPMVS_ERR_ARG, who + ": tree " + std::to_string(k) + ": root centre not finite");
-        if (!(r[3] > 0.0f) || !std::isfinite(r[3])) return fail(HPMVS_ERR_ARG, who + ": tree " + std::to_string(k) + ": root width must be finite and > 0");
-    }
     // the header block as the device reads it: [verdict] [Tree x T] [branch_first] [leaf_first] [has_level]; then the table
     // buffer and cell_width of expand_init / expand_gate
     std::vector<uint64_t> slot_first((size_t)T + 1);
@@ -2287,13 +2302,7 @@ int hpmvs_extend_forest_batch(const hpmvs_scene* s, const hpmvs_options* o, cons
     uint32_t h[kForestWords];
     HIPCHK(hipMemcpyAsync(h, verdict, sizeof(h), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (h[kForestTable] != octree::kForestGood) {
-        const std::string tree = who + ": tree " + std::to_string(octree::finding_tree(h[kForestTable]));
-        const int b = octree::finding_bad(h[kForestTable]);
-        if (b & octree::kBadKey) return fail(HPMVS_ERR_ARG, tree + ": a word is no path key of a cell below the root (a leaf deeper than 21 levels, a branch deeper than 20)");
-        if (b & octree::kBadTwice) return fail(HPMVS_ERR_ARG, tree + ": a key occurs twice (within the branch or leaf keys, or in both)");
-        return fail(HPMVS_ERR_ARG, tree + ": a key's parent prefix is neither a branch nor the root");
-    }
+    if (h[kForestTable] != octree::kForestGood) return forest_table_fail(who, h[kForestTable]);
     if (h[kForestParent] != octree::kForestGood)
         return fail(HPMVS_ERR_ARG, who + ": parent_tree[" + std::to_string(h[kForestParent]) + "] is outside [0, n_trees)");
     if (h[kForestLevel] != octree::kForestGood)
@@ -2329,6 +2338,186 @@ int hpmvs_extend_forest_batch(const hpmvs_scene* s, const hpmvs_options* o, cons
     }
     if ((rc = c.finish())) return rc;
     return ck.finish();   // (waits in both forms: the tables are freed when this call returns)
+}
+// One regularize / settle sweep of processCell over ALL subtrees of a partition (kernel_process_forest.hip).  Two
+// Calls as above: the inputs and the call's own block first -- [verdict] [Tree x T] [branch_first] [leaf_first], the tables, the
+// leaves' owner words, the cells' derived arrays -- so that ONE read-back carries the forest's verdict and the cells' before an
+// output is declared.  Behind it: level_support, ONE expand_init / refinement / expand_gate over all rows (the rows of a cell that
+// builds nothing are skipped, as hpmvs_expand_batch skips them), the decisions, regularize against them, and the sweep's
+// setDepths calls gathered on the device into ONE ordered replay.  Two more words come back mid-call, as in
+// hpmvs_depth_ops_batch: the number of op rows and the number of depth keys, which size the gather and the sort.
+int hpmvs_process_forest_batch(hpmvs_scene* s, const hpmvs_options* o, const hpmvs_octree_forest* f, const float* leaf_patch_center,
+                               const hpmvs_patch_batch* cells, const int32_t* cell_tree, const uint64_t* cell_key, float* flatness,
+                               const uint8_t* final_level, hpmvs_patch_batch* out, const hpmvs_process_forest_result* res, int on_device,
+                               void* stream) {
+    const std::string who = "process_forest_batch";
+    if (hpmvs_device_count() <= 0) return fail(HPMVS_ERR_NODEVICE, who + ": no HIP device visible");
+    int rc = check_batch(s, o, cells);
+    if (rc) return rc;
+    if ((rc = check_batch_shape(s, o, out))) return rc;
+    if (!f) return fail(HPMVS_ERR_ARG, who + ": null forest");
+    if (!s->depth_pool || !s->ddepth) return fail(HPMVS_ERR_STATE, who + ": call hpmvs_scene_depth_reset first");
+    if (s->depth_floats >= ((size_t)1 << 32)) return fail(HPMVS_ERR_STATE, who + ": the scene's depth maps hold 2^32 cells or more");
+    const size_t n = (size_t)cells->n, M = (size_t)cells->max_images;
+    if ((size_t)out->n != 4 * n) return fail(HPMVS_ERR_ARG, who + ": out->n must be 4 * cells->n");
+    if (out->max_images != cells->max_images) return fail(HPMVS_ERR_ARG, who + ": max_images mismatch");
+    if (5 * n * M >= ((size_t)1 << 28)) return fail(HPMVS_ERR_ARG, who + ": 5 * n * max_images must stay below 2^28 (run the sweep in pieces: the order between pieces is kept)");
+    if (n > 0 && (!out->center || !out->normal || !out->scale || !out->n_images || !out->images || !out->ok))
+        return fail(HPMVS_ERR_ARG, who + ": missing array");
+    if (n > 0 && (!cell_tree || !cell_key || !flatness || !final_level)) return fail(HPMVS_ERR_ARG, who + ": cell_tree / cell_key / flatness / final_level missing");
+    const int T = f->n_trees;
+    if (T < 0) return fail(HPMVS_ERR_ARG, who + ": negative count");
+    if (T == 0 && n > 0) return fail(HPMVS_ERR_ARG, who + ": cell 0: cell_tree is outside [0, n_trees): the forest has no tree");
+    if (T > 0 && (!f->root || !f->branch_first || !f->leaf_first)) return fail(HPMVS_ERR_ARG, who + ": root / branch_first / leaf_first missing");
+    if (T == 0) return HPMVS_OK;
+    if ((rc = forest_host_check(who, f))) return rc;
+    const size_t nb = (size_t)f->branch_first[T], nl = (size_t)f->leaf_first[T];
+    if (nl > 0 && n > 0 && !leaf_patch_center) return fail(HPMVS_ERR_ARG, who + ": leaf_patch_center missing");
+    std::vector<uint64_t> slot_first((size_t)T + 1);
+    octree::forest_slots(T, f->branch_first, f->leaf_first, slot_first.data());
+    const size_t slots = (size_t)slot_first[T];
+    const size_t o_trees = reg_align(sizeof(uint32_t) * kForestWords), o_bf = reg_align(o_trees + sizeof(octree::Tree) * T),
+                 o_lf = reg_align(o_bf + 4 * ((size_t)T + 1)), o_keys = reg_align(o_lf + 4 * ((size_t)T + 1)),
+                 o_vals = reg_align(o_keys + 8 * slots), o_own = reg_align(o_vals + 4 * slots), o_gl = reg_align(o_own + 4 * nl),
+                 o_cc = reg_align(o_gl + 4 * n), o_cw = reg_align(o_cc + 12 * n), o_skip = reg_align(o_cw + 4 * n),
+                 o_cnt = reg_align(o_skip + 4 * n), o_first = reg_align(o_cnt + 4 * (n + 1)), bytes = reg_align(o_first + 4 * (n + 1));
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    Call ck(s, on_device, st);
+    const unsigned long long* dbk = (const unsigned long long*)ck.in(f->branch_key, nb);
+    const unsigned long long* dlk = (const unsigned long long*)ck.in(f->leaf_key, nl);
+    const float* dlpc = ck.in(leaf_patch_center, n > 0 ? 3 * nl : 0);
+    const DevBatch P = ck.batch(cells, Call::kRead);
+    ProcessCells C;
+    memset(&C, 0, sizeof(C));
+    C.n = (int32_t)n; C.max_images = (int32_t)M;
+    C.cell_tree = ck.in(cell_tree, n);
+    C.cell_key = (const unsigned long long*)ck.in(cell_key, n);
+    float* dfl = ck.arr(flatness, n, Call::kCopyIn | Call::kCopyBack);
+    C.flatness = dfl; C.n_images = P.n_images; C.images = P.images;
+    const uint8_t* dfinal = ck.in(final_level, n);
+    char* w = (char*)ck.scratch(bytes);
+    if (!w) return ck.error();
+    size_t scan_bytes = 0;
+    if (process_scan(nullptr, &scan_bytes, nullptr, nullptr, (int)n + 1, st) != 0) return fail(HPMVS_ERR_HIP, who + ": rocPRIM size query failed");
+    void* scan_temp = ck.scratch(scan_bytes ? scan_bytes : 1);
+    if (!scan_temp) return ck.error();
+    std::vector<char> hdr(o_keys, 0);
+    for (int v = 0; v < kForestWords; v++) ((uint32_t*)hdr.data())[v] = octree::kForestGood;
+    octree::Tree* ht = (octree::Tree*)(hdr.data() + o_trees);
+    for (int k = 0; k < T; k++) {
+        const float* r = f->root + 4 * (size_t)k;
+        ht[k].root = octree::Cell{{r[0], r[1], r[2]}, r[3]};
+        ht[k].t = octree::Table{(const uint64_t*)(w + o_keys) + slot_first[k], (const int32_t*)(w + o_vals) + slot_first[k],
+                                (uint32_t)(slot_first[k + 1] - slot_first[k])};
+    }
+    memcpy(hdr.data() + o_bf, f->branch_first, 4 * ((size_t)T + 1));
+    memcpy(hdr.data() + o_lf, f->leaf_first, 4 * ((size_t)T + 1));
+    uint32_t* verdict = (uint32_t*)w;
+    const octree::Tree* dtrees = (const octree::Tree*)(w + o_trees);
+    const int32_t* dlf = (const int32_t*)(w + o_lf);
+    C.owner = (int32_t*)(w + o_own); C.gleaf = (int32_t*)(w + o_gl);
+    C.cell_center = (float*)(w + o_cc); C.cell_width = (float*)(w + o_cw);
+    uint8_t* dskip = (uint8_t*)(w + o_skip);
+    int32_t* op_count = (int32_t*)(w + o_cnt);
+    int32_t* op_first = (int32_t*)(w + o_first);
+    if ((rc = ck.begin(st))) return rc;
+    HIPCHK(hipMemcpyAsync(w, hdr.data(), o_keys, hipMemcpyHostToDevice, st));   // (pageable: consumed before it returns)
+    HIPCHK(hipMemsetAsync(w + o_keys, 0, 8 * slots, st));
+    if (nl) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)C.owner, octree::kNoOwner, nl, st));
+    launch_forest_build(T, (const int32_t*)(w + o_bf), dlf, dbk, dlk, (int)(nb + nl), dtrees, verdict, st);
+    HIPCHK(hipGetLastError());
+    launch_process_cells(T, dtrees, dlf, s->n_views, C, verdict, st);
+    HIPCHK(hipGetLastError());
+    uint32_t h[kForestWords];
+    HIPCHK(hipMemcpyAsync(h, verdict, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (h[kForestTable] != octree::kForestGood) return forest_table_fail(who, h[kForestTable]);
+    if (h[kForestParent] != octree::kForestGood) {
+        const std::string cell = who + ": cell " + std::to_string(h[kForestParent] >> 3);
+        switch (h[kForestParent] & 7u) {
+            case octree::kCellTree: return fail(HPMVS_ERR_ARG, cell + ": cell_tree is outside [0, n_trees)");
+            case octree::kCellLeaf: return fail(HPMVS_ERR_ARG, cell + ": cell_key is no nonempty leaf of its tree");
+            case octree::kCellTwice: return fail(HPMVS_ERR_ARG, cell + ": its leaf belongs to an earlier cell already (a leaf changes at most once per sweep)");
+            case octree::kCellDeep: return fail(HPMVS_ERR_ARG, cell + ": a leaf at depth 21 cannot be branched");
+            default: return fail(HPMVS_ERR_ARG, cell + ": a regularized cell's reference image is not a view of the scene");
+        }
+    }
+    if (n == 0) return ck.finish();
+    Call c(s, on_device, st);
+    const DevBatch D = c.batch(out, Call::kCreate);
+    static const hpmvs_process_forest_result none = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const hpmvs_process_forest_result& R = res ? *res : none;
+    // what the sweep itself needs lives in scratch where the caller does not ask for it
+    auto result = [&c](auto* given, size_t count) {
+        auto* p = c.arr(given, count, Call::kCopyBack);
+        return p ? p : (decltype(p))c.scratch(sizeof(*p) * count);
+    };
+    int32_t* dsup = result(R.support, n);
+    C.removed = result(R.removed, n);
+    C.split = result(R.split, n);
+    C.children = result(R.children, 4 * n);
+    C.child_key = (unsigned long long*)result(R.child_key, 4 * n);
+    int32_t* dnn = c.arr(R.n_neighbours, n, Call::kCopyBack);
+    unsigned long long* dnk = (unsigned long long*)c.arr(R.neighbour_key, 24 * n, Call::kCopyBack);
+    if (c.error()) return c.error();
+    if ((rc = c.begin(st))) return rc;
+    const DevOptions d = make_dev_options(o);
+    const DevScene sc = dev_scene(s);
+    launch_level_support(sc, P, o->MINLEVEL, dsup, st);
+    HIPCHK(hipGetLastError());
+    launch_process_skip(C, dsup, dskip, st);
+    HIPCHK(hipGetLastError());
+    {
+        std::lock_guard<std::recursive_mutex> lk(s->mu);
+        launch_expand_init(sc, HPMVS_EXPAND_BRANCH, (int)n, P, C.cell_center, C.cell_width, dskip, D, st);
+        HIPCHK(hipGetLastError());
+        if ((rc = enqueue_refinement(s, d, D, st))) return rc;
+        launch_expand_gate(HPMVS_EXPAND_BRANCH, (int)n, P, C.cell_center, C.cell_width, D, st);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemsetAsync(op_count + n, 0, 4, st));
+    launch_process_decide(C, dsup, dskip, dfinal, D, op_count, st);
+    HIPCHK(hipGetLastError());
+    launch_regularize_forest(sc, dtrees, dlf, dlpc, C, P, D, dfl, dnn, dnk, st);
+    HIPCHK(hipGetLastError());
+    if (process_scan(scan_temp, &scan_bytes, op_count, op_first, (int)n + 1, st) != 0) return fail(HPMVS_ERR_HIP, who + ": rocPRIM scan failed");
+    int32_t n_ops = 0;   // the op batch's size depends on it: read back mid-call
+    HIPCHK(hipMemcpyAsync(&n_ops, op_first + n, sizeof(n_ops), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (n_ops > 0) {
+        const size_t m = (size_t)n_ops, cap = m * M;
+        DevBatch ops;
+        memset(&ops, 0, sizeof(ops));
+        ops.n = n_ops; ops.max_images = (int32_t)M;
+        char* ob = (char*)c.scratch(reg_align(16 * m) * 2 + reg_align(4 * m) * 2 + reg_align(4 * cap) + reg_align(m));
+        unsigned long long* keys = (unsigned long long*)c.scratch(cap * sizeof(unsigned long long));
+        unsigned long long* sorted = (unsigned long long*)c.scratch(cap * sizeof(unsigned long long));
+        unsigned int* counter = (unsigned int*)c.scratch(sizeof(unsigned int));
+        if (c.error()) return c.error();
+        ops.center = (float*)ob; ops.normal = (float*)(ob + reg_align(16 * m)); ops.scale = (float*)((char*)ops.normal + reg_align(16 * m));
+        ops.n_images = (int32_t*)((char*)ops.scale + reg_align(4 * m)); ops.images = (int32_t*)((char*)ops.n_images + reg_align(4 * m));
+        uint8_t* dsub = (uint8_t*)((char*)ops.images + reg_align(4 * cap));
+        launch_process_gather(C, op_first, P, D, ops, dsub, st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned int), st));
+        launch_depth_ops_keys(sc, s->ddepth, s->depth_pool, ops, keys, counter, st);
+        HIPCHK(hipGetLastError());
+        unsigned int count = 0;  // the sort's size depends on it
+        HIPCHK(hipMemcpyAsync(&count, counter, sizeof(count), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (count > 0) {
+            size_t temp_bytes = 0;
+            if (depth_ops_sort(nullptr, &temp_bytes, keys, sorted, count, st) != 0) return fail(HPMVS_ERR_HIP, who + ": rocPRIM size query failed");
+            void* temp = c.scratch(temp_bytes ? temp_bytes : 1);
+            if (!temp) return c.error();
+            if (depth_ops_sort(temp, &temp_bytes, keys, sorted, count, st) != 0) return fail(HPMVS_ERR_HIP, who + ": rocPRIM sort failed");
+            launch_depth_ops_apply(sc, s->ddepth, s->depth_pool, ops, dsub, sorted, count, st);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    if ((rc = c.finish())) return rc;
+    return ck.finish();   // (waits in both forms: the tables are freed when this call returns; flatness travels back here)
 }
 // CellProcessor::processBorderCellQueue's insertion loop (CellProcessor.cpp:500-531): addConditional(points[i], add_width[i]) for
 // i = 0 .. n - 1 IN THAT ORDER against the tree t, which stays the caller's (kernel_octree_insert.hip: static kernel, stable sort by

@@ -167,6 +167,36 @@ void launch_extend_forest_pre(const octree::Tree* trees, const int32_t* parent_t
 void launch_extend_forest_post(const octree::Tree* trees, const int32_t* parent_tree, int n, float width, const DevBatch& out,
                                const ExtendTreeOut& k, hipStream_t st);
 
+// one regularize / settle sweep over a forest (kernel_process_forest.hip, include/hpmvs_amd.h: hpmvs_process_forest_batch),
+// against the tables launch_forest_build made.  Everything is on the device.  launch_process_cells folds what it finds wrong with
+// a row into verdict[kForestParent] as octree::cell_finding (owner: [all leaves], every word octree::kNoOwner before); the other
+// launches go only behind a good verdict, in the order they stand here: skip behind launch_level_support, decide behind
+// launch_expand_gate (it reads out.ok / out.center), regularize behind decide, gather behind the exclusive scan of op_count.
+struct ProcessCells {
+    int32_t n, max_images;
+    const int32_t* cell_tree; const unsigned long long* cell_key; const float* flatness;   // [n] the call's inputs
+    const int32_t* n_images; const int32_t* images;                                        // of the cells' patches
+    int32_t* gleaf;              // [n] the cell's leaf among all leaves of the forest
+    int32_t* owner;              // [all leaves] the row that owns the leaf
+    float* cell_center;          // [n][3] Cell::c_ by the key
+    float* cell_width;           // [n]
+    uint8_t* removed; uint8_t* split; uint8_t* children; unsigned long long* child_key;   // [n], [n], [n][4], [n][4]
+};
+void launch_process_cells(int n_trees, const octree::Tree* trees, const int32_t* leaf_first, int n_views, const ProcessCells& c,
+                          uint32_t* verdict, hipStream_t st);
+void launch_process_skip(const ProcessCells& c, const int32_t* support, uint8_t* skip, hipStream_t st);
+void launch_process_decide(const ProcessCells& c, const int32_t* support, const uint8_t* skip, const uint8_t* final_level, const DevBatch& out,
+                           int32_t* op_count, hipStream_t st);
+// flatness_out may be c.flatness: a cell's lanes have read its entry before its first lane writes it
+void launch_regularize_forest(const DevScene& sc, const octree::Tree* trees, const int32_t* leaf_first, const float* leaf_patch_center,
+                              const ProcessCells& c, const DevBatch& par, const DevBatch& out, float* flatness_out, int32_t* n_neighbours,
+                              unsigned long long* neighbour_key, hipStream_t st);
+// exclusive scan of n ints; temp == nullptr: only reports the temporary bytes rocPRIM needs.  != 0: the rocPRIM call failed
+int process_scan(void* temp, size_t* temp_bytes, const int32_t* in, int32_t* out, int n, hipStream_t st);
+// ops: op_first[n] rows of max_images ids each (wider lists do not occur: out has the cells' max_images), -1 padded
+void launch_process_gather(const ProcessCells& c, const int32_t* op_first, const DevBatch& par, const DevBatch& out, const DevBatch& ops,
+                           uint8_t* subtract, hipStream_t st);
+
 // a round's border patches (kernel_octree_insert.hip, include/hpmvs_amd.h: hpmvs_octree_route_batch, hpmvs_octree_insert_batch).
 // launch_octree_insert reads the table launch_octree_build made and enqueues static kernel, sort and replay on st; != 0: the
 // rocPRIM call failed.  Every entry of every output is written (blocker is nullable).  roots: [n_trees][4] c_, width_ on the device.

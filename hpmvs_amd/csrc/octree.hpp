@@ -3,7 +3,7 @@
 // once for the device kernels (kernel_octree.hip, kernel_octree_insert.hip) and for the host restatements the tests compile with
 // g++ (tests/octree_host.cpp, tests/octree_insert_host.cpp).  DESIGN.md §3.11 has the argument; §3.12 the one for inserting a
 // round's border patches in queue order (the second part of this file), §3.14 the one for the split into subtrees, §3.15 the one
-// for a forest of subtrees behind one table buffer (the last).
+// for a forest of subtrees behind one table buffer, §3.16 the one for the regularize / settle sweep over a forest (the last).
 //
 //   path key                 a sentinel bit, then 3 bits per level (z y x, Branch::at's child test x > c_): the root is 1, a cell
 //                            at depth d has 3 d bits below the sentinel; at most kMaxDepth = 21 levels (kernel_regularize.hip's form)
@@ -15,6 +15,7 @@
 //   addConditional(e, w)     refuses on a nonempty leaf or one with width_ < w; else splits while width_ / 2.0 > w
 // Build with -ffp-contract=off.
 #pragma once
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <unordered_map>
@@ -495,6 +496,157 @@ inline uint32_t forest_build_sequential(int32_t n_trees, const float* roots, con
         if (v < verdict) verdict = v;
     }
     return verdict;
+}
+
+// ---- one regularize / settle sweep of processCell over a forest, in queue order (hpmvs_process_forest_batch, reference
+// CellProcessor.cpp:309-420).  A leaf changes at most once per sweep, and only its own cell changes it, so the
+// tree as it stands at queue position q is the tree of the call plus ONE word per nonempty leaf -- the row of the cell that owns
+// it -- and that row's decision: removed (the leaf is empty from then on) or split (it is a branch whose nonempty children are
+// named by child_key).  Children born in the sweep are reachable only through their split parent: nothing enters the tables.
+constexpr int32_t kNoOwner = 0x7fffffff;   // a leaf no cell of the sweep owns
+HPMVS_OT_FN bool process_regularized(float flatness) { return flatness < 0.0f; }            // :399 (NaN is settled)
+HPMVS_OT_FN bool process_removed(float flatness) { return (double)flatness > 2.4; }          // :409, float against double
+HPMVS_OT_FN bool process_split(bool removed, int32_t support, bool final_level, int n_children) {   // branch, :221-224, :265-266
+    return !removed && support >= 1 && !(final_level && n_children == 0);
+}
+// the leaf a child of a split cell goes into: Branch::at of the new branch
+HPMVS_OT_FN uint64_t process_child_key(uint64_t cell_key, const Cell& cell, const float* p) { return (cell_key << 3) | octant(cell, p); }
+// setDepths calls of one cell, in order: the cell's patch with subtract (removed or split), then a split cell's children in k order
+HPMVS_OT_FN int process_op_count(bool removed, bool split, int n_children) { return removed ? 1 : split ? 1 + n_children : 0; }
+// what the cell kernel finds wrong with a row, folded with min as (row << 3 | kind): the lowest row first
+constexpr uint32_t kCellTree = 0, kCellLeaf = 1, kCellTwice = 2, kCellDeep = 3, kCellRef = 4;
+HPMVS_OT_FN uint32_t cell_finding(int32_t row, uint32_t kind) { return ((uint32_t)row << 3) | kind; }
+
+struct Sweep {
+    const int32_t* owner;        // [all leaves of the forest] the row that owns the leaf, kNoOwner
+    const uint8_t* removed;      // [n]
+    const uint8_t* split;        // [n]
+    const uint8_t* children;     // [n][4]
+    const uint64_t* child_key;   // [n][4]
+};
+struct Probe {
+    uint64_t key;      // of the leaf the probe ends in
+    int32_t leaf;      // its index among ALL leaves of the forest when it is a nonempty leaf of the call's tree, else kAbsent
+    int32_t child;     // row 4 j + k of the children when it is a leaf born in this sweep, else -1
+};
+// ptree->at(p) in the tree as it stands at queue position q; leaf_base = leaf_first[tree]
+HPMVS_OT_FN Probe locate_versioned(const Tree& tr, int32_t leaf_base, const Sweep& s, int32_t q, const float* p) {
+    const Located l = locate(tr.root, tr.t, p);
+    Probe r{l.key, kAbsent, -1};
+    if (l.index < 0) return r;   // (an empty leaf; kBranch: a branch at depth 21 cannot be in a checked table)
+    const int32_t g = leaf_base + l.index, j = s.owner[g];
+    if (j >= q) { r.leaf = g; return r; }              // untouched so far (kNoOwner is above every q)
+    if (s.removed[j]) return r;
+    if (!s.split[j]) { r.leaf = g; return r; }
+    r.key = process_child_key(l.key, l.cell, p);        // one more step of Branch::at
+    for (int k = 0; k < 4; k++)
+        if (s.children[4 * (size_t)j + k] && s.child_key[4 * (size_t)j + k] == r.key) { r.child = 4 * j + k; return r; }
+    return r;
+}
+
+// CellProcessor::regularize's arithmetic (:318-366), float as the reference's Eigen expressions evaluate
+HPMVS_OT_FN float ot_dot3(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+HPMVS_OT_FN void ot_cross3(const float* a, const float* b, float* r) {
+    const float r0 = a[1] * b[2] - a[2] * b[1], r1 = a[2] * b[0] - a[0] * b[2], r2 = a[0] * b[1] - a[1] * b[0];
+    r[0] = r0; r[1] = r1; r[2] = r2;
+}
+HPMVS_OT_FN void ot_normalized3(const float* a, float* r) {
+    const float n2 = ot_dot3(a, a);
+    if (n2 > 0.0f) { const float n = sqrtf(n2); r[0] = a[0] / n; r[1] = a[1] / n; r[2] = a[2] / n; }
+    else { r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; }
+}
+// probe `lane` of 24 (yy outer, xx inner, (0, 0) left out) of the patch (x0, normal pn) whose reference view has the x axis cam_x
+HPMVS_OT_FN void regularize_probe(const float* x0, const float* pn, const float* cam_x, float width, int lane, float* p) {
+    float t0[3], yaxis[3], xaxis[3];
+    ot_cross3(pn, cam_x, t0);
+    ot_normalized3(t0, yaxis);
+    ot_cross3(yaxis, pn, xaxis);
+    const int k = lane < 12 ? lane : lane + 1;
+    const float fy = (float)(k / 5 - 2), fx = (float)(k % 5 - 2);
+    for (int j = 0; j < 3; j++) p[j] = x0[j] + (fx * xaxis[j] + fy * yaxis[j]) * width;
+}
+// the squared plane distance of a neighbour's data[0]->center_ (nn: the normalized normal)
+HPMVS_OT_FN float regularize_err2(const float* nn, const float* x0, const float* pc) {
+    const float b[3] = {pc[0] - x0[0], pc[1] - x0[1], pc[2] - x0[2]};
+    const float e = ot_dot3(nn, b);
+    return e * e;
+}
+HPMVS_OT_FN float regularize_flatness(int cnt, float dist, float width) {
+    if (cnt < 1) return 2.6f;
+    if (cnt < 4) return 2.5f;
+    return sqrtf(dist / (float)cnt) / width;
+}
+
+// The sweep on one thread: the host restatement the tests load, row by row as the reference's queue runs.  What the refinement
+// decides is an input here: support [n], child_ok [n][4] (the child was built, refined and passed both gates), child_center
+// [n][4][3].  cam_x: [n][3] the x axis of every cell's reference view.  ops: the setDepths calls in order, a cell's own patch as
+// its row i, child k of cell i as n + 4 i + k; op_subtract beside it.  Returns kForestGood or the cell finding.
+inline uint32_t process_sequential(int32_t n_trees, const Tree* trees, const int32_t* leaf_first, const float* leaf_patch_center, int32_t n,
+                                   const float* center, const float* normal, const float* cam_x, const uint8_t* ref_ok,
+                                   const int32_t* cell_tree, const uint64_t* cell_key, float* flatness, const uint8_t* final_level,
+                                   const int32_t* support, const uint8_t* child_ok, const float* child_center, uint8_t* removed,
+                                   uint8_t* split, uint8_t* children, uint64_t* child_key, int32_t* n_neighbours, uint64_t* neighbour_key,
+                                   std::vector<int32_t>* ops, std::vector<uint8_t>* op_subtract) {
+    std::vector<int32_t> owner(n_trees > 0 ? (size_t)leaf_first[n_trees] : 0, kNoOwner), gleaf((size_t)n, -1);
+    uint32_t verdict = kForestGood;
+    auto find_bad = [&](int32_t i, uint32_t kind) { if (cell_finding(i, kind) < verdict) verdict = cell_finding(i, kind); };
+    for (int32_t i = 0; i < n; i++) {
+        const int32_t k = cell_tree[i];
+        if (k < 0 || k >= n_trees) { find_bad(i, kCellTree); continue; }
+        const int32_t idx = key_depth(cell_key[i]) < 1 ? kAbsent : find(trees[k].t, cell_key[i]);
+        if (idx < 0) { find_bad(i, kCellLeaf); continue; }
+        gleaf[i] = leaf_first[k] + idx;
+        if (owner[gleaf[i]] != kNoOwner) find_bad(i, kCellTwice); else owner[gleaf[i]] = i;
+        const bool reg = process_regularized(flatness[i]);
+        if (!reg && !process_removed(flatness[i]) && key_depth(cell_key[i]) >= kMaxDepth) find_bad(i, kCellDeep);
+        if (reg && !ref_ok[i]) find_bad(i, kCellRef);
+    }
+    if (verdict != kForestGood) return verdict;
+    const Sweep sw{owner.data(), removed, split, children, child_key};
+    for (int32_t i = 0; i < n; i++) {
+        removed[i] = split[i] = 0;
+        for (int k = 0; k < 4; k++) { children[4 * (size_t)i + k] = 0; child_key[4 * (size_t)i + k] = 0; }
+        for (int k = 0; k < 24; k++) neighbour_key[24 * (size_t)i + k] = 0;
+        n_neighbours[i] = -2;
+        const Tree& tr = trees[cell_tree[i]];
+        const Cell cell = key_cell(tr.root, cell_key[i]);
+        const float* x0 = center + 4 * (size_t)i;
+        const float* pn = normal + 4 * (size_t)i;
+        if (process_regularized(flatness[i])) {
+            float nn[3], dist = 0.0f;
+            ot_normalized3(pn, nn);
+            int cnt = 0;
+            for (int lane = 0; lane < 24; lane++) {
+                float p[3];
+                regularize_probe(x0, pn, cam_x + 3 * (size_t)i, cell.w, lane, p);
+                const Probe pr = locate_versioned(tr, leaf_first[cell_tree[i]], sw, i, p);
+                if (pr.leaf == kAbsent && pr.child < 0) continue;
+                bool first = true;
+                for (int j = 0; j < cnt && first; j++) first = neighbour_key[24 * (size_t)i + j] != pr.key;
+                if (!first) continue;
+                neighbour_key[24 * (size_t)i + cnt++] = pr.key;
+                dist += regularize_err2(nn, x0, pr.child >= 0 ? child_center + 3 * (size_t)pr.child : leaf_patch_center + 3 * (size_t)pr.leaf);
+            }
+            n_neighbours[i] = cnt;
+            flatness[i] = regularize_flatness(cnt, dist, cell.w);
+            continue;
+        }
+        removed[i] = process_removed(flatness[i]) ? 1 : 0;
+        int nc = 0;
+        if (!removed[i] && support[i] >= 1)
+            for (int k = 0; k < 4; k++)
+                if (child_ok[4 * (size_t)i + k]) { children[4 * (size_t)i + k] = 1; nc++; }
+        split[i] = process_split(removed[i] != 0, support[i], final_level[i] != 0, nc) ? 1 : 0;
+        if (!split[i])
+            for (int k = 0; k < 4; k++) children[4 * (size_t)i + k] = 0;   // (a final-level leaf without children keeps its patch)
+        for (int k = 0; k < 4; k++)
+            if (children[4 * (size_t)i + k]) child_key[4 * (size_t)i + k] = process_child_key(cell_key[i], cell, child_center + 3 * (4 * (size_t)i + k));
+        if (process_op_count(removed[i] != 0, split[i] != 0, nc)) { ops->push_back(i); op_subtract->push_back(1); }
+        if (split[i])
+            for (int k = 0; k < 4; k++)
+                if (children[4 * (size_t)i + k]) { ops->push_back(n + 4 * i + k); op_subtract->push_back(0); }
+    }
+    return kForestGood;
 }
 
 }  // namespace octree

@@ -905,6 +905,20 @@ def filter_extend_level_tree(scene: api.Scene, patches: api.Batch, cell_start, w
 
 # ---- a level over all subtrees at once --------------------------------------------------------------
 
+def _flatten_forest(trees):
+    """A list of Octree as hpmvs_octree_forest takes it: (roots [n, 4], branch_first, leaf_first, branch_key, leaf_key), every
+    tree's leaves in leaf_table() order."""
+    n = len(trees)
+    bk = [t.branch_keys() for t in trees]
+    lk = [t.leaf_table()[0] for t in trees]
+    roots = np.array([[*t.root_center, t.root_width] for t in trees], np.float32).reshape(n, 4)
+    branch_first = np.concatenate([[0], np.cumsum([len(a) for a in bk])]).astype(np.int32)
+    leaf_first = np.concatenate([[0], np.cumsum([len(a) for a in lk])]).astype(np.int32)
+    branch_key = np.concatenate(bk + [np.zeros(0, np.uint64)]).astype(np.uint64)
+    leaf_key = np.concatenate(lk + [np.zeros(0, np.uint64)]).astype(np.uint64)
+    return roots, branch_first, leaf_first, branch_key, leaf_key
+
+
 class _ForestKeys:
     """_TreeKeys for a list of Octree objects: ONE hpmvs_extend_forest_batch per level serves every tree.  The walk's leaf keys
     are (tree, key) pairs, so equal sub-keys of two subtrees stay distinct; a refusal stays REFUSED whatever the tree, and
@@ -926,13 +940,7 @@ class _ForestKeys:
                 w = np.float32(float(w) / 2.0); d += 1
             if w != self.width or d < 1:
                 raise ValueError(f"extend_level_forest: `width` is not the width of a level of tree {int(k)}")
-        bk = [t.branch_keys() for t in self.trees]
-        lk = [t.leaf_table()[0] for t in self.trees]
-        self.roots = np.array([[*t.root_center, t.root_width] for t in self.trees], np.float32).reshape(n, 4)
-        self.branch_first = np.concatenate([[0], np.cumsum([len(a) for a in bk])]).astype(np.int32)
-        self.leaf_first = np.concatenate([[0], np.cumsum([len(a) for a in lk])]).astype(np.int32)
-        self.branch_key = np.concatenate(bk + [np.zeros(0, np.uint64)]).astype(np.uint64)
-        self.leaf_key = np.concatenate(lk + [np.zeros(0, np.uint64)]).astype(np.uint64)
+        self.roots, self.branch_first, self.leaf_first, self.branch_key, self.leaf_key = _flatten_forest(self.trees)
 
     def candidates(self, scene, parents, width, o):
         out, k = api.extend_forest_batch(scene, parents, self.parent_tree, self.width, self.roots, self.branch_first, self.leaf_first,
@@ -986,6 +994,81 @@ def filter_extend_level_forest(scene: api.Scene, patches: api.Batch, cell_start,
                           "filter_extend_level_forest")
     _insert_accepted_forest(keys.trees, keys, L, rows)
     return F, L
+
+
+# ---- the regularize / settle sweep over all subtrees at once ----------------------------------------
+
+@dataclass
+class ForestProcessResult:
+    flatness: np.ndarray           # [n] flatness_ after the sweep (regularized cells updated, the others as given)
+    n_neighbours: np.ndarray       # [n] neighbour leaves of the regularized cells (-2: settled)
+    neighbour_key: np.ndarray      # [n, 24] their keys in the cell's own tree, first-probe order, 0-padded (None unless asked for)
+    candidates: api.Batch          # the 4 n branch children (stage 20: not built / not refined)
+    support: np.ndarray            # [n] Scene::getLevelSupport of every cell's patch
+    removed: np.ndarray            # [n] 1: flatness_ > 2.4, the patch was removed and the leaf emptied
+    split: np.ndarray              # [n] 1: the leaf was split
+    children: np.ndarray           # [n, 4] bool: the children that went into the new leaves
+    child_key: np.ndarray          # [n, 4] the key in the cell's tree of the leaf child k went into (0: none)
+
+
+def apply_sweep(trees, cell_tree, cell_key, removed, split, children, child_key, rows=None):
+    """A sweep's removals and splits applied to the Octree objects in row order: remove(key) for a removed cell; split(key) for a
+    split one and insert(child_key, row) for the FIRST child (in k order) of every new leaf -- data[0], the one regularize
+    reads.  The row is rows[4 i + k], or ("branch", 4 i + k)."""
+    for i in range(len(cell_key)):
+        t, key = trees[int(cell_tree[i])], int(cell_key[i])
+        if removed[i]:
+            t.remove(key)
+        elif split[i]:
+            t.split(key)
+            for k in range(4):
+                ck = int(child_key[i][k])
+                if children[i][k] and ck not in t.leaves:
+                    t.insert(ck, rows[4 * i + k] if rows is not None else ("branch", 4 * i + k))
+
+
+def process_level_forest(scene: api.Scene, cells: api.Batch, cell_tree, cell_key, flatness, trees, patch_center, final_level=None,
+                         patch_final_minlevel=None, options=None, neighbours: bool = False, rows=None) -> ForestProcessResult:
+    """process_level for ALL subtrees of a partition as ONE hpmvs_process_forest_batch: `cells` are the trees' queues one after
+    the other (cell_tree non-decreasing, ValueError otherwise), cell i being data[0] of the nonempty leaf cell_key[i] of
+    trees[cell_tree[i]]; `trees` a list of Octree such as Partition.trees.  The tree travels as its key sets: no cell centres, no
+    snapshot.  patch_center: a function or dict from (tree, key) to data[0]->center_ of that leaf.  final_level[i]:
+    nodeLevel(cell i) >= PATCH_FINAL_MINLEVEL, by default tree.node_level(key) >= patch_final_minlevel.  Equals the per-tree loop
+    process_level on tree 0, then tree 1, and so on, from the same starting maps.  Afterwards the removals and splits are applied
+    to the Octree objects in row order (apply_sweep)."""
+    trees = list(trees)
+    n = cells.n
+    ct = np.ascontiguousarray(cell_tree, dtype=np.int32).reshape(-1)
+    ck = np.ascontiguousarray(cell_key, dtype=np.uint64).reshape(-1)
+    if len(ct) != n or len(ck) != n:
+        raise ValueError("process_level_forest: cell_tree / cell_key need one entry per cell")
+    if n and (ct.min() < 0 or ct.max() >= len(trees)):
+        raise ValueError("process_level_forest: a cell's tree is outside the list of trees")
+    if (np.diff(ct) < 0).any():
+        raise ValueError("process_level_forest: cell_tree must not decrease (the queue is the trees' queues in list order)")
+    if final_level is None:
+        if patch_final_minlevel is None:
+            raise ValueError("process_level_forest: give final_level or patch_final_minlevel")
+        final_level = [trees[ct[i]].node_level(int(ck[i])) >= int(patch_final_minlevel) for i in range(n)]
+    roots, bf, lf, bk, lk = _flatten_forest(trees)
+    center = patch_center.__getitem__ if isinstance(patch_center, dict) else patch_center
+    pc = np.zeros((len(lk), 3), np.float32)
+    for t in range(len(trees)):
+        for l in range(int(lf[t]), int(lf[t + 1])):
+            pc[l] = np.asarray(center((t, int(lk[l]))), dtype=np.float32)[:3]
+    r = api.process_forest_batch(scene, cells, ct, ck, flatness, final_level, roots, bf, lf, bk, lk, pc, options=options,
+                                 neighbours=neighbours)
+    apply_sweep(trees, ct, ck, r.removed, r.split, r.children, r.child_key, rows)
+    return ForestProcessResult(r.flatness, r.n_neighbours, r.neighbour_key, r.candidates, r.support, r.removed, r.split,
+                               r.children.astype(bool), r.child_key)
+
+
+def process_level_tree(scene: api.Scene, cells: api.Batch, cell_key, flatness, tree: Octree, patch_center, final_level=None,
+                       patch_final_minlevel=None, options=None, neighbours: bool = False, rows=None) -> ForestProcessResult:
+    """process_level_forest for one tree; patch_center: a function or dict from the key to data[0]->center_."""
+    center = patch_center.__getitem__ if isinstance(patch_center, dict) else patch_center
+    return process_level_forest(scene, cells, np.zeros(cells.n, np.int32), cell_key, flatness, [tree], lambda tk: center(tk[1]),
+                                final_level, patch_final_minlevel, options, neighbours, rows)
 
 
 # ---- a round's border patches (DESIGN.md section 3.12; reference CellProcessor.cpp:487-540) ---------------------------------

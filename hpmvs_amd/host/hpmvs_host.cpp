@@ -1713,6 +1713,95 @@ bool PatchOptimizer::processLevel(mo3d::Patch3d* const* cells, const int32_t* ce
     return true;
 }
 
+bool PatchOptimizer::processLevelForest(mo3d::Patch3d* const* cells, const int32_t* cellTree, const uint64_t* cellKey, size_t n,
+                                        const uint8_t* finalLevel, const mo3d::OctreeForest& forest, const std::vector<float>& patchCenter,
+                                        ForestProcessResult& R) {
+    R = ForestProcessResult();
+    R.support.assign(n, 0); R.removed.assign(n, 0); R.split.assign(n, 0); R.child.assign(4 * n, 0); R.childKey.assign(4 * n, 0);
+    R.nNeighbours.assign(n, -2);
+    if (n == 0) return true;
+    for (size_t i = 1; i < n; i++)
+        if (cellTree[i] < cellTree[i - 1]) {
+            std::cerr << "hpmvs: processLevelForest: cellTree must not decrease (the queue is the trees' queues in list order)" << std::endl;
+            return false;
+        }
+    hpmvs_scene* dev = scene_p->deviceScene();
+    if (!dev) return false;
+    mo3d::OctreeForest::Flat flat;
+    forest.flatten(flat);
+    if (patchCenter.size() != 3 * flat.leafKey.size()) {
+        std::cerr << "hpmvs: processLevelForest: patchCenter needs 3 floats per leaf of the forest" << std::endl;
+        return false;
+    }
+    size_t longest_in = 0;
+    for (size_t i = 0; i < n; i++) longest_in = std::max(longest_in, cells[i]->images_.size());
+    const size_t m = 4 * n;
+    const int stride = list_stride(scene_p->cameras_.size(), m, longest_in);
+    const PinnedAlloc<char> pin(true);
+    PVec<float> pc(4 * n, pin), pn(4 * n, pin), ps(n, pin), fl(n, pin);
+    PVec<int32_t> pnimg(n, pin), pimg(n * stride, -1, pin), ptree(cellTree, cellTree + n, pin);
+    PVec<uint64_t> pkey(cellKey, cellKey + n, pin);
+    PVec<uint8_t> fin(n, pin);
+    for (size_t i = 0; i < n; i++) {
+        const Patch3d& p = *cells[i];
+        for (int k = 0; k < 4; k++) { pc[4 * i + k] = p.center_[k]; pn[4 * i + k] = p.normal_[k]; }
+        ps[i] = p.scale_3dx_;
+        pnimg[i] = (int32_t)p.images_.size();
+        for (size_t k = 0; k < p.images_.size() && k < (size_t)stride; k++) pimg[i * stride + k] = p.images_[k];
+        fl[i] = p.flatness_;
+        fin[i] = finalLevel ? finalLevel[i] : 0;
+    }
+    PVec<float> center(4 * m, pin), normal(4 * m, pin), scale(m, pin), color(3 * m, pin), ncc(m, pin);
+    PVec<int32_t> nimg(m, pin), images(m * stride, -1, pin), evals(m, pin), sup(n, pin), nn(n, pin);
+    PVec<double> fmin(m, pin);
+    PVec<uint8_t> accp(m, pin), rem(n, pin), spl(n, pin), chd(m, pin);
+    PVec<uint64_t> ckey(m, pin);
+    hpmvs_options o;
+    o.MAXLEVEL = options_p->MAXLEVEL; o.MINLEVEL = options_p->MINLEVEL;
+    o.MAX_ANGLE = options_p->MAX_ANGLE; o.MIN_ANGLE = options_p->MIN_ANGLE;
+    o.MAX_IMAGES_PER_PATCH = options_p->MAX_IMAGES_PER_PATCH; o.MIN_IMAGES_PER_PATCH = options_p->MIN_IMAGES_PER_PATCH;
+    o.NCC_ALPHA_1 = options_p->NCC_ALPHA_1; o.NCC_ALPHA_2 = options_p->NCC_ALPHA_2;
+    hpmvs_patch_batch pb, ob;
+    memset(&pb, 0, sizeof(pb));
+    memset(&ob, 0, sizeof(ob));
+    pb.n = (int32_t)n; pb.max_images = stride;
+    pb.center = pc.data(); pb.normal = pn.data(); pb.scale = ps.data(); pb.n_images = pnimg.data(); pb.images = pimg.data();
+    ob.n = (int32_t)m; ob.max_images = stride;
+    ob.center = center.data(); ob.normal = normal.data(); ob.scale = scale.data(); ob.n_images = nimg.data();
+    ob.images = images.data(); ob.ok = accp.data(); ob.color = color.data(); ob.ncc = ncc.data();
+    ob.fmin = fmin.data(); ob.nevals = evals.data();
+    hpmvs_octree_forest f;
+    f.n_trees = (int32_t)forest.trees.size();
+    f.root = flat.root.data(); f.branch_first = flat.branchFirst.data(); f.leaf_first = flat.leafFirst.data();
+    f.branch_key = flat.branchKey.data(); f.leaf_key = flat.leafKey.data();
+    const hpmvs_process_forest_result res = {sup.data(), rem.data(), spl.data(), chd.data(), ckey.data(), nn.data(), nullptr};
+    if (hpmvs_process_forest_batch(dev, &o, &f, patchCenter.data(), &pb, ptree.data(), pkey.data(), fl.data(), fin.data(), &ob, &res, 0, nullptr) !=
+        HPMVS_OK) {
+        std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl;
+        return false;
+    }
+    R.support.assign(sup.begin(), sup.end()); R.removed.assign(rem.begin(), rem.end()); R.split.assign(spl.begin(), spl.end());
+    R.child.assign(chd.begin(), chd.end()); R.childKey.assign(ckey.begin(), ckey.end()); R.nNeighbours.assign(nn.begin(), nn.end());
+    R.candidates.resize(m);
+    for (size_t t = 0; t < m; t++) {   // as expandBatch builds them: *newP = *p (CellProcessor.cpp:238)
+        Patch3d& q = R.candidates[t];
+        q = *cells[t / 4];
+        q.expanded_ = false;
+        q.flatness_ = -1.0f;
+        for (int k = 0; k < 4; k++) { q.center_[k] = center[4 * t + k]; q.normal_[k] = normal[4 * t + k]; }
+        q.scale_3dx_ = scale[t];
+        if (!accp[t]) continue;
+        q.images_.assign(images.begin() + t * stride, images.begin() + t * stride + nimg[t]);
+        q.ncc_ = ncc[t];
+        q.color_ = Eigen::Vector3f(color[3 * t], color[3 * t + 1], color[3 * t + 2]);
+    }
+    for (size_t i = 0; i < n; i++) {
+        if (R.nNeighbours[i] != -2) { cells[i]->flatness_ = fl[i]; cells[i]->priorityReduction_ = 0; }   // regularized (:399)
+        else if (R.removed[i] || R.split[i]) cells[i]->images_.clear();                                    // (:411, :279-280)
+    }
+    return true;
+}
+
 // The centres of a level's candidates BEFORE optimize (CellProcessor.cpp:103-116: the leaf look-up of :118-122 uses them): the device's
 // own construction with every candidate skipped, read back without building 6 n Patch3d objects, in rows just wide enough for the
 // parents' lists (nothing is refined, no list grows).  centers: 3 floats per candidate.

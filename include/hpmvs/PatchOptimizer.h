@@ -133,6 +133,24 @@ public:
     };
     bool processLevel(mo3d::Patch3d* const* cells, const int32_t* cellLeaf, size_t n, const uint8_t* finalLevel, const LeafTable& table,
                       ProcessResult& out);
+    // processLevel for ALL subtrees of a partition as ONE hpmvs_process_forest_batch (hpmvs_amd.frontier.process_level_forest: same
+    // call, same results): cells[i] is data[0] of the nonempty leaf cellKey[i] of forest.trees[cellTree[i]], the
+    // trees' queues one after the other (cellTree must not decrease, false otherwise).  The tree travels as its key sets -- no
+    // leaf table, no cell centres; patchCenter holds data[0]->center_ of every nonempty leaf, 3 floats each, in the order
+    // OctreeForest::flatten lists the leaves.  Thin marshalling: the sweep's decisions, regularize against the tree as it stands
+    // at every cell's turn and the ordered depth-map replay all happen in the one device call.  Written back: flatness_ and
+    // priorityReduction_ = 0 of the regularized cells (CellProcessor.cpp:399); images_ cleared for removed patches (:411) and for
+    // the old patch of a split leaf (:279-280).  The forest is NOT changed: OctreeIndex::applySweep applies a tree's share.
+    struct ForestProcessResult {
+        std::vector<mo3d::Patch3d> candidates;   // 4 per cell (those of a regularized, removed or exhausted cell are not built)
+        std::vector<int> support;                // per cell
+        std::vector<uint8_t> removed, split;     // per cell
+        std::vector<uint8_t> child;              // 4 per cell
+        std::vector<uint64_t> childKey;          // 4 per cell: the key in the cell's tree of the leaf the child goes into, 0: none
+        std::vector<int> nNeighbours;            // per cell; -2 for settled cells
+    };
+    bool processLevelForest(mo3d::Patch3d* const* cells, const int32_t* cellTree, const uint64_t* cellKey, size_t n, const uint8_t* finalLevel,
+                            const mo3d::OctreeForest& forest, const std::vector<float>& patchCenter, ForestProcessResult& out);
     // Priority L*10 of processCell for cells holding several patches (reference src/hpmvs/CellProcessor.cpp:369-392, filter :43-82), the
     // C++ form of hpmvs_amd.frontier.filter_level / filter_extend_level (same calls, same results).  patches: the cells' patches in data
     // order, the cells in the scheduler's order; cell c holds patches[cellStart[c]] .. patches[cellStart[c + 1] - 1] (cellStart has

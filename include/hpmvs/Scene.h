@@ -12,6 +12,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <unordered_map>
 #include <unordered_set>
 #include <vector>
 #include <hpmvs/Camera.h>
@@ -43,6 +44,68 @@ struct OctreeIndex {
         int d = 0;
         while (w > width && d < 21) { w = (float)((double)w / 2.0); d++; }
         return (w == width && d >= 1) ? d : -1;
+    }
+    // One regularize / settle sweep's removals and splits of THIS tree (PatchOptimizer::processLevelForest, whose arrays these
+    // are, restricted to the cells of this tree and in queue order), with the meaning of DynOctTree::remove / Leaf::split:
+    //   removed[i]   the leaf cellKey[i] is emptied; when its parent Branch is then empty all through, the parent becomes ONE
+    //                empty leaf (remove_internal collapses one level only, doctree.h:422-450; the root stays a Branch)
+    //   split[i]     the leaf becomes a Branch; child k (child[4 i + k]) goes into the leaf childKey[4 i + k], the FIRST child
+    //                of a leaf being its data[0]
+    // The vectors keep the order of what survives; new branches and leaves are appended in the order they were made.
+    // leafFrom (optional): per entry of the new leafKeys its index in the old ones, or -(1 + 4 i + k) for a leaf born from
+    // child k of cell i -- what the caller needs to carry its per-leaf data (data[0]->center_) over.  One pass over the keys
+    // and the cells, whatever the number of removals.  False, and nothing changed, when a removed or split cell's key is no
+    // nonempty leaf of the tree.
+    bool applySweep(const uint64_t* cellKey, const uint8_t* removed, const uint8_t* split, const uint8_t* child, const uint64_t* childKey,
+                    size_t n, std::vector<int32_t>* leafFrom = nullptr) {
+        std::unordered_set<uint64_t> B(branchKeys.begin(), branchKeys.end()), L(leafKeys.begin(), leafKeys.end());
+        for (size_t i = 0; i < n; i++)
+            if ((removed[i] || split[i]) && !L.count(cellKey[i])) return false;
+        std::unordered_map<uint64_t, int32_t> below;   // Branch -> nonempty leaves below it
+        for (uint64_t key : leafKeys)
+            for (uint64_t k = key >> 3; k > 1; k >>= 3) below[k]++;
+        std::vector<uint64_t> newBranches, newLeaves, stack;
+        std::vector<int32_t> newFrom;
+        for (size_t i = 0; i < n; i++) {
+            const uint64_t key = cellKey[i];
+            if (!removed[i] && !split[i]) continue;
+            L.erase(key);
+            for (uint64_t k = key >> 3; k > 1; k >>= 3) below[k]--;
+            if (removed[i]) {
+                const uint64_t par = key >> 3;
+                if (par == 1 || below[par] != 0) continue;
+                stack.assign(1, par);   // the parent and every Branch below it go: one empty leaf is left
+                while (!stack.empty()) {
+                    const uint64_t b = stack.back();
+                    stack.pop_back();
+                    B.erase(b);
+                    below.erase(b);
+                    for (uint64_t c = 0; c < 8; c++)
+                        if (B.count((b << 3) | c)) stack.push_back((b << 3) | c);
+                }
+                continue;
+            }
+            if (B.insert(key).second) newBranches.push_back(key);
+            for (int k = 0; k < 4; k++) {
+                const uint64_t ck = childKey[4 * i + k];
+                if (!child[4 * i + k] || !L.insert(ck).second) continue;
+                for (uint64_t a = ck >> 3; a > 1; a >>= 3) below[a]++;
+                newLeaves.push_back(ck);
+                newFrom.push_back(-(int32_t)(1 + 4 * i + k));
+            }
+        }
+        std::vector<uint64_t> bk, lk;
+        for (uint64_t k : branchKeys) if (B.count(k)) bk.push_back(k);
+        for (uint64_t k : newBranches) if (B.count(k)) bk.push_back(k);
+        if (leafFrom) leafFrom->clear();
+        for (size_t j = 0; j < leafKeys.size(); j++)
+            if (L.count(leafKeys[j])) { lk.push_back(leafKeys[j]); if (leafFrom) leafFrom->push_back((int32_t)j); }
+        lk.insert(lk.end(), newLeaves.begin(), newLeaves.end());
+        if (leafFrom) leafFrom->insert(leafFrom->end(), newFrom.begin(), newFrom.end());
+        branchKeys.swap(bk);
+        leafKeys.swap(lk);
+        branchSet_.swap(B);
+        return true;
     }
     std::unordered_set<uint64_t> branchSet_;   // insertLeaf's view of branchKeys; rebuilt when branchKeys was changed by hand
 };

@@ -42,6 +42,7 @@
  *   hpmvs_octree_locate_batch <- the tree look-ups of CellProcessor::extend, src/hpmvs/CellProcessor.cpp:122-125, 147-154.
  *   hpmvs_extend_tree_batch   <- CellProcessor::extend's candidate loop with both tree look-ups, src/hpmvs/CellProcessor.cpp:84-154.
  *   hpmvs_extend_forest_batch <- the same for all subtrees of getSubTrees' list at once (one processQueue level each, src/main.cpp).
+ *   hpmvs_process_forest_batch <- the regularize / settle sweep (priorities L*10+1 / +2) over all subtrees at once, in queue order.
  *   hpmvs_octree_route_batch, <- CellProcessor::distributeBorderCell and ::processBorderCellQueue,
  *   hpmvs_octree_insert_batch    src/hpmvs/CellProcessor.cpp:487-540 (the root search and the addConditional loop).
  *   hpmvs_octree_partition    <- getSubTrees, src/main.cpp:50-96, and DynOctTree::cellHistogram, doctree.h:493-511.
@@ -522,6 +523,50 @@ typedef struct {
 int hpmvs_extend_forest_batch(const hpmvs_scene *s, const hpmvs_options *o, const hpmvs_octree_forest *f,
                               const hpmvs_patch_batch *parents, const int32_t *parent_tree /*[parents->n], follows on_device*/,
                               float width, hpmvs_patch_batch *out, const hpmvs_extend_tree_keys *keys, int on_device, void *stream);
+
+/* The other two priorities of processCell -- L*10+1 regularize, L*10+2 removal or branch (reference CellProcessor.cpp:309-420) --
+ * as ONE sweep over expanded cells of mixed flatness_, for all subtrees of a forest, in queue order (queue position = row index).
+ * The tree is the key sets of hpmvs_extend_forest_batch: no cell centres travel, every leaf's Cell comes from its key.
+ *   cells[i]             data[0] of cell i; cell_tree[i] its tree, cell_key[i] the key of its (nonempty) leaf in that tree
+ *   leaf_patch_center    [leaf_first[n_trees]][3]: data[0]->center_ of every nonempty leaf, in leaf_key order
+ *   flatness[i] < 0      the cell is REGULARIZED at position i (NaN is not < 0): 24 probes descend from its own tree's root, the
+ *                        distinct nonempty leaves give 2.6 / 2.5 / RMS plane distance over width_, summed in first-probe order.
+ *                        The tree a probe sees is the tree as it stands at position i: a leaf an earlier cell of the same tree
+ *                        removed is empty, a leaf an earlier cell split is a branch -- one more octant step finds the child leaf
+ *                        (data[0]: the first child in k order that went into that octant, at its refined centre) or an empty one
+ *   any other cell       is SETTLED: (double)flatness > 2.4 removes the patch (setDepths(p, true), the leaf emptied), else
+ *                        CellProcessor::branch: getLevelSupport(p, MINLEVEL) < 1 ends it, else the four diagonal children as
+ *                        hpmvs_expand_batch(HPMVS_EXPAND_BRANCH) makes them in Cell(parent, idx) of the key.
+ *                        split = !removed && support >= 1 && !(final_level && no child survived)
+ *   depth maps           ONE ordered setDepths replay for the sweep, in row order across all trees: a removed cell's patch with
+ *                        subtract; a split cell's patch with subtract, then its surviving children in k order
+ * The sweep is the sequential loop over the rows as given, each cell acting in its own tree and all on the shared maps; cells of
+ * different trees may be interleaved.  The tree is NOT modified: the caller applies removals and splits.
+ * Outputs (every pointer of the result nullable, every entry written, all follow on_device): `out` (4 n rows) is what
+ * hpmvs_expand_batch(BRANCH) returns with skip = 1 for the rows of every regularized, removed or support < 1 cell; child_key is
+ * (cell_key << 3) | octant of the leaf child k went into (0: none; two children may share a key, the leaf's data[0] is the lower
+ * k); n_neighbours is -2 for settled cells; neighbour_key holds the neighbours' keys in the cell's tree, first-probe order,
+ * 0-padded.  flatness is in/out: updated for regularized cells only.
+ * HPMVS_ERR_ARG before any output byte or map cell is written, the lowest offender named in hpmvs_last_error: whatever
+ * hpmvs_extend_forest_batch refuses for the forest ("tree K"); a cell_tree[i] outside the forest, a cell_key[i] that is no
+ * nonempty leaf of its tree, the same (tree, key) twice, a cell at depth HPMVS_MAX_TREE_DEPTH that would go to branch, a
+ * regularized cell whose reference image is no view ("cell i"); out->n != 4 n, a max_images mismatch, 5 n * max_images >= 2^28.
+ * A scene without depth maps: HPMVS_ERR_STATE, as hpmvs_depth_ops_batch.  n == 0, trees without cells, all cells regularized (no
+ * refinement launch, no depth ops) and all settled are valid.  Host-synchronous in BOTH pointer forms: the tables, the op rows
+ * and the sort's temporaries are the call's own and are freed when it returns. */
+typedef struct {
+    int32_t  *support;        /* [n] getLevelSupport(p, MINLEVEL) of every row */
+    uint8_t  *removed;        /* [n] */
+    uint8_t  *split;          /* [n] */
+    uint8_t  *children;       /* [n][4] the children that go into the new leaves */
+    uint64_t *child_key;      /* [n][4] */
+    int32_t  *n_neighbours;   /* [n] */
+    uint64_t *neighbour_key;  /* [n][24] */
+} hpmvs_process_forest_result;
+int hpmvs_process_forest_batch(hpmvs_scene *s, const hpmvs_options *o, const hpmvs_octree_forest *f, const float *leaf_patch_center,
+                               const hpmvs_patch_batch *cells, const int32_t *cell_tree, const uint64_t *cell_key, float *flatness,
+                               const uint8_t *final_level, hpmvs_patch_batch *out, const hpmvs_process_forest_result *res,
+                               int on_device, void *stream);
 
 /* A round's border patches (reference src/hpmvs/CellProcessor.cpp:487-540): candidates of CellProcessor::extend that passed every
  * gate but left their subtree's root.  distributeBorderCell hands each to the first processor whose root contains it;
