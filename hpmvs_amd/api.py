@@ -72,6 +72,10 @@ class ProcessForestResultStruct(C.Structure):
                 ("child_key", C.c_void_p), ("n_neighbours", C.c_void_p), ("neighbour_key", C.c_void_p)]
 
 
+class BorderForestResultStruct(C.Structure):
+    _fields_ = [("tree", C.c_void_p), ("accepted", C.c_void_p), ("leaf_key", C.c_void_p), ("blocker", C.c_void_p)]
+
+
 class OctreePartitionInfo(C.Structure):
     _fields_ = [("n_trees", C.c_int32), ("n_orphans", C.c_int32), ("n_splits", C.c_int32), ("stop", C.c_int32),
                 ("histogram", C.c_int32 * 22)]
@@ -96,7 +100,7 @@ EXPORTS = [
     "hpmvs_undistort", "hpmvs_undistort_map", "hpmvs_scene_set_view_distorted",
     "hpmvs_regularize_batch", "hpmvs_filter_batch", "hpmvs_seed_tree_batch", "hpmvs_octree_locate_batch",
     "hpmvs_octree_insert_batch", "hpmvs_octree_route_batch", "hpmvs_octree_partition", "hpmvs_extend_tree_batch",
-    "hpmvs_extend_forest_batch", "hpmvs_process_forest_batch",
+    "hpmvs_extend_forest_batch", "hpmvs_process_forest_batch", "hpmvs_border_forest_batch",
     "hpmvs_scene_center", "hpmvs_init_patches_sphere_batch",
     "hpmvs_jpeg_info", "hpmvs_jpeg_decode", "hpmvs_scene_set_view_jpeg", "hpmvs_jpeg_decode_timed",
 ]
@@ -179,6 +183,8 @@ def lib():
     L.hpmvs_process_forest_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(OctreeForest), C.c_void_p, C.POINTER(PatchBatch),
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PatchBatch),
                                              C.POINTER(ProcessForestResultStruct), C.c_int, C.c_void_p]
+    L.hpmvs_border_forest_batch.argtypes = [C.c_void_p, C.POINTER(OctreeForest), C.POINTER(PatchBatch), C.c_int,
+                                            C.POINTER(BorderForestResultStruct), C.c_int, C.c_void_p]
     L.hpmvs_octree_route_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.hpmvs_octree_partition.argtypes = [C.c_void_p, C.POINTER(OctreeIndex), C.c_int, C.c_int, C.POINTER(OctreePartitionInfo)] + \
         [C.c_void_p] * 9 + [C.c_int, C.c_void_p]
@@ -866,6 +872,35 @@ def octree_route_batch(scene: Scene, roots, points) -> np.ndarray:
     tree = np.zeros(len(pts), np.int32)
     _chk(lib().hpmvs_octree_route_batch(scene.h, len(rt), rt.ctypes.data, len(pts), pts.ctypes.data, tree.ctypes.data, 0, None))
     return tree
+
+
+@dataclass
+class BorderForestInsertion:
+    tree: np.ndarray               # [n] int32 the first tree in list order whose root contains the patch, -1: none (dropped)
+    accepted: np.ndarray           # [n] uint8 addConditional's return in that tree, in queue order
+    leaf_key: np.ndarray           # [n] uint64 the key in that tree of the leaf the patch went into, or that refused it; 0: dropped
+    blocker: np.ndarray            # [n] int32 queue index of the earlier patch behind a refusal, -1: accepted, refused by the tree, dropped
+
+    def c_struct(self) -> BorderForestResultStruct:
+        r = BorderForestResultStruct()
+        r.tree, r.accepted, r.leaf_key, r.blocker = _ptr(self.tree), _ptr(self.accepted), _ptr(self.leaf_key), _ptr(self.blocker)
+        return r
+
+
+def border_forest_batch(scene: Scene, border: Batch, roots, branch_first, leaf_first, branch_key, leaf_key,
+                        set_depths: bool = True) -> BorderForestInsertion:
+    """A round's border queue delivered to ALL trees of a forest as ONE hpmvs_border_forest_batch (include/hpmvs_amd.h):
+    octree_route_batch over `roots`, then for every tree octree_insert_batch of its rows in queue order with add_width =
+    scale * 2.0, then set_depths_batch over the accepted rows (set_depths).  The forest is given as extend_forest_batch takes
+    it; the keys are not changed: the caller enters the accepted ones.  HpmvsError names the offending tree; nothing is
+    written then."""
+    f, hold = octree_forest(roots, branch_first, leaf_first, branch_key, leaf_key)
+    n = border.n
+    r = BorderForestInsertion(np.zeros(n, np.int32), np.zeros(n, np.uint8), np.zeros(n, np.uint64), np.zeros(n, np.int32))
+    bb, rb = border.c_struct(), r.c_struct()
+    _chk(lib().hpmvs_border_forest_batch(scene.h, C.byref(f), C.byref(bb), 1 if set_depths else 0, C.byref(rb), 0, None))
+    del hold
+    return r
 
 
 MAX_SUBTREES = 4096   # HPMVS_MAX_SUBTREES: the largest min_trees

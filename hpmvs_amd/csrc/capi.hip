@@ -2519,6 +2519,115 @@ int hpmvs_process_forest_batch(hpmvs_scene* s, const hpmvs_options* o, const hpm
     if ((rc = c.finish())) return rc;
     return ck.finish();   // (waits in both forms: the tables are freed when this call returns; flatness travels back here)
 }
+// A round's border queue over ALL subtrees (kernel_border_forest.hip): distributeBorderCell, every tree's
+// processBorderCellQueue and the accepted patches' setDepths(p, false) as ONE call.  One Call: no array is filled by begin() (the
+// kernels write every entry of every output), so declaring the outputs ahead of the verdict writes nothing; the forest's verdict
+// comes back in ONE read-back before the first kernel that touches an output or a map is enqueued.  The block is the call's own:
+// [verdict] [Tree x T] [branch_first] [leaf_first], the tables, then 56 bytes per patch and rocPRIM's temporary storage.
+int hpmvs_border_forest_batch(hpmvs_scene* s, const hpmvs_octree_forest* f, const hpmvs_patch_batch* border, int set_depths,
+                              const hpmvs_border_forest_result* res, int on_device, void* stream) {
+    const std::string who = "border_forest_batch";
+    if (hpmvs_device_count() <= 0) return fail(HPMVS_ERR_NODEVICE, who + ": no HIP device visible");
+    if (!s || !f || !border) return fail(HPMVS_ERR_ARG, who + ": null scene / forest / batch");
+    if (!s->committed) return fail(HPMVS_ERR_STATE, who + ": scene not committed");
+    if (border->n < 0 || border->max_images < 1 || border->max_images > HPMVS_MAX_IMAGES) return fail(HPMVS_ERR_ARG, who + ": bad n/max_images");
+    if (border->n > 0 && (!border->center || !border->scale)) return fail(HPMVS_ERR_ARG, who + ": batch input arrays missing (center / scale)");
+    if (border->n > 0 && set_depths && (!border->normal || !border->n_images || !border->images))
+        return fail(HPMVS_ERR_ARG, who + ": batch input arrays missing (set_depths reads normal / n_images / images)");
+    const int T = f->n_trees;
+    if (T < 0) return fail(HPMVS_ERR_ARG, who + ": negative count");
+    if (T > 0 && (!f->root || !f->branch_first || !f->leaf_first)) return fail(HPMVS_ERR_ARG, who + ": root / branch_first / leaf_first missing");
+    int rc;
+    if (T > 0 && (rc = forest_host_check(who, f))) return rc;
+    if (set_depths && (!s->depth_pool || !s->ddepth)) return fail(HPMVS_ERR_STATE, who + ": call hpmvs_scene_depth_reset first");
+    const size_t n = (size_t)border->n, M = (size_t)border->max_images;
+    if (T == 0 && n == 0) return HPMVS_OK;
+    const size_t nb = T ? (size_t)f->branch_first[T] : 0, nl = T ? (size_t)f->leaf_first[T] : 0;
+    std::vector<uint64_t> slot_first((size_t)T + 1, 0);
+    if (T) octree::forest_slots(T, f->branch_first, f->leaf_first, slot_first.data());
+    const size_t slots = (size_t)slot_first[T];
+    const size_t o_trees = reg_align(sizeof(uint32_t) * kForestWords), o_bf = reg_align(o_trees + sizeof(octree::Tree) * T),
+                 o_lf = reg_align(o_bf + 4 * ((size_t)T + 1)), o_keys = reg_align(o_lf + 4 * ((size_t)T + 1)),
+                 o_vals = reg_align(o_keys + 8 * slots), bytes = reg_align(o_vals + 4 * slots);
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    Call c(s, on_device, st);
+    const unsigned long long* dbk = (const unsigned long long*)c.in(f->branch_key, nb);
+    const unsigned long long* dlk = (const unsigned long long*)c.in(f->leaf_key, nl);
+    DevBatch D;
+    memset(&D, 0, sizeof(D));
+    D.n = border->n; D.max_images = border->max_images;
+    D.center = c.in(border->center, 4 * n);
+    D.scale = c.in(border->scale, n);
+    if (set_depths) {
+        D.n_images = c.in(border->n_images, n);
+        D.images = c.in(border->images, n * M);
+    }
+    static const hpmvs_border_forest_result none = {nullptr, nullptr, nullptr, nullptr};
+    const hpmvs_border_forest_result& R = res ? *res : none;
+    BorderForestOut out;   // (the static and the replay kernel between them write every entry: no zero fill)
+    out.tree = c.arr(R.tree, n, Call::kCopyBack);
+    out.accepted = c.arr(R.accepted, n, Call::kCopyBack);
+    out.leaf_key = (unsigned long long*)c.arr(R.leaf_key, n, Call::kCopyBack);
+    out.blocker = c.arr(R.blocker, n, Call::kCopyBack);
+    if (c.error()) return c.error();
+    if (set_depths && n > 0 && !out.accepted) {   // the mask of set_depths_kernel, in scratch where the caller does not ask for it
+        out.accepted = (uint8_t*)c.scratch(n);
+        if (!out.accepted) return c.error();
+    }
+    char* w = (char*)c.scratch(bytes);
+    if (!w) return c.error();
+    BorderForestScratch S;
+    memset(&S, 0, sizeof(S));
+    if (n > 0) {
+        S.temp_bytes = border_forest_temp_bytes((int)n, T);
+        if (S.temp_bytes == (size_t)-1) return fail(HPMVS_ERR_HIP, who + ": rocPRIM size query failed");
+        // one block: four 8-byte arrays, six 4-byte ones, then rocPRIM's temporary storage
+        const size_t o_temp = reg_align(56 * n);
+        char* blk = (char*)c.scratch(o_temp + S.temp_bytes);
+        if (!blk) return c.error();
+        S.path = (unsigned long long*)blk; S.key_a = S.path + n; S.key_b = S.key_a + n; S.acc_key = S.key_b + n;
+        S.val_a = (uint32_t*)(S.acc_key + n); S.val_b = S.val_a + n; S.tree_a = S.val_b + n; S.tree_b = S.tree_a + n; S.tree_c = S.tree_b + n;
+        S.acc_owner = (int32_t*)(S.tree_c + n);
+        S.temp = blk + o_temp;
+    }
+    std::vector<char> hdr(o_keys, 0);
+    for (int v = 0; v < kForestWords; v++) ((uint32_t*)hdr.data())[v] = octree::kForestGood;
+    octree::Tree* ht = (octree::Tree*)(hdr.data() + o_trees);
+    for (int k = 0; k < T; k++) {
+        const float* r = f->root + 4 * (size_t)k;
+        ht[k].root = octree::Cell{{r[0], r[1], r[2]}, r[3]};
+        ht[k].t = octree::Table{(const uint64_t*)(w + o_keys) + slot_first[k], (const int32_t*)(w + o_vals) + slot_first[k],
+                                (uint32_t)(slot_first[k + 1] - slot_first[k])};
+    }
+    if (T) {
+        memcpy(hdr.data() + o_bf, f->branch_first, 4 * ((size_t)T + 1));
+        memcpy(hdr.data() + o_lf, f->leaf_first, 4 * ((size_t)T + 1));
+    }
+    uint32_t* verdict = (uint32_t*)w;
+    const octree::Tree* dtrees = (const octree::Tree*)(w + o_trees);
+    if ((rc = c.begin(st))) return rc;
+    if (T) {
+        HIPCHK(hipMemcpyAsync(w, hdr.data(), o_keys, hipMemcpyHostToDevice, st));   // (pageable: consumed before it returns)
+        HIPCHK(hipMemsetAsync(w + o_keys, 0, 8 * slots, st));
+        launch_forest_build(T, (const int32_t*)(w + o_bf), (const int32_t*)(w + o_lf), dbk, dlk, (int)(nb + nl), dtrees, verdict, st);
+        HIPCHK(hipGetLastError());
+        uint32_t h[kForestWords];
+        HIPCHK(hipMemcpyAsync(h, verdict, sizeof(h), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (h[kForestTable] != octree::kForestGood) return forest_table_fail(who, h[kForestTable]);
+    }
+    if (n > 0) {
+        if (launch_border_forest(T, dtrees, (int)n, D.center, D.scale, S, out, st)) return fail(HPMVS_ERR_HIP, who + ": rocPRIM sort failed");
+        HIPCHK(hipGetLastError());
+        if (set_depths) {
+            D.ok = out.accepted;
+            launch_set_depths(dev_scene(s), s->ddepth, D, st);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    return c.finish();   // (waits in both forms: the tables and the scratch are freed when this call returns)
+}
 // CellProcessor::processBorderCellQueue's insertion loop (CellProcessor.cpp:500-531): addConditional(points[i], add_width[i]) for
 // i = 0 .. n - 1 IN THAT ORDER against the tree t, which stays the caller's (kernel_octree_insert.hip: static kernel, stable sort by
 // static leaf, one wavefront per leaf's run).  The scratch is the call's own, sized by n alone.

@@ -216,6 +216,24 @@ int launch_octree_insert(const float* root, const unsigned long long* keys, cons
                          hipStream_t st);
 void launch_octree_route(int n_trees, const float* roots, int n, const float* points, int32_t* tree, hipStream_t st);
 
+// a round's border queue over a forest (kernel_border_forest.hip, include/hpmvs_amd.h: hpmvs_border_forest_batch), against the
+// tables launch_forest_build made: static kernel (route, locate, refusal, path), two stable sorts (leaf key, then tree id), replay
+// with one wavefront per (tree, leaf key) run, all enqueued on st; != 0: a rocPRIM call failed.  center: [n][4], scale: [n] of the
+// patch batch.  Every output is nullable; what is given is written in every entry.  n_trees == 0: trees may be null.
+struct BorderForestOut {
+    int32_t* tree; uint8_t* accepted; unsigned long long* leaf_key; int32_t* blocker;
+};
+struct BorderForestScratch {
+    unsigned long long *path, *key_a, *key_b, *acc_key;   // [n] each
+    uint32_t *val_a, *val_b, *tree_a, *tree_b, *tree_c;   // [n] each
+    int32_t* acc_owner;                                   // [n]
+    void* temp;                                           // border_forest_temp_bytes(n, n_trees)
+    size_t temp_bytes;
+};
+size_t border_forest_temp_bytes(int n, int n_trees);   // (size_t)-1: a size query failed
+int launch_border_forest(int n_trees, const octree::Tree* trees, int n, const float* center, const float* scale,
+                         const BorderForestScratch& s, const BorderForestOut& out, hipStream_t st);
+
 // the split into subtrees (kernel_octree_partition.hip, include/hpmvs_amd.h: hpmvs_octree_partition).  launch_octree_partition
 // reads the table launch_octree_build made and enqueues the leaf kernel, the sort, the one-wavefront loop and the assignment on
 // st; != 0: the rocPRIM call failed.  info: the call's device record, zeroed by the caller -- the hpmvs_octree_partition_info the

@@ -3,7 +3,8 @@
 // once for the device kernels (kernel_octree.hip, kernel_octree_insert.hip) and for the host restatements the tests compile with
 // g++ (tests/octree_host.cpp, tests/octree_insert_host.cpp).  DESIGN.md §3.11 has the argument; §3.12 the one for inserting a
 // round's border patches in queue order (the second part of this file), §3.14 the one for the split into subtrees, §3.15 the one
-// for a forest of subtrees behind one table buffer, §3.16 the one for the regularize / settle sweep over a forest (the last).
+// for a forest of subtrees behind one table buffer, §3.16 the one for the regularize / settle sweep over a forest, §3.17 the one
+// for a round's border queue delivered to a forest (the last).
 //
 //   path key                 a sentinel bit, then 3 bits per level (z y x, Branch::at's child test x > c_): the root is 1, a cell
 //                            at depth d has 3 d bits below the sentinel; at most kMaxDepth = 21 levels (kernel_regularize.hip's form)
@@ -647,6 +648,52 @@ inline uint32_t process_sequential(int32_t n_trees, const Tree* trees, const int
                 if (children[4 * (size_t)i + k]) { ops->push_back(n + 4 * i + k); op_subtract->push_back(0); }
     }
     return kForestGood;
+}
+
+// ---- a round's border queue delivered to a forest (hpmvs_border_forest_batch, reference CellProcessor.cpp:487-540, DESIGN.md
+// §3.17): distributeBorderCell hands patch i to the first tree in list order whose root contains center_, and every tree's
+// processBorderCellQueue inserts what it was handed in queue order with addConditional(center_, scale_3dx_ * 2.0).  Trees never
+// meet, so a run of the replay is a (tree, static leaf key) PAIR: two trees often hold the same sub-key.
+// scale_3dx_ * 2.0: a double product, narrowed by addConditional's float parameter
+HPMVS_OT_FN float border_add_width(float scale) { return (float)((double)scale * 2.0); }
+// distributeBorderCell's search over the trees of a forest
+HPMVS_OT_FN int32_t route(int32_t n_trees, const Tree* trees, const float* p) {
+    for (int32_t k = 0; k < n_trees; k++)
+        if (contains(trees[k].root, p)) return k;
+    return -1;
+}
+// The queue on one thread: the route loop, then insert_sequential per tree over that tree's rows in their given order, the
+// blocker mapped back through the row selection.  center: [n][4] as a patch batch holds it.  The host restatement the tests
+// load, and the loop the one call's cost is set against.  tree / accepted / leaf_key: [n]; blocker: [n], nullable.
+inline void border_forest_sequential(int32_t n_trees, const Tree* trees, int n, const float* center, const float* scale, int32_t* tree,
+                                     uint8_t* accepted, uint64_t* leaf_key, int32_t* blocker) {
+    std::vector<std::vector<int32_t>> rows(n_trees > 0 ? (size_t)n_trees : 0);
+    for (int i = 0; i < n; i++) {
+        tree[i] = route(n_trees, trees, center + 4 * (size_t)i);
+        accepted[i] = 0;
+        leaf_key[i] = 0;
+        if (blocker) blocker[i] = -1;
+        if (tree[i] >= 0) rows[(size_t)tree[i]].push_back(i);
+    }
+    for (int32_t k = 0; k < n_trees; k++) {
+        const std::vector<int32_t>& sel = rows[(size_t)k];
+        const int m = (int)sel.size();
+        if (m == 0) continue;
+        std::vector<float> pts(3 * (size_t)m), aw((size_t)m);
+        std::vector<uint8_t> acc((size_t)m);
+        std::vector<uint64_t> key((size_t)m);
+        std::vector<int32_t> blk((size_t)m);
+        for (int j = 0; j < m; j++) {
+            for (int c = 0; c < 3; c++) pts[3 * (size_t)j + c] = center[4 * (size_t)sel[j] + c];
+            aw[j] = border_add_width(scale[sel[j]]);
+        }
+        insert_sequential(trees[k].root, trees[k].t, m, pts.data(), aw.data(), acc.data(), key.data(), blk.data());
+        for (int j = 0; j < m; j++) {
+            accepted[sel[j]] = acc[j];
+            leaf_key[sel[j]] = key[j];
+            if (blocker) blocker[sel[j]] = blk[j] < 0 ? -1 : sel[blk[j]];
+        }
+    }
 }
 
 }  // namespace octree

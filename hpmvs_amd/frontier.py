@@ -1110,6 +1110,36 @@ def insert_border(scene: api.Scene, tree: Octree, border: api.Batch, priority, r
                         priority[acc].copy(), r)
 
 
+@dataclass
+class BorderForestResult:
+    tree: np.ndarray               # [border.n] int32 the tree every row was handed to, -1: no root contains it (dropped)
+    accepted: np.ndarray           # rows of `border` that went into their tree, in queue order
+    leaf_key: np.ndarray           # [len(accepted)] uint64 path key, in the row's own tree, of the leaf each went into
+    node_level: np.ndarray         # [len(accepted)] int32 DynOctTree::nodeLevel of that leaf
+    flatness: np.ndarray           # [len(accepted)] float32 0: no regularization on border cells (CellProcessor.cpp:514)
+    priority: np.ndarray           # [len(accepted)] float32 handed through for the scheduler's processing_queue
+    insertion: api.BorderForestInsertion  # every row's tree, decision, leaf and blocker
+
+
+def deliver_border_forest(scene: api.Scene, trees, border: api.Batch, priority, rows=None) -> BorderForestResult:
+    """route_border and the loop of insert_border over the destination trees as ONE hpmvs_border_forest_batch (DESIGN.md
+    section 3.17): every row of the round's border queue `border` (push order) is handed to the first tree of `trees` (a list
+    of Octree such as Partition.trees) whose root contains it, goes in with addConditional(center, scale_3dx_ * 2.0) in queue
+    order among the rows of its tree, and the accepted ones write their depths.  The accepted keys are entered into their Octree
+    objects in queue order under rows[i] (default ("border", i)).  The result covers the whole queue: its fields are
+    BorderResult's, with `tree` beside them."""
+    trees = list(trees)
+    n = border.n
+    priority = np.broadcast_to(np.asarray(priority, np.float32), (n,))
+    r = api.border_forest_batch(scene, border, *_flatten_forest(trees), set_depths=True)
+    acc = np.nonzero(r.accepted)[0]
+    for i in acc:
+        trees[int(r.tree[i])].insert(int(r.leaf_key[i]), rows[i] if rows is not None else ("border", int(i)))
+    keys = r.leaf_key[acc]
+    level = np.array([trees[int(r.tree[i])].node_level(int(r.leaf_key[i])) for i in acc], np.int32)
+    return BorderForestResult(r.tree, acc, keys, level, np.zeros(len(acc), np.float32), priority[acc].copy(), r)
+
+
 # ---- the split into subtrees (DESIGN.md section 3.14; reference src/main.cpp:50-96, CellProcessor.cpp:422-455) --------------
 
 @dataclass

@@ -756,6 +756,25 @@ bool Scene::octreeRoute(const std::vector<float>& roots, const std::vector<float
     }
     return true;
 }
+bool Scene::octreeBorderForest(const OctreeForest& forest, const Patch3d* const* patches, size_t n, bool setDepths,
+                               BorderForestInsertion& out) const {
+    hpmvs_scene* dev = deviceScene();
+    if (!dev) return false;
+    OctreeForest::Flat flat;
+    forest.flatten(flat);
+    hpmvs_octree_forest f;
+    f.n_trees = (int32_t)forest.trees.size();
+    f.root = flat.root.data(); f.branch_first = flat.branchFirst.data(); f.leaf_first = flat.leafFirst.data();
+    f.branch_key = flat.branchKey.data(); f.leaf_key = flat.leafKey.data();
+    HostBatch hb(patches, n);
+    out.tree.assign(n, 0); out.accepted.assign(n, 0); out.leafKey.assign(n, 0); out.blocker.assign(n, 0);
+    const hpmvs_border_forest_result res = {out.tree.data(), out.accepted.data(), out.leafKey.data(), out.blocker.data()};
+    if (hpmvs_border_forest_batch(dev, &f, &hb.b, setDepths ? 1 : 0, &res, 0, nullptr) != HPMVS_OK) {
+        std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl;
+        return false;
+    }
+    return true;
+}
 bool Scene::octreePartition(const OctreeIndex& tree, int minTrees, OctreePartition& out, int minSplitLeaves) const {
     hpmvs_scene* dev = deviceScene();
     if (!dev) return false;
@@ -1710,6 +1729,17 @@ bool PatchOptimizer::processLevel(mo3d::Patch3d* const* cells, const int32_t* ce
     std::vector<int> nn;
     if (!regularizeLevel(rp.data(), rp.size(), rw.data(), rq.data(), T, &nn)) return false;
     for (size_t j = 0; j < reg.size(); j++) R.nNeighbours[reg[j]] = nn[j];
+    return true;
+}
+
+bool PatchOptimizer::deliverBorderForest(mo3d::Patch3d* const* border, size_t n, mo3d::OctreeForest& forest,
+                                         mo3d::BorderForestInsertion& out) {
+    if (!scene_p->octreeBorderForest(forest, border, n, true, out)) return false;
+    for (size_t i = 0; i < n; i++) {
+        if (!out.accepted[i]) continue;
+        border[i]->flatness_ = 0;   // no regularization on border cells (CellProcessor.cpp:514)
+        forest.trees[(size_t)out.tree[i]].insertLeaf(out.leafKey[i]);
+    }
     return true;
 }
 

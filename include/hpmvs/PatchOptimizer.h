@@ -16,6 +16,7 @@ class HpmvsOptions;
 class Scene;
 struct OctreeIndex;
 struct OctreeForest;
+struct BorderForestInsertion;
 class PatchOptimizer {
 public:
     PatchOptimizer(const mo3d::HpmvsOptions& options, const mo3d::Scene* scene);
@@ -151,6 +152,11 @@ public:
     };
     bool processLevelForest(mo3d::Patch3d* const* cells, const int32_t* cellTree, const uint64_t* cellKey, size_t n, const uint8_t* finalLevel,
                             const mo3d::OctreeForest& forest, const std::vector<float>& patchCenter, ForestProcessResult& out);
+    // A round's border queue delivered to ALL subtrees as ONE hpmvs_border_forest_batch (hpmvs_amd.frontier.deliver_border_forest:
+    // same call, same results; reference CellProcessor.cpp:487-540): Scene::octreeBorderForest with setDepths, then
+    // for the accepted patches, in queue order, flatness_ = 0 (:514: no regularization on border cells) and
+    // OctreeIndex::insertLeaf of their key into their own tree.  The scheduler's queue and its priorities stay the caller's.
+    bool deliverBorderForest(mo3d::Patch3d* const* border, size_t n, mo3d::OctreeForest& forest, mo3d::BorderForestInsertion& out);
     // Priority L*10 of processCell for cells holding several patches (reference src/hpmvs/CellProcessor.cpp:369-392, filter :43-82), the
     // C++ form of hpmvs_amd.frontier.filter_level / filter_extend_level (same calls, same results).  patches: the cells' patches in data
     // order, the cells in the scheduler's order; cell c holds patches[cellStart[c]] .. patches[cellStart[c + 1] - 1] (cellStart has

@@ -133,6 +133,13 @@ struct OctreeForest {
         }
     }
 };
+// What hpmvs_border_forest_batch returns for a round's border queue (Scene::octreeBorderForest, PatchOptimizer::deliverBorderForest).
+struct BorderForestInsertion {
+    std::vector<int32_t> tree;         // [n] -1: no root contains the patch (it is dropped)
+    std::vector<uint8_t> accepted;     // [n]
+    std::vector<uint64_t> leafKey;     // [n] in the row's own tree
+    std::vector<int32_t> blocker;      // [n] an index into the queue
+};
 // The split of a DynOctTree into subtrees (include/hpmvs_amd.h: hpmvs_octree_partition); the roots' vectors hold nTrees entries.
 struct OctreePartition {
     int nTrees, nOrphans, nSplits, stop;   // stop 0: the root alone; 1: the list reached minTrees; 2: the largest subtree is too small
@@ -238,6 +245,13 @@ public:
     bool octreeInsert(const OctreeIndex& tree, const std::vector<float>& points /*[n][3]*/, const std::vector<float>& addWidth /*[n]*/,
                       OctreeInsertion& out) const;
     bool octreeRoute(const std::vector<float>& roots /*[t][4]*/, const std::vector<float>& points /*[n][3]*/, std::vector<int32_t>& out) const;
+    // Both of them for a whole round's border queue and ALL subtrees as ONE batched GPU call (hpmvs_border_forest_batch):
+    // patches[i] is handed to the first tree of the forest whose root contains center_, inserted in queue order among the rows of
+    // its tree with addConditional(center_, scale_3dx_ * 2.0), and with setDepths the accepted ones write their depths.  Thin
+    // marshalling through OctreeForest::flatten; the forest and the patches are not changed.  Results as the call's
+    // (include/hpmvs_amd.h): leafKey is relative to the row's own tree, blocker an index into this queue.
+    bool octreeBorderForest(const OctreeForest& forest, const Patch3d* const* patches, size_t n, bool setDepths,
+                            BorderForestInsertion& out) const;
     // getSubTrees(scene.patchTree_, subTrees, FLAGS_subtrees) of the reference's main (src/main.cpp:50-96) and
     // DynOctTree::cellHistogram as ONE batched GPU call (hpmvs_octree_partition): the subtree roots in the reference's list order
     // (the order octreeRoute takes), every key's subtree and its key re-based on that root, and the Leaf_iterator order that

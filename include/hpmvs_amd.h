@@ -45,6 +45,8 @@
  *   hpmvs_process_forest_batch <- the regularize / settle sweep (priorities L*10+1 / +2) over all subtrees at once, in queue order.
  *   hpmvs_octree_route_batch, <- CellProcessor::distributeBorderCell and ::processBorderCellQueue,
  *   hpmvs_octree_insert_batch    src/hpmvs/CellProcessor.cpp:487-540 (the root search and the addConditional loop).
+ *   hpmvs_border_forest_batch <- both of them for a whole round's border queue over all subtrees at once, with the accepted
+ *                                patches' setDepths (CellProcessor.cpp:487-540): the third forest call of a tree level.
  *   hpmvs_octree_partition    <- getSubTrees, src/main.cpp:50-96, and DynOctTree::cellHistogram, doctree.h:493-511.
  *   hpmvs_camera_from_nvm    <- Camera::init, src/hpmvs/Camera.cpp:34-81.
  */
@@ -595,6 +597,32 @@ int hpmvs_octree_insert_batch(const hpmvs_scene *s, const hpmvs_octree_index *t,
                               int32_t *blocker /*[n], nullable*/, int on_device, void *stream);
 int hpmvs_octree_route_batch(const hpmvs_scene *s, int n_trees, const float *roots /*[n_trees][4]: c_, width_*/, int n,
                              const float *points /*[n][3]*/, int32_t *tree /*[n]*/, int on_device, void *stream);
+
+/* The same delivery for a whole round's border queue and ALL subtrees in ONE call: distributeBorderCell, every subtree's
+ * processBorderCellQueue and the accepted patches' setDepths(p, false).  `border` is the queue in push order; the call reads
+ * center and scale, with set_depths != 0 also normal, n_images and images; ok is neither read nor written and the batch is not
+ * modified.  add_width[i] = (float)((double)scale[i] * 2.0) is formed on the device.
+ *   CONTRACT     tree[] equals hpmvs_octree_route_batch over f->root.  For every tree k, take the rows with tree[i] == k in their
+ *                given order: accepted and leaf_key of those rows are byte-identical to hpmvs_octree_insert_batch on tree k alone
+ *                with those rows, and blocker is that call's blocker mapped back through the row selection (an index into THIS
+ *                queue).  A row no root contains is dropped: tree -1, accepted 0, leaf_key 0, blocker -1.  With set_depths != 0
+ *                the maps end as after hpmvs_set_depths_batch over the accepted rows (a float minimum: order plays no part).
+ * The forest is NOT modified: the caller enters the accepted keys.  The rows of different trees may be interleaved in any order,
+ * and two trees may hold the same sub-key: a run of the replay is a (tree, leaf key) pair.  root / branch_first / leaf_first are
+ * HOST arrays in both forms; the key arrays, the batch and the result follow on_device.  Every pointer of the result is nullable,
+ * and so is the result; what is given is written in every entry.  n == 0, n_trees == 0 (every tree is -1), trees without keys and
+ * trees no patch reaches are valid.  HPMVS_ERR_ARG before any output byte or map cell is written, the lowest offender named, for
+ * whatever hpmvs_extend_forest_batch refuses for the forest ("tree K") and for a bad batch; HPMVS_ERR_STATE, likewise before any
+ * write, for set_depths on a scene without depth maps.  The tables and 56 bytes per patch plus the sorts' temporary storage are the
+ * call's own; no allocation and no launch size depends on data read back.  Host-synchronous in both pointer forms. */
+typedef struct {             /* every pointer nullable; [border->n] each; follow on_device */
+    int32_t  *tree;          /* first tree in list order whose root contains center_, -1: none (the patch is dropped) */
+    uint8_t  *accepted;      /* 1: inserted */
+    uint64_t *leaf_key;      /* key IN THAT TREE of the leaf it went into / that refused it; 0 where tree == -1 */
+    int32_t  *blocker;       /* as hpmvs_octree_insert_batch, as an index into THIS queue; -1 where tree == -1 */
+} hpmvs_border_forest_result;
+int hpmvs_border_forest_batch(hpmvs_scene *s, const hpmvs_octree_forest *f, const hpmvs_patch_batch *border,
+                              int set_depths, const hpmvs_border_forest_result *res, int on_device, void *stream);
 
 /* The split of the octree into subtrees that main() makes between initPatches and the first level (reference src/main.cpp:50-96,
  * getSubTrees(scene.patchTree_, subTrees, FLAGS_subtrees); DynOctTree::getSubTrees, doctree.h:513-523; Branch::nrLeafs,
