@@ -101,6 +101,7 @@ EXPORTS = [
     "hpmvs_regularize_batch", "hpmvs_filter_batch", "hpmvs_seed_tree_batch", "hpmvs_octree_locate_batch",
     "hpmvs_octree_insert_batch", "hpmvs_octree_route_batch", "hpmvs_octree_partition", "hpmvs_extend_tree_batch",
     "hpmvs_extend_forest_batch", "hpmvs_process_forest_batch", "hpmvs_border_forest_batch",
+    "hpmvs_level_conflicts_batch", "hpmvs_conflicts_from_footprints",
     "hpmvs_scene_center", "hpmvs_init_patches_sphere_batch",
     "hpmvs_jpeg_info", "hpmvs_jpeg_decode", "hpmvs_scene_set_view_jpeg", "hpmvs_jpeg_decode_timed",
 ]
@@ -165,6 +166,12 @@ def lib():
     L.hpmvs_set_depths_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_int, C.c_void_p]
     L.hpmvs_depth_footprints_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_int, C.c_void_p]
+    L.hpmvs_level_conflicts_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                              C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                              C.c_int, C.c_void_p]
+    L.hpmvs_conflicts_from_footprints.argtypes = [C.c_int] * 5 + [C.c_void_p] * 6 + [C.c_void_p, C.c_void_p, C.c_size_t,
+                                                  C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                  C.c_int, C.c_void_p]
     L.hpmvs_depth_gates_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_float, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int, C.c_void_p]
     L.hpmvs_depth_ops_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_void_p, C.c_int, C.c_void_p]
@@ -582,6 +589,50 @@ def depth_footprints_batch(scene: Scene, batch: Batch):
     at = np.zeros((n, M, 3), np.int32); vb = np.zeros((n, V, 3), np.int32)
     _chk(lib().hpmvs_depth_footprints_batch(scene.h, C.byref(b), wr.ctypes.data, fr.ctypes.data, at.ctypes.data, vb.ctypes.data, 0, None))
     return wr, fr, at, vb
+
+
+def _conflicts(call, n):
+    """The capacity contract of the two conflict-graph calls (include/hpmvs_amd.h): a call with room for 32 edges per node in
+    each list; when that does not hold them the totals are valid all the same, and a second call gets arrays of that size.
+    call(flow_off, flow_adj, cap_flow, anti_off, anti_adj, cap_anti, n_flow, n_anti) -> status."""
+    fo = np.zeros(n + 1, np.uint32); ao = np.zeros(n + 1, np.uint32)
+    nf, na = C.c_uint32(0), C.c_uint32(0)
+    fa = np.zeros(32 * n + 64, np.uint32); aa = np.zeros(32 * n + 64, np.uint32)
+    rc = call(fo.ctypes.data, fa.ctypes.data, fa.size, ao.ctypes.data, aa.ctypes.data, aa.size, C.byref(nf), C.byref(na))
+    if rc != 0:
+        if "capacity" not in lib().hpmvs_last_error().decode():
+            _chk(rc)
+        fa = np.zeros(nf.value, np.uint32); aa = np.zeros(na.value, np.uint32)
+        _chk(call(fo.ctypes.data, fa.ctypes.data, fa.size, ao.ctypes.data, aa.ctypes.data, aa.size, C.byref(nf), C.byref(na)))
+    return fo, fa[:nf.value].copy(), ao, aa[:na.value].copy()
+
+
+def level_conflicts(scene: Scene, batch: Batch, is_event=None):
+    """The conflict graph of one extend level as ONE hpmvs_level_conflicts_batch (include/hpmvs_amd.h): the
+    batch's patches are the level's nodes in queue order, is_event marks the subtraction events (None: none).  No footprint
+    leaves the device.  Returns (flow_off [n + 1], flow_adj, anti_off [n + 1], anti_adj), uint32, every list ascending."""
+    b = batch.c_struct()
+    ev = None if is_event is None else np.ascontiguousarray(is_event, dtype=np.uint8).reshape(batch.n)
+    evp = None if ev is None else ev.ctypes.data
+    return _conflicts(lambda fo, fa, cf, ao, aa, ca, nf, na: lib().hpmvs_level_conflicts_batch(
+        scene.h, C.byref(b), evp, fo, fa, cf, ao, aa, ca, nf, na, 0, None), batch.n)
+
+
+def conflicts_from_footprints(n_images, writes, frees, attached, view_block, n_levels, is_event=None, device: int = 0):
+    """The graph step alone, on footprint arrays in the layouts of depth_footprints_batch (writes / frees [n, M, 4], attached
+    [n, M, 3], view_block [n, V, 3]; n_images [n]: the entries of a row that count): hpmvs_conflicts_from_footprints.  Needs
+    no scene.  Returns what level_conflicts returns."""
+    wr = np.ascontiguousarray(writes, dtype=np.int32); fr = np.ascontiguousarray(frees, dtype=np.int32)
+    at = np.ascontiguousarray(attached, dtype=np.int32); vb = np.ascontiguousarray(view_block, dtype=np.int32)
+    n, M, V = wr.shape[0], wr.shape[1], vb.shape[1]
+    if wr.shape != (n, M, 4) or fr.shape != (n, M, 4) or at.shape != (n, M, 3) or vb.shape != (n, V, 3):
+        raise ValueError("conflicts_from_footprints: the footprint arrays do not have the layouts of depth_footprints_batch")
+    ni = np.ascontiguousarray(n_images, dtype=np.int32).reshape(n)
+    ev = None if is_event is None else np.ascontiguousarray(is_event, dtype=np.uint8).reshape(n)
+    evp = None if ev is None else ev.ctypes.data
+    return _conflicts(lambda fo, fa, cf, ao, aa, ca, nf, na: lib().hpmvs_conflicts_from_footprints(
+        int(device), n, M, V, int(n_levels), ni.ctypes.data, wr.ctypes.data, fr.ctypes.data, at.ctypes.data, vb.ctypes.data, evp,
+        fo, fa, cf, ao, aa, ca, nf, na, 0, None), n)
 
 
 def build_pyramid(img: np.ndarray, device: int = 0) -> np.ndarray:

@@ -2814,6 +2814,125 @@ int hpmvs_depth_footprints_batch(const hpmvs_scene* s, const hpmvs_patch_batch* 
     return c.finish();
 }
 
+// An extend level's conflict graph (kernel_conflicts.hip, conflicts.hpp).  conflicts_call is the part the two
+// entry points share: the graph of device footprints F into the caller's CSR arrays.  The offsets and the totals are always
+// written; the adjacency arrays only when both capacities suffice (host pointers: they are staged here, so a call that fails on
+// capacity leaves the caller's arrays as they were).  n_flow / n_anti are host words in both forms.
+static int conflicts_check(const std::string& who, long long n, int M, int V, int n_levels, const uint32_t* flow_off, const uint32_t* flow_adj,
+                           size_t cap_flow, const uint32_t* anti_off, const uint32_t* anti_adj, size_t cap_anti, const uint32_t* n_flow,
+                           const uint32_t* n_anti) {
+    if (n < 0) return fail(HPMVS_ERR_ARG, who + ": negative n");
+    if (M < 1 || M > HPMVS_MAX_IMAGES) return fail(HPMVS_ERR_ARG, who + ": max_images outside 1 .. HPMVS_MAX_IMAGES");
+    if (V < 1 || V > conflicts::kMaxViews) return fail(HPMVS_ERR_ARG, who + ": the number of views is outside 1 .. 8191");
+    if (n_levels < 1 || n_levels > HPMVS_MAX_LEVELS) return fail(HPMVS_ERR_ARG, who + ": n_levels outside 1 .. HPMVS_MAX_LEVELS");
+    if (n * (long long)M >= (1ll << 28)) return fail(HPMVS_ERR_ARG, who + ": n * max_images must be below 2^28");
+    if (!flow_off || !anti_off || !n_flow || !n_anti) return fail(HPMVS_ERR_ARG, who + ": flow_off / anti_off / n_flow / n_anti missing");
+    if ((cap_flow && !flow_adj) || (cap_anti && !anti_adj)) return fail(HPMVS_ERR_ARG, who + ": an adjacency array is null but has a capacity");
+    return HPMVS_OK;
+}
+static int conflicts_call(Call& c, const std::string& who, const conflicts::Footprints& F, int on_device, uint32_t* dflow_off, uint32_t* flow_adj,
+                          size_t cap_flow, uint32_t* danti_off, uint32_t* anti_adj, size_t cap_anti, uint32_t* n_flow, uint32_t* n_anti,
+                          hipStream_t st) {
+    const unsigned long long* pairs = nullptr;
+    uint32_t nf = 0, na = 0;
+    const int rc = launch_conflicts(F, [&c](size_t bytes) { return c.scratch(bytes); }, dflow_off, danti_off, &pairs, &nf, &na, st);
+    if (rc == kConflictsMemory) return c.error() ? c.error() : fail(HPMVS_ERR_HIP, who + ": out of device memory");
+    if (rc == kConflictsTooMany)
+        return fail(HPMVS_ERR_STATE, who + ": more than 2^30 conflicting (reader, writer) pairs before duplicates are dropped");
+    if (rc != kConflictsOk) return fail(HPMVS_ERR_HIP, who + ": " + hipGetErrorString(hipGetLastError()));
+    *n_flow = nf; *n_anti = na;
+    const bool fits = nf <= cap_flow && na <= cap_anti;
+    if (fits && nf + (size_t)na) {
+        uint32_t *df = flow_adj, *da = anti_adj;
+        if (!on_device) {
+            df = nf ? (uint32_t*)c.scratch(4 * (size_t)nf) : nullptr; da = na ? (uint32_t*)c.scratch(4 * (size_t)na) : nullptr;
+            if ((nf && !df) || (na && !da)) return c.error();
+        }
+        launch_conflicts_adjacency(pairs, nf, na, df, da, st);
+        HIPCHK(hipGetLastError());
+        if (!on_device) {
+            HIPCHK(hipStreamSynchronize(st));
+            if (nf) HIPCHK(hipMemcpy(flow_adj, df, 4 * (size_t)nf, hipMemcpyDeviceToHost));
+            if (na) HIPCHK(hipMemcpy(anti_adj, da, 4 * (size_t)na, hipMemcpyDeviceToHost));
+        }
+    }
+    const int done = c.finish();   // (the offsets travel back here; waits in both forms: the scratch is freed on return)
+    if (done) return done;
+    if (!fits) return fail(HPMVS_ERR_ARG, who + ": capacity: the graph has " + std::to_string(nf) + " flow and " + std::to_string(na) +
+                                              " anti entries (n_flow / n_anti are set; allocate and call again)");
+    return HPMVS_OK;
+}
+// n == 0: the empty graph
+static int conflicts_empty(int on_device, uint32_t* flow_off, uint32_t* anti_off, uint32_t* n_flow, uint32_t* n_anti, hipStream_t st) {
+    if (on_device) {
+        HIPCHK(hipMemsetAsync(flow_off, 0, 4, st));
+        HIPCHK(hipMemsetAsync(anti_off, 0, 4, st));
+    } else { flow_off[0] = 0; anti_off[0] = 0; }
+    *n_flow = 0; *n_anti = 0;
+    return HPMVS_OK;
+}
+
+int hpmvs_conflicts_from_footprints(int device, int n, int max_images, int n_views, int n_levels, const int32_t* n_images, const int32_t* writes,
+                                    const int32_t* frees, const int32_t* attached, const int32_t* view_block, const uint8_t* is_event,
+                                    uint32_t* flow_off, uint32_t* flow_adj, size_t cap_flow, uint32_t* anti_off, uint32_t* anti_adj,
+                                    size_t cap_anti, uint32_t* n_flow, uint32_t* n_anti, int on_device, void* stream) {
+    const std::string who = "conflicts_from_footprints";
+    int rc = conflicts_check(who, n, max_images, n_views, n_levels, flow_off, flow_adj, cap_flow, anti_off, anti_adj, cap_anti, n_flow, n_anti);
+    if (rc) return rc;
+    if (n > 0 && (!n_images || !writes || !frees || !attached || !view_block)) return fail(HPMVS_ERR_ARG, who + ": a footprint array is null");
+    const int count = hpmvs_device_count();
+    if (count <= 0) return fail(HPMVS_ERR_NODEVICE, who + ": no HIP device visible");
+    if (device < 0 || device >= count) return fail(HPMVS_ERR_ARG, who + ": no such device");
+    HIPCHK(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) return conflicts_empty(on_device, flow_off, anti_off, n_flow, n_anti, st);
+    Call c(nullptr, on_device, st);
+    const size_t N = (size_t)n, M = (size_t)max_images, V = (size_t)n_views;
+    conflicts::Footprints F;
+    F.n = n; F.M = max_images; F.V = n_views; F.n_levels = n_levels;
+    F.n_images = c.in(n_images, N);
+    F.wr = c.in(writes, N * M * 4); F.fr = c.in(frees, N * M * 4); F.at = c.in(attached, N * M * 3); F.vb = c.in(view_block, N * V * 3);
+    F.is_event = c.in(is_event, N);
+    uint32_t* dfo = c.arr(flow_off, N + 1, Call::kCopyBack);   // (every offset is written)
+    uint32_t* dao = c.arr(anti_off, N + 1, Call::kCopyBack);
+    if ((rc = c.begin())) return rc;
+    return conflicts_call(c, who, F, on_device, dfo, flow_adj, cap_flow, dao, anti_adj, cap_anti, n_flow, n_anti, st);
+}
+
+int hpmvs_level_conflicts_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, const uint8_t* is_event, uint32_t* flow_off, uint32_t* flow_adj,
+                                size_t cap_flow, uint32_t* anti_off, uint32_t* anti_adj, size_t cap_anti, uint32_t* n_flow, uint32_t* n_anti,
+                                int on_device, void* stream) {
+    const std::string who = "level_conflicts_batch";
+    int rc = check_depth_batch(s, b, who.c_str());
+    if (rc) return rc;
+    // the levels a read can be on: the deepest pyramid of the scene's cameras (what getFullDepth walks)
+    int n_levels = 1;
+    for (int v = 0; v < s->n_views; v++) n_levels = std::max(n_levels, (int)s->hviews[v].n_levels);
+    if ((rc = conflicts_check(who, b->n, b->max_images, s->n_views, n_levels, flow_off, flow_adj, cap_flow, anti_off, anti_adj, cap_anti, n_flow, n_anti)))
+        return rc;
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (b->n == 0) return conflicts_empty(on_device, flow_off, anti_off, n_flow, n_anti, st);
+    Call c(s, on_device, st);
+    const size_t N = (size_t)b->n, M = (size_t)b->max_images, V = (size_t)s->n_views;
+    const DevBatch D = c.batch(b, Call::kRead);
+    const uint8_t* dev = c.in(is_event, N);
+    uint32_t* dfo = c.arr(flow_off, N + 1, Call::kCopyBack);
+    uint32_t* dao = c.arr(anti_off, N + 1, Call::kCopyBack);
+    // the footprints never leave the device: one block of scratch, cut into the four arrays
+    int32_t* fp = (int32_t*)c.scratch(4 * N * (11 * M + 3 * V));
+    if (!fp) return c.error();
+    if ((rc = c.begin())) return rc;
+    conflicts::Footprints F;
+    F.n = b->n; F.M = b->max_images; F.V = s->n_views; F.n_levels = n_levels;
+    F.n_images = D.n_images; F.is_event = dev;
+    int32_t *wr = fp, *fr = wr + N * M * 4, *at = fr + N * M * 4, *vb = at + N * M * 3;
+    F.wr = wr; F.fr = fr; F.at = at; F.vb = vb;
+    launch_depth_footprints(dev_scene(s), s->ddepth, D, wr, fr, at, vb, st);
+    HIPCHK(hipGetLastError());
+    return conflicts_call(c, who, F, on_device, dfo, flow_adj, cap_flow, dao, anti_adj, cap_anti, n_flow, n_anti, st);
+}
+
 // how many patches of the last refinement launch outgrew the batch kernel's 64-id rows and were redone by the wide kernel
 int hpmvs_last_wide_patches(const hpmvs_scene* s, int32_t* n) {
     if (!s || !n) return fail(HPMVS_ERR_ARG, "last_wide_patches: null argument");

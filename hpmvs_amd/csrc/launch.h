@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <functional>
+
+#include "conflicts.hpp"
 #include "dev_types.h"
 #include "jpeg.hpp"
 #include "seed_tree.hpp"
@@ -233,6 +236,17 @@ struct BorderForestScratch {
 size_t border_forest_temp_bytes(int n, int n_trees);   // (size_t)-1: a size query failed
 int launch_border_forest(int n_trees, const octree::Tree* trees, int n, const float* center, const float* scale,
                          const BorderForestScratch& s, const BorderForestOut& out, hipStream_t st);
+
+// an extend level's conflict graph (kernel_conflicts.hip, conflicts.hpp, include/hpmvs_amd.h: hpmvs_level_conflicts_batch).
+// launch_conflicts builds the sorted, unique pairs of the device footprints F and writes the n + 1 offsets of both lists; it is
+// host-synchronous (three counts are read back) and takes its device memory from `scratch`, which must outlive the adjacency
+// launch.  kConflictsTooMany: more raw pairs than conflicts::kMaxRawPairs, nothing written.  launch_conflicts_adjacency cuts the
+// pairs into the two adjacency arrays (flow_adj[n_flow], anti_adj[n_anti]).
+constexpr int kConflictsOk = 0, kConflictsHip = 1, kConflictsMemory = 2, kConflictsTooMany = 3;
+int launch_conflicts(const conflicts::Footprints& F, const std::function<void*(size_t)>& scratch, uint32_t* flow_off, uint32_t* anti_off,
+                     const unsigned long long** pairs_out, uint32_t* n_flow, uint32_t* n_anti, hipStream_t st);
+void launch_conflicts_adjacency(const unsigned long long* pairs, uint32_t n_flow, uint32_t n_anti, uint32_t* flow_adj, uint32_t* anti_adj,
+                                hipStream_t st);
 
 // the split into subtrees (kernel_octree_partition.hip, include/hpmvs_amd.h: hpmvs_octree_partition).  launch_octree_partition
 // reads the table launch_octree_build made and enqueues the leaf kernel, the sort, the one-wavefront loop and the assignment on

@@ -11,8 +11,10 @@ level's queue holds the candidates in the reference's order and, for `filter_ext
 (the patches CellProcessor::filter removed from a cell, right before that cell's candidates).  `extend_level` is the walk
 without events.
   * ONE hpmvs_expand_batch refines every candidate of the level (the refinement reads neither the maps nor the octree);
-  * ONE hpmvs_depth_footprints_batch names, per refined candidate, the map cells its gates read and the cells setDepths would
-    write, and per event the cells its setDepths(p, true) would write (a candidate that was not refined reads and writes none);
+  * ONE hpmvs_level_conflicts_batch gives the level's conflict graph: which refined candidate's setDepths, or which event's
+    setDepths(p, true), would write a map cell that another refined candidate's gates read or another node writes (a candidate
+    that was not refined reads and writes none).  The cells themselves stay on the device; `_walk` is handed one token per
+    conflicting pair in place of the pair's common cells (DESIGN.md §3.18);
   * the queue is then decided in WAVES.  A wave = one hpmvs_depth_gates_batch over the still undecided candidates against the
     maps as they are, a walk over the pending items in the reference's order, one ordered depth update for what was accepted
     (hpmvs_set_depths_batch when the wave holds additions only, else ONE hpmvs_depth_ops_batch in queue order: subtracting a
@@ -249,45 +251,14 @@ def _walk(queue, pre_key, post_key, refined, n_images, reads, writes, ev_cells, 
 
 def _level(scene, parents, width, occupied, margin, abs_int, o, keys, n_levels, sequential=True, events=None, event_cell=()):
     """CellProcessor::extend over `parents` with the subtraction events `events` (a Batch, or None): event j comes before the
-    candidates of parent event_cell[j] (non-decreasing).  The candidate steps, ONE hpmvs_depth_footprints_batch over the refined
-    candidates followed by the events, the queue, and the walk with the device behind its two callables."""
+    candidates of parent event_cell[j] (non-decreasing).  The candidate steps, the queue, ONE hpmvs_level_conflicts_batch over the
+    queue's events and refined candidates, and the walk with the device behind its two callables.  `n_levels` is not used: the
+    call takes the pyramid levels from the scene's cameras, as _pyramid_levels does."""
     out, pre_key, post_key, skip, refined, border = _candidates(scene, parents, width, keys, o)
     N = 6 * parents.n
     rc = np.nonzero(refined)[0]
     n_ev = events.n if events is not None else 0
     M = max(out.max_images, events.max_images) if n_ev else out.max_images
-    fp = _concat([_rows(out, rc, M)] + ([_rows(events, np.arange(n_ev), M)] if n_ev else []))
-    wr, fr, at, vb = api.depth_footprints_batch(scene, fp) if fp.n else (None,) * 4
-    fpi = {int(t): i for i, t in enumerate(rc)}
-    V = scene.n_views
-    reads_cache, writes_cache = {}, {}
-
-    def reads(t):
-        r = reads_cache.get(t)
-        if r is None:
-            i = fpi[t]
-            r = set()
-            for k in range(int(fp.n_images[i])):
-                if at[i, k, 0] >= 0:
-                    _full_depth_cells(at[i, k, 0], int(at[i, k, 1]), int(at[i, k, 2]), n_levels, r)
-                if fr[i, k, 0] >= 0:
-                    r.add(_cell(*fr[i, k]))
-            for v in range(V):
-                if vb[i, v, 0]:
-                    _full_depth_cells(v, int(vb[i, v, 1]), int(vb[i, v, 2]), n_levels, r)
-            reads_cache[t] = r
-        return r
-
-    def writes_row(i):
-        return {_cell(*wr[i, k]) for k in range(int(fp.n_images[i])) if wr[i, k, 0] >= 0}
-
-    def writes(t):
-        w = writes_cache.get(t)
-        if w is None:
-            w = writes_cache[t] = writes_row(fpi[t])
-        return w
-
-    ev_cells = [writes_row(len(rc) + j) for j in range(n_ev)]
     # the queue: per parent its events, then its six candidates
     queue = []
     j = 0
@@ -296,6 +267,37 @@ def _level(scene, parents, width, occupied, margin, abs_int, o, keys, n_levels, 
             queue.append(("e", j))
             j += 1
         queue.extend(("c", t) for t in range(6 * i, 6 * i + 6) if not skip[t])
+    # The level's conflict graph from ONE hpmvs_level_conflicts_batch over the nodes in queue order (the events and the refined
+    # candidates): no footprint and no cell key reaches the host.  _walk only ever intersects one node's reads /
+    # writes with other nodes' writes / reads, so every conflicting pair gets ONE token, in both sets it is a member of: ("rw",
+    # writer, reader) in the writer's writes (an event's ev_cells) and in the reader's reads, ("ww", candidate, event) in the
+    # candidate's writes and in the event's ev_cells.  Every intersection test then has the truth value it has over cells.
+    nodes = [(kind, t) for kind, t in queue if kind == "e" or refined[t]]
+    both = _concat([_rows(out, rc, M)] + ([_rows(events, np.arange(n_ev), M)] if n_ev else []))
+    at_row = {int(t): i for i, t in enumerate(rc)}
+    fp = _rows(both, [len(rc) + t if kind == "e" else at_row[t] for kind, t in nodes])
+    is_ev = np.array([kind == "e" for kind, _ in nodes], np.uint8)
+    read_tok, write_tok = [set() for _ in nodes], [set() for _ in nodes]
+    if fp.n:
+        flow_off, flow_adj, anti_off, anti_adj = api.level_conflicts(scene, fp, is_ev if n_ev else None)
+        for i in range(fp.n):
+            for j in flow_adj[flow_off[i]:flow_off[i + 1]].tolist():
+                if is_ev[i]:
+                    write_tok[i].add(("ww", j, i)); write_tok[j].add(("ww", j, i))
+                else:
+                    write_tok[j].add(("rw", j, i)); read_tok[i].add(("rw", j, i))
+            for j in anti_adj[anti_off[i]:anti_off[i + 1]].tolist():
+                if is_ev[j]:
+                    write_tok[i].add(("ww", i, j)); write_tok[j].add(("ww", i, j))
+                else:
+                    write_tok[i].add(("rw", i, j)); read_tok[j].add(("rw", i, j))
+    node_of = {t: i for i, (kind, t) in enumerate(nodes) if kind == "c"}
+    reads = lambda t: read_tok[node_of[t]]
+    writes = lambda t: write_tok[node_of[t]]
+    ev_cells = [None] * n_ev
+    for i, (kind, t) in enumerate(nodes):
+        if kind == "e":
+            ev_cells[t] = write_tok[i]
 
     def gates(todo):
         v, b, f = api.depth_gates_batch(scene, _rows(out, todo), margin, abs_int)

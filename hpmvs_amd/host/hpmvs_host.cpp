@@ -1247,6 +1247,46 @@ extern "C" int hpmvs_host_selftest_event_graph(unsigned seed, int n, int n_views
     return bad;
 }
 
+// Hook (tests/test_cpu_conflicts_host_build.py, tools/level_conflicts_scale.py; no device needed): the host build of the level's
+// graph -- clear_event_reads, build_conflict_graph, add_event_edges, exactly what walk_level runs -- on footprint arrays of the
+// caller's, in the layouts of hpmvs_depth_footprints_batch, with every list sorted so that the result can be compared byte for
+// byte with hpmvs_conflicts_from_footprints.  Same capacity contract: offsets and totals always, the lists when both fit (0),
+// else -2; -1 for bad arguments.
+extern "C" int hpmvs_host_conflict_graph(int n, int max_images, int n_views, int n_levels, int max_w, int max_h, const int32_t* n_images,
+                                         const int32_t* writes, const int32_t* frees, const int32_t* attached, const int32_t* view_block,
+                                         const uint8_t* is_event, uint32_t* flow_off, uint32_t* flow_adj, size_t cap_flow, uint32_t* anti_off,
+                                         uint32_t* anti_adj, size_t cap_anti, uint32_t* n_flow, uint32_t* n_anti) {
+    if (n < 1 || max_images < 1 || n_views < 1 || n_levels < 1 || n_levels > HPMVS_MAX_LEVELS || max_w < 1 || max_h < 1 || !n_images || !writes ||
+        !frees || !attached || !view_block || !flow_off || !anti_off || !n_flow || !n_anti)
+        return -1;
+    RawFootprints F;
+    F.n = (size_t)n; F.M = (size_t)max_images; F.V = (size_t)n_views;
+    F.nimg.assign(n_images, n_images + F.n);
+    for (size_t i = 0; i < F.n; i++) F.nimg[i] = F.nimg[i] < 0 ? 0 : (F.nimg[i] > max_images ? max_images : F.nimg[i]);
+    F.wr.assign(writes, writes + F.n * F.M * 4); F.fr.assign(frees, frees + F.n * F.M * 4);
+    F.at.assign(attached, attached + F.n * F.M * 3); F.vb.assign(view_block, view_block + F.n * F.V * 3);
+    ConflictGraph G;
+    if (is_event) {
+        const std::vector<uint8_t> ev(is_event, is_event + F.n);
+        clear_event_reads(F, ev);
+        build_conflict_graph(F, n_levels, max_w, max_h, G);
+        add_event_edges(F, ev, G);
+    } else {
+        build_conflict_graph(F, n_levels, max_w, max_h, G);
+    }
+    for (size_t i = 0; i < F.n; i++) {
+        std::sort(G.flow_adj.begin() + G.flow_off[i], G.flow_adj.begin() + G.flow_off[i + 1]);
+        std::sort(G.anti_adj.begin() + G.anti_off[i], G.anti_adj.begin() + G.anti_off[i + 1]);
+    }
+    std::copy(G.flow_off.begin(), G.flow_off.end(), flow_off);
+    std::copy(G.anti_off.begin(), G.anti_off.end(), anti_off);
+    *n_flow = (uint32_t)G.flow_adj.size(); *n_anti = (uint32_t)G.anti_adj.size();
+    if (G.flow_adj.size() > cap_flow || G.anti_adj.size() > cap_anti) return -2;
+    if (flow_adj) std::copy(G.flow_adj.begin(), G.flow_adj.end(), flow_adj);
+    if (anti_adj) std::copy(G.anti_adj.begin(), G.anti_adj.end(), anti_adj);
+    return 0;
+}
+
 bool Scene::depthFootprints(const Patch3d* const* patches, size_t n, std::vector<std::vector<uint64_t> >& reads,
                             std::vector<std::vector<uint64_t> >& writes, int nLevels) const {
     reads.assign(n, std::vector<uint64_t>());
@@ -1258,6 +1298,43 @@ bool Scene::depthFootprints(const Patch3d* const* patches, size_t n, std::vector
         for_write_cells(F, i, [&](uint64_t k) { writes[i].push_back(k); return false; });
     }
     return true;
+}
+
+namespace {
+// The level's conflict graph from ONE hpmvs_level_conflicts_batch: no footprint reaches the host.  Room for 16
+// edges per node in each list first; when that does not hold them the call has set the totals all the same, and a second call
+// gets arrays of that size.  Returns 0, 1 when the device refuses the input's size (HPMVS_ERR_STATE: more than 2^30 raw pairs --
+// the caller may fall back to build_conflict_graph), -1 for any other failure (reported).
+int device_conflict_graph(const Scene& sc, const Patch3d* const* patches, size_t n, const uint8_t* isEvent, std::vector<uint32_t>& flowOff,
+                          std::vector<uint32_t>& flowAdj, std::vector<uint32_t>& antiOff, std::vector<uint32_t>& antiAdj) {
+    hpmvs_scene* dev = sc.deviceScene();
+    if (!dev) return -1;
+    flowOff.assign(n + 1, 0); antiOff.assign(n + 1, 0);
+    flowAdj.clear(); antiAdj.clear();
+    if (n == 0) return 0;
+    HostBatch hb(patches, n);
+    const uint32_t unset = 0xFFFFFFFFu;
+    size_t capFlow = 16 * n + 1024, capAnti = capFlow;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        flowAdj.resize(capFlow); antiAdj.resize(capAnti);
+        uint32_t nFlow = unset, nAnti = unset;
+        const int rc = hpmvs_level_conflicts_batch(dev, &hb.b, isEvent, flowOff.data(), flowAdj.data(), capFlow, antiOff.data(), antiAdj.data(), capAnti,
+                                                   &nFlow, &nAnti, 0, nullptr);
+        if (rc == HPMVS_OK) { flowAdj.resize(nFlow); antiAdj.resize(nAnti); return 0; }
+        if (rc == HPMVS_ERR_STATE) return 1;   // (a scene without depth maps answers so too: the host path then reports it)
+        if (rc == HPMVS_ERR_ARG && attempt == 0 && nFlow != unset && nAnti != unset && (nFlow > capFlow || nAnti > capAnti)) {
+            capFlow = nFlow; capAnti = nAnti;   // (the capacity answer: the totals are valid)
+            continue;
+        }
+        std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl;
+        return -1;
+    }
+    return -1;
+}
+}  // namespace
+
+bool Scene::levelConflicts(const Patch3d* const* patches, size_t n, const uint8_t* isEvent, LevelGraph& graph) const {
+    return device_conflict_graph(*this, patches, n, isEvent, graph.flowOff, graph.flowAdj, graph.antiOff, graph.antiAdj) == 0;
 }
 
 // ---------------------------------------------------------------- PatchOptimizer
@@ -1886,6 +1963,18 @@ static uint64_t grid_leaf_key(const Eigen::Vector3f& p, float width, void*) {
     return (uint64_t)(((ix + (1 << 20)) << 42) | ((iy + (1 << 20)) << 21) | (iz + (1 << 20)));
 }
 
+// Where walk_level makes its conflict graph: on the host from the footprints, unless HPMVS_DEVICE_GRAPH=1 asks for ONE
+// hpmvs_level_conflicts_batch.  On the 98 304-candidate level of the 50-view 4K scene the device graph's "footprints + conflict
+// graph" is 4.3 ms against 6.9 ms, but the host build's own spread over five runs was 3.2 ms there: by the decision rule of
+// DESIGN.md §3.18 that does not make it the default.  HPMVS_HOST_GRAPH=1 names the host build and wins over the other switch.
+static bool graph_on_device() {
+    static const bool on = [] {
+        const char *d = getenv("HPMVS_DEVICE_GRAPH"), *h = getenv("HPMVS_HOST_GRAPH");
+        return d && d[0] == '1' && !(h && h[0] == '1');
+    }();
+    return on;
+}
+
 // The deepest pyramid of the scene's cameras: the levels getFullDepth walks, so the levels a read can be on (-1: more than the gates support)
 static int pyramid_levels(const Scene* scene, const char* who) {
     int nLevels = 1;
@@ -1969,12 +2058,22 @@ static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, 
             pending.push_back(t);
         }
     }
-    RawFootprints F;
-    if (!raw_footprints(*scene, nodes.data(), nodes.size(), F)) return false;
-    const double t_fp = level_now();
-    // the level's conflict graph (who writes what whom reads): once, from the footprints
+    // The level's conflict graph (who writes what whom reads), once.  With graph_on_device() it is ONE hpmvs_level_conflicts_batch
+    // and no footprint reaches the host; build_conflict_graph / add_event_edges below are the same graph from the
+    // footprints on the host -- the default (graph_on_device), and the fallback when the device refuses the level's size.  The
+    // walk only asks whether a list holds a node of this wave, so the order inside a list does not matter.
     ConflictGraph G;
-    if (sequential && F.n > 0) {   // (the plain frontier round decides everything in one wave)
+    bool haveGraph = false;
+    if (sequential && !nodes.empty() && graph_on_device()) {   // (the plain frontier round decides everything in one wave)
+        const int rc = device_conflict_graph(*scene, nodes.data(), nodes.size(), nEvents ? isEvent.data() : nullptr, G.flow_off, G.flow_adj,
+                                             G.anti_off, G.anti_adj);
+        if (rc < 0) return false;
+        haveGraph = rc == 0;
+    }
+    RawFootprints F;   // (only the host build reads footprints: none are fetched for the device graph or for the one-wave round)
+    if (!haveGraph && sequential && !raw_footprints(*scene, nodes.data(), nodes.size(), F)) return false;
+    const double t_fp = haveGraph ? t_ref : level_now();   // (on the device the two steps are one call: it is timed as the graph)
+    if (!haveGraph && sequential && F.n > 0) {
         int maxW = 1, maxH = 1;
         for (const Image& im : scene->images_) { maxW = std::max(maxW, im.getWidth()); maxH = std::max(maxH, im.getHeight()); }
         if (nEvents) clear_event_reads(F, isEvent);

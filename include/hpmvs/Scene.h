@@ -216,6 +216,15 @@ public:
     // pixels, every pyramid level) and pixelFreeTests' cell; writes[i]: the cell per attached image.  nLevels: pyramid levels.
     bool depthFootprints(const Patch3d* const* patches, size_t n, std::vector<std::vector<uint64_t> >& reads,
                          std::vector<std::vector<uint64_t> >& writes, int nLevels = 6) const;
+    // The conflict graph of one level over those cells, made on the device (ONE hpmvs_level_conflicts_batch: no footprint reaches
+    // the host): `patches` are the level's nodes in queue order, isEvent[i] != 0 marks a subtraction event (writes, no reads;
+    // nullptr: all candidates).  flow[i]: the nodes j < i that write a cell i reads (an event i: the candidates that write a cell
+    // it writes); anti[i]: the candidates j < i that read a cell i writes, and for a candidate i the events j < i that write one.
+    // CSR, every list ascending without duplicates; the pyramid levels are the scene's cameras'.
+    struct LevelGraph {
+        std::vector<uint32_t> flowOff, flowAdj, antiOff, antiAdj;
+    };
+    bool levelConflicts(const Patch3d* const* patches, size_t n, const uint8_t* isEvent, LevelGraph& graph) const;
     // The scheduler's octree as CellProcessor::extend consults it (CellProcessor.cpp:122-125, 147-154), for a list of points as
     // ONE batched GPU call (hpmvs_octree_locate_batch): root->at(p), getRoot()->contains(p) and the leaf
     // DynOctTree::addConditional(p, addWidth) would put p in.  OctreeIndex names the tree by path keys (sentinel bit, 3 bits per

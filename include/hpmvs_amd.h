@@ -343,6 +343,37 @@ int hpmvs_level_support_batch(const hpmvs_scene *s, const hpmvs_patch_batch *b, 
  *   view_block [n][n_views][3]     every view v: 1 if viewBlockTest examines it, ix0, iy0 of its 3x3 block (read the same way) */
 int hpmvs_depth_footprints_batch(const hpmvs_scene *s, const hpmvs_patch_batch *b, int32_t *writes, int32_t *frees,
                                  int32_t *attached, int32_t *view_block, int on_device, void *stream);
+/* The conflict graph of one extend level, made on the device from those footprints: what the wave walk of a level needs and
+ * nothing else (hpmvs_amd/csrc/conflicts.hpp states the cells and has the host restatement).  Nodes are the
+ * batch's patches in queue order; is_event[i] != 0 marks a subtraction event (writes, NO reads; NULL: all candidates).
+ *   flow[i], i a candidate: nodes j < i of either kind that write a cell i reads
+ *   flow[i], i an event:    candidates j < i that write a cell i writes
+ *   anti[i], i a candidate: candidates j < i that read a cell i writes, and events j < i that write a cell i writes
+ *   anti[i], i an event:    candidates j < i that read a cell i writes
+ * A read block from (ix0, iy0) covers the cells x0 >> (1 + l) .. x1 >> (1 + l), x1 = ix0 + 2, x0 = max(ix0, 0), of every level
+ * l < n_levels (likewise y; none when x1 < 0 or y1 < 0); a pixelFreeTests read is its one cell.  Ignored: entries with view < 0 or
+ * view >= n_views, writes / frees on a level outside [0, n_levels), cells or blocks beyond 2^24 (no map has them).  No edge
+ * between two events, no node its own neighbour.
+ * Output: CSR, *_off[n + 1] and *_adj, every list ascending without duplicates -- one byte string per input.  The offsets and the
+ * totals *n_flow / *n_anti (HOST words in both forms) are always written; the adjacency arrays only when cap_flow >= *n_flow and
+ * cap_anti >= *n_anti (entries), else HPMVS_ERR_ARG with "capacity" in hpmvs_last_error and the totals valid: allocate and call
+ * again (an adjacency array may be NULL with capacity 0).  n == 0, nodes without images and is_event == NULL are valid.
+ * HPMVS_ERR_ARG before any write for n_levels outside 1 .. HPMVS_MAX_LEVELS, max_images outside 1 .. HPMVS_MAX_IMAGES, n_views
+ * outside 1 .. 8191, n * max_images >= 2^28 and null arrays; HPMVS_ERR_STATE before any output when more than 2^30 (reader, writer)
+ * pairs meet before duplicates are dropped (every node on one cell; counted by key-range bounds, a node's own writes included, so
+ * such an input is refused without a walk over its pairs).  Host-synchronous also with on_device = 1 (three counts are
+ * read back on the way; the scratch is freed on return).
+ * hpmvs_level_conflicts_batch runs the footprint kernel into scratch of its own -- no footprint leaves the device -- with
+ * n_levels = the deepest pyramid of the scene's cameras.  hpmvs_conflicts_from_footprints takes footprint arrays in the layouts
+ * above (host or device pointers; n_images[n]: the entries of a row that count) and needs no scene. */
+int hpmvs_level_conflicts_batch(const hpmvs_scene *s, const hpmvs_patch_batch *b, const uint8_t *is_event, uint32_t *flow_off,
+                                uint32_t *flow_adj, size_t cap_flow, uint32_t *anti_off, uint32_t *anti_adj, size_t cap_anti,
+                                uint32_t *n_flow, uint32_t *n_anti, int on_device, void *stream);
+int hpmvs_conflicts_from_footprints(int device, int n, int max_images, int n_views, int n_levels, const int32_t *n_images,
+                                    const int32_t *writes, const int32_t *frees, const int32_t *attached, const int32_t *view_block,
+                                    const uint8_t *is_event, uint32_t *flow_off, uint32_t *flow_adj, size_t cap_flow,
+                                    uint32_t *anti_off, uint32_t *anti_adj, size_t cap_anti, uint32_t *n_flow, uint32_t *n_anti,
+                                    int on_device, void *stream);
 
 /* ---- CellProcessor::regularize for a priority level (src/hpmvs/CellProcessor.cpp:309-367, processCell :369-420) ----------------
  * The octree stays the scheduler's.  For each call it passes a VERSIONED snapshot of the nonempty leaves: a leaf is part of the
