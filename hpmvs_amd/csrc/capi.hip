@@ -34,6 +34,8 @@ static constexpr int kQueueSlots = 16;
 static constexpr size_t kQueueSlotBytes = 1024;
 static constexpr int kServiceMaxPatches = 4;  // host batches up to this size go through the open batch (Service)  // the counter block at the head of a workspace (zeroed per launch)
 
+static size_t reg_align(size_t v) { return (v + 255) & ~(size_t)255; }  // regions of a workspace or a scratch block start at multiples of 256 bytes
+
 static thread_local std::string g_err;
 
 static int fail(int code, const std::string& msg) {
@@ -143,11 +145,18 @@ static int acquire_workspace(const hpmvs_scene* s, int32_t** q, int* slot, hipSt
     s->last_queue = *q;
     return HPMVS_OK;
 }
-static int release_workspace(const hpmvs_scene* s, int slot, hipStream_t st) {
-    HIPCHK(hipEventRecord(s->slot_done[slot], st));
-    s->slot_used[slot] = true;
-    return HPMVS_OK;
-}
+// A workspace (q) for the work a call enqueues on `st`: declare it with s->mu held, and check rc.  Whatever happens behind the
+// declaration, the slot's event is recorded behind the work that was enqueued, so that the next user of the workspace waits for it.
+struct Workspace {
+    const hpmvs_scene* s;
+    hipStream_t st;
+    int32_t* q = nullptr;
+    int slot = 0, rc;
+    Workspace(const hpmvs_scene* s_, hipStream_t st_) : s(s_), st(st_) { rc = acquire_workspace(s, &q, &slot, st); }
+    ~Workspace() { if (!rc) { hipEventRecord(s->slot_done[slot], st); s->slot_used[slot] = true; } }
+    Workspace(const Workspace&) = delete;
+    Workspace& operator=(const Workspace&) = delete;
+};
 
 extern "C" {
 
@@ -966,12 +975,9 @@ static int enqueue_refinement(const hpmvs_scene* s, const DevOptions& d, const D
     // milliseconds) and drained.  Callers that come later start a new one, which queues behind this launch (service_open).
     if ((rc = service_quiesce(s))) return rc;
     {
-        int32_t* q;
-        int slot;
-        if ((rc = acquire_workspace(s, &q, &slot, st))) return rc;
-        // whatever happens below, the slot's event is recorded behind the work that was enqueued, so that the next
-        // user of this workspace waits for it
-        struct Release { const hpmvs_scene* s; int slot; hipStream_t st; ~Release() { hipEventRecord(s->slot_done[slot], st); s->slot_used[slot] = true; } } rel{s, slot, st};
+        Workspace ws(s, st);
+        if (ws.rc) return ws.rc;
+        int32_t* q = ws.q;
         HIPCHK(hipMemsetAsync(q, 0, kQueueSlotBytes, st));
         HIPCHK(hipEventRecord(s->ev0, st));
         launch_optimize(dev_scene(s), d, batch, q, s->n_cus, st);
@@ -1809,7 +1815,6 @@ int hpmvs_level_support_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, 
 // (kernel_regularize.hip).  Every device byte comes from a launch workspace: [1 KB counter block, untouched] [header] [hash keys]
 // [hash values] and, for host pointers, the leaf table and the cells in chunks that fit the rest.  The scene lock is held for the
 // whole call (the workspace is this call's until its last kernel has been enqueued).
-static size_t reg_align(size_t v) { return (v + 255) & ~(size_t)255; }
 int hpmvs_regularize_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, const float* cell_width, const int32_t* position,
                            const uint8_t* expanded, const hpmvs_leaf_table* lt, float* flatness, int32_t* n_neighbours,
                            int32_t* neighbour_leaf, int on_device, void* stream) {
@@ -1854,11 +1859,9 @@ int hpmvs_regularize_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b, con
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::recursive_mutex> lk(s->mu);
     if ((rc = service_quiesce(s))) return rc;
-    int32_t* q;
-    int slot;
-    if ((rc = acquire_workspace(s, &q, &slot, st))) return rc;
-    struct Release { const hpmvs_scene* s; int slot; hipStream_t st; ~Release() { hipEventRecord(s->slot_done[slot], st); s->slot_used[slot] = true; } } rel{s, slot, st};
-    char* w = (char*)q;
+    Workspace ws(s, st);
+    if (ws.rc) return ws.rc;
+    char* w = (char*)ws.q;
     int32_t* hdr = (int32_t*)(w + o_hdr);
     RegTree t;
     t.root[0] = lt->root_center[0]; t.root[1] = lt->root_center[1]; t.root[2] = lt->root_center[2]; t.root[3] = lt->root_width;
@@ -2104,6 +2107,28 @@ static int octree_table_build(const hpmvs_octree_index* t, const unsigned long l
     if (h & octree::kBadOrphan) return fail(HPMVS_ERR_ARG, who + ": a key's parent prefix is neither a branch nor the root");
     return HPMVS_OK;
 }
+// The single tree's table in a launch workspace, for the rest of a call that declares it behind begin() (check rc): the scene lock
+// is held from here to the call's return -- the workspace is the call's until its last kernel has been enqueued -- the open batches
+// are drained and the table is built and verified.
+struct WorkspaceTable {
+    std::lock_guard<std::recursive_mutex> lk;
+    std::optional<Workspace> ws;   // (behind lk: released before the lock is)
+    const float root[4];
+    unsigned long long* keys = nullptr;
+    int32_t* vals = nullptr;
+    const uint32_t slots;
+    int rc;
+    WorkspaceTable(const hpmvs_scene* s, const hpmvs_octree_index* t, const unsigned long long* dbk, const unsigned long long* dlk,
+                   const OctreeLayout& L, hipStream_t st, const std::string& who)
+        : lk(s->mu), root{t->root_center[0], t->root_center[1], t->root_center[2], t->root_width}, slots((uint32_t)L.slots) {
+        if ((rc = service_quiesce(s))) return;
+        ws.emplace(s, st);
+        if ((rc = ws->rc)) return;
+        char* w = (char*)ws->q;
+        keys = (unsigned long long*)(w + L.o_keys); vals = (int32_t*)(w + L.o_vals);
+        rc = octree_table_build(t, dbk, dlk, L, w, st, who);
+    }
+};
 // root->at(p), Cell::contains and addConditional's target for a level's points against the scheduler's octree
 int hpmvs_octree_locate_batch(const hpmvs_scene* s, const hpmvs_octree_index* t, int n, const float* points, const float* add_width,
                               uint8_t* inside, uint64_t* leaf_key, int32_t* leaf_index, float* leaf_width, float* leaf_center,
@@ -2128,19 +2153,53 @@ int hpmvs_octree_locate_batch(const hpmvs_scene* s, const hpmvs_octree_index* t,
     out.leaf_center = c.arr(leaf_center, 3 * np, Call::kCopyBack);
     out.target_key = (unsigned long long*)c.arr(target_key, np, Call::kCopyBack);
     if ((rc = c.begin(st))) return rc;
-    // the scene lock is held from here on: the workspace is this call's until its last kernel has been enqueued
-    std::lock_guard<std::recursive_mutex> lk(s->mu);
-    if ((rc = service_quiesce(s))) return rc;
-    int32_t* q;
-    int slot;
-    if ((rc = acquire_workspace(s, &q, &slot, st))) return rc;
-    struct Release { const hpmvs_scene* s; int slot; hipStream_t st; ~Release() { hipEventRecord(s->slot_done[slot], st); s->slot_used[slot] = true; } } rel{s, slot, st};
-    char* w = (char*)q;
-    if ((rc = octree_table_build(t, dbk, dlk, L, w, st, who))) return rc;
-    const float root[4] = {t->root_center[0], t->root_center[1], t->root_center[2], t->root_width};
-    launch_octree_locate(root, (unsigned long long*)(w + L.o_keys), (int32_t*)(w + L.o_vals), (uint32_t)L.slots, n, dpts, daw, out, st);
+    WorkspaceTable tt(s, t, dbk, dlk, L, st, who);
+    if (tt.rc) return tt.rc;
+    launch_octree_locate(tt.root, tt.keys, tt.vals, tt.slots, n, dpts, daw, out, st);
     HIPCHK(hipGetLastError());
     return c.finish();
+}
+// ---- what an extend level is whichever look-ups it makes (hpmvs_extend_tree_batch, hpmvs_extend_forest_batch): the shape of
+// its candidates, the key arrays, and the enqueue order around the two look-up launches
+static int extend_out_check(const std::string& who, const hpmvs_patch_batch* parents, const hpmvs_patch_batch* out) {
+    if (out->n != parents->n * expand_fanout(HPMVS_EXPAND_EXTEND)) return fail(HPMVS_ERR_ARG, who + ": out->n must be 6 * parents->n");
+    if (out->max_images != parents->max_images) return fail(HPMVS_ERR_ARG, who + ": max_images mismatch");
+    if (parents->n > 0 && (!out->center || !out->normal || !out->scale || !out->n_images || !out->images || !out->ok))
+        return fail(HPMVS_ERR_ARG, who + ": missing array");
+    return HPMVS_OK;
+}
+static ExtendTreeOut extend_keys(Call& c, const hpmvs_extend_tree_keys* keys, size_t nc) {
+    ExtendTreeOut K;
+    memset(&K, 0, sizeof(K));
+    if (keys) {   // (the two kernels write every entry of what they are given: no zero fill)
+        K.skip = c.arr(keys->skip, nc, Call::kCopyBack);
+        K.pre_inside = c.arr(keys->pre_inside, nc, Call::kCopyBack);
+        K.pre_key = (unsigned long long*)c.arr(keys->pre_key, nc, Call::kCopyBack);
+        K.border = c.arr(keys->border, nc, Call::kCopyBack);
+        K.post_key = (unsigned long long*)c.arr(keys->post_key, nc, Call::kCopyBack);
+    }
+    return K;
+}
+// dcw: [parents->n], cell_width of expand_init / expand_gate: `width` for every parent (mode 0 reads no cell_center).  pre / post
+// enqueue the look-ups before and after the refinement.
+static int extend_enqueue(const hpmvs_scene* s, const hpmvs_options* o, const hpmvs_patch_batch* parents, const DevBatch& P, const DevBatch& D,
+                          float width, float* dcw, hipStream_t st, const std::function<void()>& pre, const std::function<void()>& post) {
+    const DevOptions d = make_dev_options(o);
+    uint32_t wbits;
+    memcpy(&wbits, &width, 4);
+    int rc;
+    std::lock_guard<std::recursive_mutex> lk(s->mu);
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)dcw, (int)wbits, (size_t)parents->n, st));
+    launch_expand_init(dev_scene(s), HPMVS_EXPAND_EXTEND, parents->n, P, nullptr, dcw, nullptr, D, st);
+    HIPCHK(hipGetLastError());
+    pre();
+    HIPCHK(hipGetLastError());
+    if ((rc = enqueue_refinement(s, d, D, st))) return rc;
+    launch_expand_gate(HPMVS_EXPAND_EXTEND, parents->n, P, nullptr, dcw, D, st);
+    HIPCHK(hipGetLastError());
+    post();
+    HIPCHK(hipGetLastError());
+    return HPMVS_OK;
 }
 // One extend level's candidate steps against the real tree (CellProcessor.cpp:84-178; kernel_extend_tree.hip): expand_init, the pre
 // look-up, the refinement, the gates, the post look-up.  The table is built once and must outlive the refinement launch, which
@@ -2149,20 +2208,16 @@ int hpmvs_octree_locate_batch(const hpmvs_scene* s, const hpmvs_octree_index* t,
 // pinned host memory is cleared in place by begin().
 int hpmvs_extend_tree_batch(const hpmvs_scene* s, const hpmvs_options* o, const hpmvs_octree_index* t, const hpmvs_patch_batch* parents,
                             float width, hpmvs_patch_batch* out, const hpmvs_extend_tree_keys* keys, int on_device, void* stream) {
-    const char* who = "extend_tree_batch";
+    const std::string who = "extend_tree_batch";
     int rc = check_batch(s, o, parents);
     if (rc) return rc;
     if ((rc = check_batch_shape(s, o, out))) return rc;
     OctreeLayout L;
     if ((rc = octree_index_check(s, t, 0, nullptr, who, &L, true))) return rc;
-    const int N = expand_fanout(HPMVS_EXPAND_EXTEND);
-    if (out->n != parents->n * N) return fail(HPMVS_ERR_ARG, "extend_tree_batch: out->n must be 6 * parents->n");
-    if (out->max_images != parents->max_images) return fail(HPMVS_ERR_ARG, "extend_tree_batch: max_images mismatch");
-    if (parents->n > 0 && (!out->center || !out->normal || !out->scale || !out->n_images || !out->images || !out->ok))
-        return fail(HPMVS_ERR_ARG, "extend_tree_batch: missing array");
+    if ((rc = extend_out_check(who, parents, out))) return rc;
     if (!std::isfinite(width) || octree::level_depth(t->root_width, width) < 0)
-        return fail(HPMVS_ERR_ARG, "extend_tree_batch: width is not the width of a level of the tree");
-    const size_t nb = (size_t)t->n_branches, nl = (size_t)t->n_leaves, n = (size_t)parents->n, nc = n * N;
+        return fail(HPMVS_ERR_ARG, who + ": width is not the width of a level of the tree");
+    const size_t nb = (size_t)t->n_branches, nl = (size_t)t->n_leaves, n = (size_t)parents->n, nc = (size_t)out->n;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     Call ck(s, on_device, st);
@@ -2177,41 +2232,25 @@ int hpmvs_extend_tree_batch(const hpmvs_scene* s, const hpmvs_options* o, const 
     if (n == 0) return ck.finish();
     Call c(s, on_device, st);
     const DevBatch P = c.batch(parents, Call::kRead), D = c.batch(out, Call::kCreate);
-    ExtendTreeOut K;
-    memset(&K, 0, sizeof(K));
-    if (keys) {   // (the two kernels write every entry of what they are given: no zero fill)
-        K.skip = c.arr(keys->skip, nc, Call::kCopyBack);
-        K.pre_inside = c.arr(keys->pre_inside, nc, Call::kCopyBack);
-        K.pre_key = (unsigned long long*)c.arr(keys->pre_key, nc, Call::kCopyBack);
-        K.border = c.arr(keys->border, nc, Call::kCopyBack);
-        K.post_key = (unsigned long long*)c.arr(keys->post_key, nc, Call::kCopyBack);
-    }
+    const ExtendTreeOut K = extend_keys(c, keys, nc);
     if ((rc = c.begin(st))) return rc;
-    const DevOptions d = make_dev_options(o);
     const float root[4] = {t->root_center[0], t->root_center[1], t->root_center[2], t->root_width};
     const unsigned long long* tk = (const unsigned long long*)(w + L.o_keys);
     const int32_t* tv = (const int32_t*)(w + L.o_vals);
-    uint32_t wbits;
-    memcpy(&wbits, &width, 4);
-    {
-        std::lock_guard<std::recursive_mutex> lk(s->mu);
-        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)dcw, (int)wbits, n, st));
-        launch_expand_init(dev_scene(s), HPMVS_EXPAND_EXTEND, parents->n, P, nullptr, dcw, nullptr, D, st);
-        HIPCHK(hipGetLastError());
-        launch_extend_tree_pre(root, tk, tv, (uint32_t)L.slots, (int)nc, width, D, K, st);
-        HIPCHK(hipGetLastError());
-        if ((rc = enqueue_refinement(s, d, D, st))) return rc;
-        launch_expand_gate(HPMVS_EXPAND_EXTEND, parents->n, P, nullptr, dcw, D, st);
-        HIPCHK(hipGetLastError());
-        launch_extend_tree_post(root, tk, tv, (uint32_t)L.slots, (int)nc, width, D, K, st);
-        HIPCHK(hipGetLastError());
-    }
+    rc = extend_enqueue(s, o, parents, P, D, width, dcw, st,
+                        [&] { launch_extend_tree_pre(root, tk, tv, (uint32_t)L.slots, (int)nc, width, D, K, st); },
+                        [&] { launch_extend_tree_post(root, tk, tv, (uint32_t)L.slots, (int)nc, width, D, K, st); });
+    if (rc) return rc;
     if ((rc = c.finish())) return rc;
     return ck.finish();   // (waits in both forms: the table is freed when this call returns)
 }
-// what the host can check of a forest with n_trees > 0 whose offset arrays are there: the offsets, the key arrays, the roots
-static int forest_host_check(const std::string& who, const hpmvs_octree_forest* f) {
+// what the host can check of a forest: the count, then the offsets, the key arrays, the roots.  A forest without trees has nothing
+// more to check: it is refused with no_tree where the caller has rows that would name a tree (null: it is fine).
+static int forest_host_check(const std::string& who, const hpmvs_octree_forest* f, const char* no_tree) {
     const int T = f->n_trees;
+    if (T < 0) return fail(HPMVS_ERR_ARG, who + ": negative count");
+    if (T == 0) return no_tree ? fail(HPMVS_ERR_ARG, who + ": " + no_tree) : HPMVS_OK;
+    if (!f->root || !f->branch_first || !f->leaf_first) return fail(HPMVS_ERR_ARG, who + ": root / branch_first / leaf_first missing");
     int32_t bad = octree::forest_offsets_bad(T, f->branch_first);
     if (bad < 0) bad = octree::forest_offsets_bad(T, f->leaf_first);
     if (bad >= 0) return fail(HPMVS_ERR_ARG, who + ": tree " + std::to_string(bad) + ": the key offsets must start at 0 and never decrease");
@@ -2234,6 +2273,51 @@ static int forest_table_fail(const std::string& who, uint32_t finding) {
     if (b & octree::kBadTwice) return fail(HPMVS_ERR_ARG, tree + ": a key occurs twice (within the branch or leaf keys, or in both)");
     return fail(HPMVS_ERR_ARG, tree + ": a key's parent prefix is neither a branch nor the root");
 }
+// The forest's block (octree::ForestBlock) in scratch of the Call that carries the forest's arrays; f has passed
+// forest_host_check.  Before begin(): the constructor declares the two key arrays, which lead the call's copies, and take() --
+// behind the caller's own arrays -- the block with `tail` bytes of the caller's behind it, and fills the header's host image (hdr;
+// the extra bytes are the caller's to set).  After begin(): build() uploads the header, zeroes the keys and enqueues the tables'
+// build; verdict(), behind whatever kernel of the caller's folds into the same words, is the call's ONE read-back of them and the
+// refusal of bad tables.  The other words are the caller's to read.
+struct ForestTables {
+    Call& c;
+    const hpmvs_octree_forest* f;
+    const octree::ForestBlock B;
+    const size_t nb, nl;   // all branch / leaf keys of the forest
+    const unsigned long long *dbk, *dlk;
+    char* w = nullptr;
+    std::vector<char> hdr;
+
+    ForestTables(Call& c_, const hpmvs_octree_forest* f_, size_t extra_bytes)
+        : c(c_), f(f_), B(octree::forest_block(f->n_trees, f->branch_first, f->leaf_first, extra_bytes)),
+          nb(f->n_trees ? (size_t)f->branch_first[f->n_trees] : 0), nl(f->n_trees ? (size_t)f->leaf_first[f->n_trees] : 0),
+          dbk((const unsigned long long*)c.in(f->branch_key, nb)), dlk((const unsigned long long*)c.in(f->leaf_key, nl)) {}
+    bool take(size_t tail) {
+        if (!(w = (char*)c.scratch(B.end + tail))) return false;
+        hdr.resize(B.o_keys);
+        octree::forest_block_fill(B, f->n_trees, f->root, f->branch_first, f->leaf_first, (uintptr_t)w, hdr.data());
+        return true;
+    }
+    uint32_t* words() const { return (uint32_t*)(w + B.o_verdict); }
+    const octree::Tree* trees() const { return (const octree::Tree*)(w + B.o_trees); }
+    const int32_t* leaf_first() const { return (const int32_t*)(w + B.o_lf); }
+    int upload(hipStream_t st) const {
+        HIPCHK(hipMemcpyAsync(w, hdr.data(), B.o_keys, hipMemcpyHostToDevice, st));   // (pageable: consumed before it returns)
+        HIPCHK(hipMemsetAsync(w + B.o_keys, 0, 8 * B.slots, st));
+        return HPMVS_OK;
+    }
+    int launch(hipStream_t st) const {
+        launch_forest_build(f->n_trees, (const int32_t*)(w + B.o_bf), leaf_first(), dbk, dlk, (int)(nb + nl), trees(), words(), st);
+        HIPCHK(hipGetLastError());
+        return HPMVS_OK;
+    }
+    int build(hipStream_t st) const { const int rc = upload(st); return rc ? rc : launch(st); }   // (in two steps where the caller has fills between them)
+    int verdict(const std::string& who, hipStream_t st, uint32_t (&h)[kForestWords]) const {
+        HIPCHK(hipMemcpyAsync(h, words(), sizeof(h), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return h[kForestTable] != octree::kForestGood ? forest_table_fail(who, h[kForestTable]) : HPMVS_OK;
+    }
+};
 // The same level for ALL subtrees of a partition (kernel_extend_forest.hip): one table buffer in which every tree
 // owns a slot range, one device array of {root, table}, and ONE expand_init / refinement / expand_gate for the candidates of all
 // trees.  What the host knows (offsets, roots, which trees have the level) travels in one header block behind the verdict words;
@@ -2247,62 +2331,29 @@ int hpmvs_extend_forest_batch(const hpmvs_scene* s, const hpmvs_options* o, cons
     if (rc) return rc;
     if ((rc = check_batch_shape(s, o, out))) return rc;
     if (!f) return fail(HPMVS_ERR_ARG, who + ": null forest");
-    const int N = expand_fanout(HPMVS_EXPAND_EXTEND);
-    if (out->n != parents->n * N) return fail(HPMVS_ERR_ARG, who + ": out->n must be 6 * parents->n");
-    if (out->max_images != parents->max_images) return fail(HPMVS_ERR_ARG, who + ": max_images mismatch");
-    if (parents->n > 0 && (!out->center || !out->normal || !out->scale || !out->n_images || !out->images || !out->ok))
-        return fail(HPMVS_ERR_ARG, who + ": missing array");
+    if ((rc = extend_out_check(who, parents, out))) return rc;
     if (parents->n > 0 && !parent_tree) return fail(HPMVS_ERR_ARG, who + ": parent_tree missing");
     if (!std::isfinite(width)) return fail(HPMVS_ERR_ARG, who + ": width is not finite");
+    if ((rc = forest_host_check(who, f, parents->n > 0 ? "parent_tree[0] is outside [0, n_trees): the forest has no tree" : nullptr))) return rc;
     const int T = f->n_trees;
-    if (T < 0) return fail(HPMVS_ERR_ARG, who + ": negative count");
-    if (T == 0 && parents->n > 0) return fail(HPMVS_ERR_ARG, who + ": parent_tree[0] is outside [0, n_trees): the forest has no tree");
-    if (T > 0 && (!f->root || !f->branch_first || !f->leaf_first)) return fail(HPMVS_ERR_ARG, who + ": root / branch_first / leaf_first missing");
     if (T == 0) return HPMVS_OK;
-    if ((rc = forest_host_check(who, f))) return rc;
-    const size_t nb = (size_t)f->branch_first[T], nl = (size_t)f->leaf_first[T], n = (size_t)parents->n, nc = n * N;
-    // the header block as the device reads it: [verdict] [Tree x T] [branch_first] [leaf_first] [has_level]; then the table
-    // buffer and cell_width of expand_init / expand_gate
-    std::vector<uint64_t> slot_first((size_t)T + 1);
-    octree::forest_slots(T, f->branch_first, f->leaf_first, slot_first.data());
-    const size_t slots = (size_t)slot_first[T];
-    const size_t o_trees = reg_align(sizeof(uint32_t) * kForestWords), o_bf = reg_align(o_trees + sizeof(octree::Tree) * T),
-                 o_lf = reg_align(o_bf + 4 * ((size_t)T + 1)), o_lvl = reg_align(o_lf + 4 * ((size_t)T + 1)), o_keys = reg_align(o_lvl + T),
-                 o_vals = reg_align(o_keys + 8 * slots), o_cw = reg_align(o_vals + 4 * slots), bytes = o_cw + sizeof(float) * n;
+    const size_t n = (size_t)parents->n, nc = (size_t)out->n;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     Call ck(s, on_device, st);
-    const unsigned long long* dbk = (const unsigned long long*)ck.in(f->branch_key, nb);
-    const unsigned long long* dlk = (const unsigned long long*)ck.in(f->leaf_key, nl);
+    // the block's extra header bytes are has_level, one per tree; behind the block cell_width of expand_init / expand_gate
+    ForestTables F(ck, f, (size_t)T);
     const int32_t* dpt = ck.in(parent_tree, n);
-    char* w = (char*)ck.scratch(bytes);
-    if (!w) return ck.error();
-    std::vector<char> hdr(o_keys, 0);
-    for (int v = 0; v < kForestWords; v++) ((uint32_t*)hdr.data())[v] = octree::kForestGood;
-    octree::Tree* ht = (octree::Tree*)(hdr.data() + o_trees);
-    for (int k = 0; k < T; k++) {
-        const float* r = f->root + 4 * (size_t)k;
-        ht[k].root = octree::Cell{{r[0], r[1], r[2]}, r[3]};
-        ht[k].t = octree::Table{(const uint64_t*)(w + o_keys) + slot_first[k], (const int32_t*)(w + o_vals) + slot_first[k],
-                                (uint32_t)(slot_first[k + 1] - slot_first[k])};
-        hdr[o_lvl + k] = octree::level_depth(r[3], width) >= 0 ? 1 : 0;
-    }
-    memcpy(hdr.data() + o_bf, f->branch_first, 4 * ((size_t)T + 1));
-    memcpy(hdr.data() + o_lf, f->leaf_first, 4 * ((size_t)T + 1));
-    uint32_t* verdict = (uint32_t*)w;
-    const octree::Tree* dtrees = (const octree::Tree*)(w + o_trees);
-    float* dcw = (float*)(w + o_cw);
+    if (!F.take(sizeof(float) * n)) return ck.error();
+    for (int k = 0; k < T; k++) F.hdr[F.B.o_extra + k] = octree::level_depth(f->root[4 * (size_t)k + 3], width) >= 0 ? 1 : 0;
+    const octree::Tree* dtrees = F.trees();
+    float* dcw = (float*)(F.w + F.B.end);
     if ((rc = ck.begin(st))) return rc;
-    HIPCHK(hipMemcpyAsync(w, hdr.data(), o_keys, hipMemcpyHostToDevice, st));   // (pageable: consumed before it returns)
-    HIPCHK(hipMemsetAsync(w + o_keys, 0, 8 * slots, st));
-    launch_forest_build(T, (const int32_t*)(w + o_bf), (const int32_t*)(w + o_lf), dbk, dlk, (int)(nb + nl), dtrees, verdict, st);
-    HIPCHK(hipGetLastError());
-    launch_forest_parents(T, (const uint8_t*)(w + o_lvl), (int)n, dpt, verdict, st);
+    if ((rc = F.build(st))) return rc;
+    launch_forest_parents(T, (const uint8_t*)(F.w + F.B.o_extra), (int)n, dpt, F.words(), st);
     HIPCHK(hipGetLastError());
     uint32_t h[kForestWords];
-    HIPCHK(hipMemcpyAsync(h, verdict, sizeof(h), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (h[kForestTable] != octree::kForestGood) return forest_table_fail(who, h[kForestTable]);
+    if ((rc = F.verdict(who, st, h))) return rc;
     if (h[kForestParent] != octree::kForestGood)
         return fail(HPMVS_ERR_ARG, who + ": parent_tree[" + std::to_string(h[kForestParent]) + "] is outside [0, n_trees)");
     if (h[kForestLevel] != octree::kForestGood)
@@ -2310,38 +2361,18 @@ int hpmvs_extend_forest_batch(const hpmvs_scene* s, const hpmvs_options* o, cons
     if (n == 0) return ck.finish();
     Call c(s, on_device, st);
     const DevBatch P = c.batch(parents, Call::kRead), D = c.batch(out, Call::kCreate);
-    ExtendTreeOut K;
-    memset(&K, 0, sizeof(K));
-    if (keys) {   // (the two kernels write every entry of what they are given: no zero fill)
-        K.skip = c.arr(keys->skip, nc, Call::kCopyBack);
-        K.pre_inside = c.arr(keys->pre_inside, nc, Call::kCopyBack);
-        K.pre_key = (unsigned long long*)c.arr(keys->pre_key, nc, Call::kCopyBack);
-        K.border = c.arr(keys->border, nc, Call::kCopyBack);
-        K.post_key = (unsigned long long*)c.arr(keys->post_key, nc, Call::kCopyBack);
-    }
+    const ExtendTreeOut K = extend_keys(c, keys, nc);
     if ((rc = c.begin(st))) return rc;
-    const DevOptions d = make_dev_options(o);
-    uint32_t wbits;
-    memcpy(&wbits, &width, 4);
-    {
-        std::lock_guard<std::recursive_mutex> lk(s->mu);
-        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)dcw, (int)wbits, n, st));
-        launch_expand_init(dev_scene(s), HPMVS_EXPAND_EXTEND, parents->n, P, nullptr, dcw, nullptr, D, st);
-        HIPCHK(hipGetLastError());
-        launch_extend_forest_pre(dtrees, dpt, (int)nc, width, D, K, st);
-        HIPCHK(hipGetLastError());
-        if ((rc = enqueue_refinement(s, d, D, st))) return rc;
-        launch_expand_gate(HPMVS_EXPAND_EXTEND, parents->n, P, nullptr, dcw, D, st);
-        HIPCHK(hipGetLastError());
-        launch_extend_forest_post(dtrees, dpt, (int)nc, width, D, K, st);
-        HIPCHK(hipGetLastError());
-    }
+    rc = extend_enqueue(s, o, parents, P, D, width, dcw, st,
+                        [&] { launch_extend_forest_pre(dtrees, dpt, (int)nc, width, D, K, st); },
+                        [&] { launch_extend_forest_post(dtrees, dpt, (int)nc, width, D, K, st); });
+    if (rc) return rc;
     if ((rc = c.finish())) return rc;
     return ck.finish();   // (waits in both forms: the tables are freed when this call returns)
 }
 // One regularize / settle sweep of processCell over ALL subtrees of a partition (kernel_process_forest.hip).  Two
-// Calls as above: the inputs and the call's own block first -- [verdict] [Tree x T] [branch_first] [leaf_first], the tables, the
-// leaves' owner words, the cells' derived arrays -- so that ONE read-back carries the forest's verdict and the cells' before an
+// Calls as above: the inputs and the call's own block first -- the forest's (ForestTables), then the leaves' owner words and the
+// cells' derived arrays -- so that ONE read-back carries the forest's verdict and the cells' before an
 // output is declared.  Behind it: level_support, ONE expand_init / refinement / expand_gate over all rows (the rows of a cell that
 // builds nothing are skipped, as hpmvs_expand_batch skips them), the decisions, regularize against them, and the sweep's
 // setDepths calls gathered on the device into ONE ordered replay.  Two more words come back mid-call, as in
@@ -2365,27 +2396,19 @@ int hpmvs_process_forest_batch(hpmvs_scene* s, const hpmvs_options* o, const hpm
     if (n > 0 && (!out->center || !out->normal || !out->scale || !out->n_images || !out->images || !out->ok))
         return fail(HPMVS_ERR_ARG, who + ": missing array");
     if (n > 0 && (!cell_tree || !cell_key || !flatness || !final_level)) return fail(HPMVS_ERR_ARG, who + ": cell_tree / cell_key / flatness / final_level missing");
+    if ((rc = forest_host_check(who, f, n > 0 ? "cell 0: cell_tree is outside [0, n_trees): the forest has no tree" : nullptr))) return rc;
     const int T = f->n_trees;
-    if (T < 0) return fail(HPMVS_ERR_ARG, who + ": negative count");
-    if (T == 0 && n > 0) return fail(HPMVS_ERR_ARG, who + ": cell 0: cell_tree is outside [0, n_trees): the forest has no tree");
-    if (T > 0 && (!f->root || !f->branch_first || !f->leaf_first)) return fail(HPMVS_ERR_ARG, who + ": root / branch_first / leaf_first missing");
     if (T == 0) return HPMVS_OK;
-    if ((rc = forest_host_check(who, f))) return rc;
-    const size_t nb = (size_t)f->branch_first[T], nl = (size_t)f->leaf_first[T];
+    const size_t nl = (size_t)f->leaf_first[T];
     if (nl > 0 && n > 0 && !leaf_patch_center) return fail(HPMVS_ERR_ARG, who + ": leaf_patch_center missing");
-    std::vector<uint64_t> slot_first((size_t)T + 1);
-    octree::forest_slots(T, f->branch_first, f->leaf_first, slot_first.data());
-    const size_t slots = (size_t)slot_first[T];
-    const size_t o_trees = reg_align(sizeof(uint32_t) * kForestWords), o_bf = reg_align(o_trees + sizeof(octree::Tree) * T),
-                 o_lf = reg_align(o_bf + 4 * ((size_t)T + 1)), o_keys = reg_align(o_lf + 4 * ((size_t)T + 1)),
-                 o_vals = reg_align(o_keys + 8 * slots), o_own = reg_align(o_vals + 4 * slots), o_gl = reg_align(o_own + 4 * nl),
-                 o_cc = reg_align(o_gl + 4 * n), o_cw = reg_align(o_cc + 12 * n), o_skip = reg_align(o_cw + 4 * n),
-                 o_cnt = reg_align(o_skip + 4 * n), o_first = reg_align(o_cnt + 4 * (n + 1)), bytes = reg_align(o_first + 4 * (n + 1));
+    // behind the forest's block: the leaves' owner words and the cells' derived arrays
+    const size_t o_own = 0, o_gl = reg_align(o_own + 4 * nl), o_cc = reg_align(o_gl + 4 * n), o_cw = reg_align(o_cc + 12 * n),
+                 o_skip = reg_align(o_cw + 4 * n), o_cnt = reg_align(o_skip + 4 * n), o_first = reg_align(o_cnt + 4 * (n + 1)),
+                 tail = reg_align(o_first + 4 * (n + 1));
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     Call ck(s, on_device, st);
-    const unsigned long long* dbk = (const unsigned long long*)ck.in(f->branch_key, nb);
-    const unsigned long long* dlk = (const unsigned long long*)ck.in(f->leaf_key, nl);
+    ForestTables F(ck, f, 0);
     const float* dlpc = ck.in(leaf_patch_center, n > 0 ? 3 * nl : 0);
     const DevBatch P = ck.batch(cells, Call::kRead);
     ProcessCells C;
@@ -2396,43 +2419,27 @@ int hpmvs_process_forest_batch(hpmvs_scene* s, const hpmvs_options* o, const hpm
     float* dfl = ck.arr(flatness, n, Call::kCopyIn | Call::kCopyBack);
     C.flatness = dfl; C.n_images = P.n_images; C.images = P.images;
     const uint8_t* dfinal = ck.in(final_level, n);
-    char* w = (char*)ck.scratch(bytes);
-    if (!w) return ck.error();
+    if (!F.take(tail)) return ck.error();
     size_t scan_bytes = 0;
     if (process_scan(nullptr, &scan_bytes, nullptr, nullptr, (int)n + 1, st) != 0) return fail(HPMVS_ERR_HIP, who + ": rocPRIM size query failed");
     void* scan_temp = ck.scratch(scan_bytes ? scan_bytes : 1);
     if (!scan_temp) return ck.error();
-    std::vector<char> hdr(o_keys, 0);
-    for (int v = 0; v < kForestWords; v++) ((uint32_t*)hdr.data())[v] = octree::kForestGood;
-    octree::Tree* ht = (octree::Tree*)(hdr.data() + o_trees);
-    for (int k = 0; k < T; k++) {
-        const float* r = f->root + 4 * (size_t)k;
-        ht[k].root = octree::Cell{{r[0], r[1], r[2]}, r[3]};
-        ht[k].t = octree::Table{(const uint64_t*)(w + o_keys) + slot_first[k], (const int32_t*)(w + o_vals) + slot_first[k],
-                                (uint32_t)(slot_first[k + 1] - slot_first[k])};
-    }
-    memcpy(hdr.data() + o_bf, f->branch_first, 4 * ((size_t)T + 1));
-    memcpy(hdr.data() + o_lf, f->leaf_first, 4 * ((size_t)T + 1));
-    uint32_t* verdict = (uint32_t*)w;
-    const octree::Tree* dtrees = (const octree::Tree*)(w + o_trees);
-    const int32_t* dlf = (const int32_t*)(w + o_lf);
+    const octree::Tree* dtrees = F.trees();
+    const int32_t* dlf = F.leaf_first();
+    char* w = F.w + F.B.end;
     C.owner = (int32_t*)(w + o_own); C.gleaf = (int32_t*)(w + o_gl);
     C.cell_center = (float*)(w + o_cc); C.cell_width = (float*)(w + o_cw);
     uint8_t* dskip = (uint8_t*)(w + o_skip);
     int32_t* op_count = (int32_t*)(w + o_cnt);
     int32_t* op_first = (int32_t*)(w + o_first);
     if ((rc = ck.begin(st))) return rc;
-    HIPCHK(hipMemcpyAsync(w, hdr.data(), o_keys, hipMemcpyHostToDevice, st));   // (pageable: consumed before it returns)
-    HIPCHK(hipMemsetAsync(w + o_keys, 0, 8 * slots, st));
+    if ((rc = F.upload(st))) return rc;
     if (nl) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)C.owner, octree::kNoOwner, nl, st));
-    launch_forest_build(T, (const int32_t*)(w + o_bf), dlf, dbk, dlk, (int)(nb + nl), dtrees, verdict, st);
-    HIPCHK(hipGetLastError());
-    launch_process_cells(T, dtrees, dlf, s->n_views, C, verdict, st);
+    if ((rc = F.launch(st))) return rc;
+    launch_process_cells(T, dtrees, dlf, s->n_views, C, F.words(), st);
     HIPCHK(hipGetLastError());
     uint32_t h[kForestWords];
-    HIPCHK(hipMemcpyAsync(h, verdict, sizeof(h), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (h[kForestTable] != octree::kForestGood) return forest_table_fail(who, h[kForestTable]);
+    if ((rc = F.verdict(who, st, h))) return rc;
     if (h[kForestParent] != octree::kForestGood) {
         const std::string cell = who + ": cell " + std::to_string(h[kForestParent] >> 3);
         switch (h[kForestParent] & 7u) {
@@ -2522,8 +2529,8 @@ int hpmvs_process_forest_batch(hpmvs_scene* s, const hpmvs_options* o, const hpm
 // A round's border queue over ALL subtrees (kernel_border_forest.hip): distributeBorderCell, every tree's
 // processBorderCellQueue and the accepted patches' setDepths(p, false) as ONE call.  One Call: no array is filled by begin() (the
 // kernels write every entry of every output), so declaring the outputs ahead of the verdict writes nothing; the forest's verdict
-// comes back in ONE read-back before the first kernel that touches an output or a map is enqueued.  The block is the call's own:
-// [verdict] [Tree x T] [branch_first] [leaf_first], the tables, then 56 bytes per patch and rocPRIM's temporary storage.
+// comes back in ONE read-back before the first kernel that touches an output or a map is enqueued.  The scratch is the call's own:
+// the forest's block (ForestTables), then 56 bytes per patch and rocPRIM's temporary storage.
 int hpmvs_border_forest_batch(hpmvs_scene* s, const hpmvs_octree_forest* f, const hpmvs_patch_batch* border, int set_depths,
                               const hpmvs_border_forest_result* res, int on_device, void* stream) {
     const std::string who = "border_forest_batch";
@@ -2534,26 +2541,16 @@ int hpmvs_border_forest_batch(hpmvs_scene* s, const hpmvs_octree_forest* f, cons
     if (border->n > 0 && (!border->center || !border->scale)) return fail(HPMVS_ERR_ARG, who + ": batch input arrays missing (center / scale)");
     if (border->n > 0 && set_depths && (!border->normal || !border->n_images || !border->images))
         return fail(HPMVS_ERR_ARG, who + ": batch input arrays missing (set_depths reads normal / n_images / images)");
-    const int T = f->n_trees;
-    if (T < 0) return fail(HPMVS_ERR_ARG, who + ": negative count");
-    if (T > 0 && (!f->root || !f->branch_first || !f->leaf_first)) return fail(HPMVS_ERR_ARG, who + ": root / branch_first / leaf_first missing");
     int rc;
-    if (T > 0 && (rc = forest_host_check(who, f))) return rc;
+    if ((rc = forest_host_check(who, f, nullptr))) return rc;   // (no tree: every patch is routed nowhere)
     if (set_depths && (!s->depth_pool || !s->ddepth)) return fail(HPMVS_ERR_STATE, who + ": call hpmvs_scene_depth_reset first");
+    const int T = f->n_trees;
     const size_t n = (size_t)border->n, M = (size_t)border->max_images;
     if (T == 0 && n == 0) return HPMVS_OK;
-    const size_t nb = T ? (size_t)f->branch_first[T] : 0, nl = T ? (size_t)f->leaf_first[T] : 0;
-    std::vector<uint64_t> slot_first((size_t)T + 1, 0);
-    if (T) octree::forest_slots(T, f->branch_first, f->leaf_first, slot_first.data());
-    const size_t slots = (size_t)slot_first[T];
-    const size_t o_trees = reg_align(sizeof(uint32_t) * kForestWords), o_bf = reg_align(o_trees + sizeof(octree::Tree) * T),
-                 o_lf = reg_align(o_bf + 4 * ((size_t)T + 1)), o_keys = reg_align(o_lf + 4 * ((size_t)T + 1)),
-                 o_vals = reg_align(o_keys + 8 * slots), bytes = reg_align(o_vals + 4 * slots);
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     Call c(s, on_device, st);
-    const unsigned long long* dbk = (const unsigned long long*)c.in(f->branch_key, nb);
-    const unsigned long long* dlk = (const unsigned long long*)c.in(f->leaf_key, nl);
+    ForestTables F(c, f, 0);
     DevBatch D;
     memset(&D, 0, sizeof(D));
     D.n = border->n; D.max_images = border->max_images;
@@ -2575,8 +2572,7 @@ int hpmvs_border_forest_batch(hpmvs_scene* s, const hpmvs_octree_forest* f, cons
         out.accepted = (uint8_t*)c.scratch(n);
         if (!out.accepted) return c.error();
     }
-    char* w = (char*)c.scratch(bytes);
-    if (!w) return c.error();
+    if (!F.take(0)) return c.error();
     BorderForestScratch S;
     memset(&S, 0, sizeof(S));
     if (n > 0) {
@@ -2591,34 +2587,13 @@ int hpmvs_border_forest_batch(hpmvs_scene* s, const hpmvs_octree_forest* f, cons
         S.acc_owner = (int32_t*)(S.tree_c + n);
         S.temp = blk + o_temp;
     }
-    std::vector<char> hdr(o_keys, 0);
-    for (int v = 0; v < kForestWords; v++) ((uint32_t*)hdr.data())[v] = octree::kForestGood;
-    octree::Tree* ht = (octree::Tree*)(hdr.data() + o_trees);
-    for (int k = 0; k < T; k++) {
-        const float* r = f->root + 4 * (size_t)k;
-        ht[k].root = octree::Cell{{r[0], r[1], r[2]}, r[3]};
-        ht[k].t = octree::Table{(const uint64_t*)(w + o_keys) + slot_first[k], (const int32_t*)(w + o_vals) + slot_first[k],
-                                (uint32_t)(slot_first[k + 1] - slot_first[k])};
-    }
-    if (T) {
-        memcpy(hdr.data() + o_bf, f->branch_first, 4 * ((size_t)T + 1));
-        memcpy(hdr.data() + o_lf, f->leaf_first, 4 * ((size_t)T + 1));
-    }
-    uint32_t* verdict = (uint32_t*)w;
-    const octree::Tree* dtrees = (const octree::Tree*)(w + o_trees);
     if ((rc = c.begin(st))) return rc;
-    if (T) {
-        HIPCHK(hipMemcpyAsync(w, hdr.data(), o_keys, hipMemcpyHostToDevice, st));   // (pageable: consumed before it returns)
-        HIPCHK(hipMemsetAsync(w + o_keys, 0, 8 * slots, st));
-        launch_forest_build(T, (const int32_t*)(w + o_bf), (const int32_t*)(w + o_lf), dbk, dlk, (int)(nb + nl), dtrees, verdict, st);
-        HIPCHK(hipGetLastError());
+    if (T) {   // (without a tree the block is never read: nothing to upload or build)
         uint32_t h[kForestWords];
-        HIPCHK(hipMemcpyAsync(h, verdict, sizeof(h), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (h[kForestTable] != octree::kForestGood) return forest_table_fail(who, h[kForestTable]);
+        if ((rc = F.build(st)) || (rc = F.verdict(who, st, h))) return rc;
     }
     if (n > 0) {
-        if (launch_border_forest(T, dtrees, (int)n, D.center, D.scale, S, out, st)) return fail(HPMVS_ERR_HIP, who + ": rocPRIM sort failed");
+        if (launch_border_forest(T, F.trees(), (int)n, D.center, D.scale, S, out, st)) return fail(HPMVS_ERR_HIP, who + ": rocPRIM sort failed");
         HIPCHK(hipGetLastError());
         if (set_depths) {
             D.ok = out.accepted;
@@ -2664,17 +2639,9 @@ int hpmvs_octree_insert_batch(const hpmvs_scene* s, const hpmvs_octree_index* t,
         S.temp = blk + o_temp;
     }
     if ((rc = c.begin(st))) return rc;
-    // the scene lock is held from here on: the workspace is this call's until its last kernel has been enqueued
-    std::lock_guard<std::recursive_mutex> lk(s->mu);
-    if ((rc = service_quiesce(s))) return rc;
-    int32_t* q;
-    int slot;
-    if ((rc = acquire_workspace(s, &q, &slot, st))) return rc;
-    struct Release { const hpmvs_scene* s; int slot; hipStream_t st; ~Release() { hipEventRecord(s->slot_done[slot], st); s->slot_used[slot] = true; } } rel{s, slot, st};
-    char* w = (char*)q;
-    if ((rc = octree_table_build(t, dbk, dlk, L, w, st, who))) return rc;
-    const float root[4] = {t->root_center[0], t->root_center[1], t->root_center[2], t->root_width};
-    if (launch_octree_insert(root, (unsigned long long*)(w + L.o_keys), (int32_t*)(w + L.o_vals), (uint32_t)L.slots, n, dpts, daw, S, out, st))
+    WorkspaceTable tt(s, t, dbk, dlk, L, st, who);
+    if (tt.rc) return tt.rc;
+    if (launch_octree_insert(tt.root, tt.keys, tt.vals, tt.slots, n, dpts, daw, S, out, st))
         return fail(HPMVS_ERR_HIP, "octree_insert_batch: rocPRIM sort failed");
     HIPCHK(hipGetLastError());
     return c.finish();   // (waits in both forms: the scratch is freed when this call returns)
@@ -2729,19 +2696,11 @@ int hpmvs_octree_partition(const hpmvs_scene* s, const hpmvs_octree_index* t, in
     S.val_a = (int32_t*)(S.key_b + nl); S.val_b = S.val_a + nl;
     S.temp = blk + o_temp;
     if ((rc = c.begin(st))) return rc;
-    // the scene lock is held from here on: the workspace is this call's until its last kernel has been enqueued
-    std::lock_guard<std::recursive_mutex> lk(s->mu);
-    if ((rc = service_quiesce(s))) return rc;
-    int32_t* q;
-    int slot;
-    if ((rc = acquire_workspace(s, &q, &slot, st))) return rc;
-    struct Release { const hpmvs_scene* s; int slot; hipStream_t st; ~Release() { hipEventRecord(s->slot_done[slot], st); s->slot_used[slot] = true; } } rel{s, slot, st};
-    char* w = (char*)q;
-    if ((rc = octree_table_build(t, dbk, dlk, L, w, st, who))) return rc;
+    WorkspaceTable tt(s, t, dbk, dlk, L, st, who);
+    if (tt.rc) return tt.rc;
     HIPCHK(hipMemsetAsync(blk, 0, o_ka, st));
-    const float root[4] = {t->root_center[0], t->root_center[1], t->root_center[2], t->root_width};
-    if (launch_octree_partition(root, (unsigned long long*)(w + L.o_keys), (int32_t*)(w + L.o_vals), (uint32_t)L.slots, dbk, (int)nb, dlk, (int)nl,
-                                min_trees, min_split_leaves, cap, S, roots, dorder, out, st))
+    if (launch_octree_partition(tt.root, tt.keys, tt.vals, tt.slots, dbk, (int)nb, dlk, (int)nl, min_trees, min_split_leaves, cap, S, roots, dorder,
+                                out, st))
         return fail(HPMVS_ERR_HIP, "octree_partition: rocPRIM sort failed");
     HIPCHK(hipGetLastError());
     int32_t h[kPartitionInts];

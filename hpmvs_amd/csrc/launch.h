@@ -7,6 +7,7 @@
 #include "conflicts.hpp"
 #include "dev_types.h"
 #include "jpeg.hpp"
+#include "octree.hpp"
 #include "seed_tree.hpp"
 
 namespace hpmvs {
@@ -160,8 +161,7 @@ void launch_extend_tree_post(const float* root, const unsigned long long* keys, 
 // by the caller and folded with min -- the table's finding (octree::forest_finding), the first parent whose parent_tree names no
 // tree, the lowest tree with a parent and has_level == 0.  The candidate kernels read parent_tree[i / 6] unchecked: launch them
 // only behind a good verdict.
-namespace octree { struct Tree; }
-constexpr int kForestTable = 0, kForestParent = 1, kForestLevel = 2, kForestWords = 4;
+using octree::kForestTable; using octree::kForestParent; using octree::kForestLevel; using octree::kForestWords;   // (octree.hpp: the forest's block)
 void launch_forest_build(int n_trees, const int32_t* branch_first, const int32_t* leaf_first, const unsigned long long* branch_key,
                          const unsigned long long* leaf_key, int n_keys, const octree::Tree* trees, uint32_t* verdict, hipStream_t st);
 void launch_forest_parents(int n_trees, const uint8_t* has_level, int n, const int32_t* parent_tree, uint32_t* verdict, hipStream_t st);

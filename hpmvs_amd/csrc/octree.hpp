@@ -19,6 +19,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <unordered_map>
 #include <vector>
 
@@ -466,6 +467,53 @@ HPMVS_OT_FN uint32_t forest_check_key(const Tree* trees, const ForestKey& k) {
     if (key_form(k.key, k.index == kBranch)) return kForestGood;   // (reported by the build; its parent prefix means nothing)
     const int bad = key_parentage(trees[k.tree].t, k.key);
     return bad ? forest_finding(k.tree, bad) : kForestGood;
+}
+// The forest's device block, the same for every entry point that takes a forest:
+//   [verdict words] [Tree x n_trees] [branch_first] [leaf_first] [extra] | [keys] [vals] | end
+// every region at a multiple of 256 bytes.  Up to o_keys it is the header, which the host fills and ONE upload carries; `extra`
+// are header bytes of the caller's own (the extend level's has_level); behind `end` the caller appends what is its own.  The
+// verdict words are folded with min, each set to kForestGood before: kForestTable is the tables' finding, the others are the
+// entry point's.  n_trees == 0 gives a block without tables and reads neither offset array.
+constexpr int kForestTable = 0, kForestParent = 1, kForestLevel = 2, kForestWords = 4;
+struct ForestBlock {
+    size_t o_verdict, o_trees, o_bf, o_lf, o_extra, o_keys, o_vals, end;
+    size_t slots;                       // of the whole buffer: slot_first[n_trees]
+    std::vector<uint64_t> slot_first;   // [n_trees + 1]
+};
+inline ForestBlock forest_block(int32_t n_trees, const int32_t* branch_first, const int32_t* leaf_first, size_t extra_bytes) {
+    const auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t T = (size_t)n_trees;
+    ForestBlock b;
+    b.slot_first.assign(T + 1, 0);
+    if (n_trees > 0) forest_slots(n_trees, branch_first, leaf_first, b.slot_first.data());
+    b.slots = (size_t)b.slot_first[T];
+    b.o_verdict = 0;
+    b.o_trees = align(sizeof(uint32_t) * kForestWords);
+    b.o_bf = align(b.o_trees + sizeof(Tree) * T);
+    b.o_lf = align(b.o_bf + 4 * (T + 1));
+    b.o_extra = align(b.o_lf + 4 * (T + 1));
+    b.o_keys = align(b.o_extra + extra_bytes);
+    b.o_vals = align(b.o_keys + 8 * b.slots);
+    b.end = align(b.o_vals + 4 * b.slots);
+    return b;
+}
+// the header's host image, hdr[0, o_keys), for a block that lies at the device address `base`; roots: [n_trees][4].  The extra
+// bytes are zeroed.
+inline void forest_block_fill(const ForestBlock& b, int32_t n_trees, const float* roots, const int32_t* branch_first,
+                              const int32_t* leaf_first, uintptr_t base, char* hdr) {
+    std::memset(hdr, 0, b.o_keys);
+    for (int v = 0; v < kForestWords; v++) ((uint32_t*)(hdr + b.o_verdict))[v] = kForestGood;
+    Tree* trees = (Tree*)(hdr + b.o_trees);
+    for (int32_t k = 0; k < n_trees; k++) {
+        const float* r = roots + 4 * (size_t)k;
+        trees[k].root = Cell{{r[0], r[1], r[2]}, r[3]};
+        trees[k].t = Table{(const uint64_t*)(base + b.o_keys + 8 * b.slot_first[k]), (const int32_t*)(base + b.o_vals + 4 * b.slot_first[k]),
+                           (uint32_t)(b.slot_first[k + 1] - b.slot_first[k])};
+    }
+    if (n_trees > 0) {
+        std::memcpy(hdr + b.o_bf, branch_first, 4 * ((size_t)n_trees + 1));
+        std::memcpy(hdr + b.o_lf, leaf_first, 4 * ((size_t)n_trees + 1));
+    }
 }
 // the two look-ups of a candidate through its tree's id
 HPMVS_OT_FN ExtendPre extend_forest_pre(const Tree* trees, int32_t tree, const float* p, float width, float add_width) {
