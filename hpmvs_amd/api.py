@@ -104,7 +104,11 @@ EXPORTS = [
     "hpmvs_level_conflicts_batch", "hpmvs_conflicts_from_footprints",
     "hpmvs_scene_center", "hpmvs_init_patches_sphere_batch",
     "hpmvs_jpeg_info", "hpmvs_jpeg_decode", "hpmvs_scene_set_view_jpeg", "hpmvs_jpeg_decode_timed",
+    "hpmvs_jpeg_decode_ex", "hpmvs_scene_set_view_jpeg_ex", "hpmvs_jpeg_coefficients", "hpmvs_jpeg_entropy_timed",
+    "hpmvs_jpeg_last_decode",
 ]
+JPEG_ENTROPY = {"auto": 0, "host": 1, "device": 2}   # HPMVS_JPEG_ENTROPY_AUTO / _HOST / _DEVICE
+
 
 _lib = None
 
@@ -140,6 +144,13 @@ def lib():
     L.hpmvs_jpeg_decode.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int]
     L.hpmvs_jpeg_decode_timed.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_float)]
     L.hpmvs_scene_set_view_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(Camera), C.c_float, C.c_float]
+    L.hpmvs_jpeg_decode_ex.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    L.hpmvs_scene_set_view_jpeg_ex.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(Camera), C.c_float, C.c_float,
+                                               C.c_int, C.POINTER(C.c_int)]
+    L.hpmvs_jpeg_coefficients.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                          C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.hpmvs_jpeg_last_decode.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.hpmvs_jpeg_entropy_timed.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_float)]
     L.hpmvs_optimize_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(PatchBatch), C.c_int, C.c_void_p]
     L.hpmvs_init_patches_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.POINTER(PatchBatch), C.c_int, C.c_void_p]
@@ -285,26 +296,55 @@ def jpeg_info(data):
     return tuple(x.value for x in v)
 
 
-def jpeg_decode(data, device: int = 0, on_device: bool = False):
-    """Baseline JPEG file (bytes-like) -> uint8 [H, W, 3] with libjpeg's default pixels: entropy decoding on the host, everything
-    behind it on the GPU.  A numpy array, or with on_device a torch tensor on the device (the pixels never visit the host)."""
+def _jpeg_entropy(name):
+    if name not in JPEG_ENTROPY:
+        raise HpmvsError(f"entropy must be one of {sorted(JPEG_ENTROPY)}, not {name!r}")
+    return JPEG_ENTROPY[name]
+
+
+def jpeg_decode(data, device: int = 0, on_device: bool = False, entropy: str = "auto"):
+    """Baseline JPEG file (bytes-like) -> uint8 [H, W, 3] with libjpeg's default pixels, everything behind the entropy decode on
+    the GPU.  A numpy array, or with on_device a torch tensor on the device (the pixels never visit the host).
+    entropy: where the Huffman scan is decoded -- "auto" (the library's choice, or what HPMVS_JPEG_ENTROPY names), "host", or
+    "device" (the GPU itself: a scan it does not take raises HPMVS_ERR_STATE = -3 instead of falling back).  The pixels do not
+    depend on it."""
     data = bytes(data)
+    mode = _jpeg_entropy(entropy)
     w, h = jpeg_info(data)[:2]
     if on_device:
         out = torch.empty((h, w, 3), dtype=torch.uint8, device=f"cuda:{device}")
-        _chk(lib().hpmvs_jpeg_decode(device, data, len(data), out.data_ptr(), out.numel(), 1))
-        return out
-    out = np.empty((h, w, 3), dtype=np.uint8)
-    _chk(lib().hpmvs_jpeg_decode(device, data, len(data), out.ctypes.data, out.nbytes, 0))
+        ptr, nb = out.data_ptr(), out.numel()
+    else:
+        out = np.empty((h, w, 3), dtype=np.uint8)
+        ptr, nb = out.ctypes.data, out.nbytes
+    if mode == 0:
+        _chk(lib().hpmvs_jpeg_decode(device, data, len(data), ptr, nb, int(on_device)))
+    else:
+        _chk(lib().hpmvs_jpeg_decode_ex(device, data, len(data), ptr, nb, int(on_device), mode, None))
     return out
+
+
+def jpeg_coefficients(data, entropy: str = "auto", subseq_bits: int = 0, device: int = 0):
+    """The dense coefficients behind the entropy decode -> (int16 array: per component [blocks_y][blocks_x][64], one component behind
+    the other; "host" or "device", what decoded the scan; synchronisation rounds of the device decode).  subseq_bits: the device
+    decode's subsequence size, 0 for the shipped one, else a multiple of 32 from 64 up (a test hook)."""
+    data = bytes(data)
+    w, h, comps, hs, vs = jpeg_info(data)
+    mx, my = -(-w // (8 * hs)), -(-h // (8 * vs))
+    out = np.empty(64 * mx * my * (hs * vs + (2 if comps == 3 else 0)), dtype=np.int16)
+    used, rounds = C.c_int(), C.c_int()
+    _chk(lib().hpmvs_jpeg_coefficients(device, data, len(data), _jpeg_entropy(entropy), int(subseq_bits), out.ctypes.data, out.size,
+                                       C.byref(used), C.byref(rounds)))
+    return out, "device" if used.value == 2 else "host", rounds.value
 
 
 class Scene:
     """HBM-resident scene: Scene::addCameras + extractCoVisiblilty state the path reads
     (reference include/hpmvs/Scene.h:69-71)."""
 
-    def __init__(self, synth_scene, device: int = 0):
+    def __init__(self, synth_scene, device: int = 0, jpeg_entropy: str = "auto"):
         L = lib()
+        jpeg_mode = _jpeg_entropy(jpeg_entropy)   # where views given as JPEG bytes have their scans decoded (jpeg_decode)
         self.h = C.c_void_p()
         self.device = device
         self.n_views = synth_scene.n_views
@@ -319,8 +359,12 @@ class Scene:
                 cam = camera_from_nvm(v.f, v.q, v.c, w, h, synth_scene.max_level)
                 self.view_levels.append(int(cam.n_levels))
                 self.cameras.append(cam)
-                _chk(L.hpmvs_scene_set_view_jpeg(self.h, i, data, len(data), C.byref(cam), float(v.f),
-                                                 float(getattr(v, "k1", 0.0))))
+                if jpeg_mode == 0:
+                    _chk(L.hpmvs_scene_set_view_jpeg(self.h, i, data, len(data), C.byref(cam), float(v.f),
+                                                     float(getattr(v, "k1", 0.0))))
+                else:
+                    _chk(L.hpmvs_scene_set_view_jpeg_ex(self.h, i, data, len(data), C.byref(cam), float(v.f),
+                                                        float(getattr(v, "k1", 0.0)), jpeg_mode, None))
                 continue
             cam = camera_from_nvm(v.f, v.q, v.c, v.width, v.height, synth_scene.max_level)
             self.view_levels.append(int(cam.n_levels))

@@ -3,12 +3,13 @@
 // YCbCr conversion), written once for the device kernels (kernel_jpeg.hip), the C ABI (capi.hip) and the host
 // restatement the tests compile with g++ (tests/jpeg_host.cpp).
 //
-// The split: the host parses the markers and decodes the bit-serial entropy data into dense int16 coefficients
-// (second half of this file, plain C++); everything after the coefficients -- dequantisation, the 8x8 integer IDCT,
-// chroma interpolation, colour conversion -- is the arithmetic of the first half, which the kernels run per block and
-// per pixel and the host restatement runs in loops.  All products and sums of the IDCT are formed on uint32_t and
-// converted back, so that coefficients no encoder produces wrap identically on both sides instead of overflowing a
-// signed int on the host.
+// The split: the host parses the markers and either decodes the bit-serial entropy data into dense int16 coefficients
+// itself (decode_scan, plain C++) or hands the scan to the device, which decodes it in parallel subsequences with
+// decode_subseq (last part of this file; kernel_jpeg_entropy.hip); everything after the coefficients --
+// dequantisation, the 8x8 integer IDCT, chroma interpolation, colour conversion -- is the arithmetic of the first half,
+// which the kernels run per block and per pixel and the host restatement runs in loops.  All products and sums of the
+// IDCT are formed on uint32_t and converted back, so that coefficients no encoder produces wrap identically on both
+// sides instead of overflowing a signed int on the host.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -260,13 +261,11 @@ inline int fail(std::string* err, int code, const char* msg) {
     return code;
 }
 
-// Parses the file and decodes its one scan.  keep_coef: fill fr.coef; otherwise the entropy data is walked and checked
-// all the same, without the coefficient buffer (hpmvs_jpeg_info).  -> kOk, kErrArg (malformed, truncated) or
-// kErrUnsupported (a legal file outside what is decoded here), with the reason in *err.
-inline int decode_file(const uint8_t* b, size_t n, Frame& fr, bool keep_coef, std::string* err) {
+// The header parse of decode_file: everything in front of the entropy-coded bytes.  Fills fr (all but coef) and
+// huff[8] ([class * 4 + id]) and gives the scan's first byte.  -> kOk, kErrArg (malformed, truncated) or kErrUnsupported
+// (a legal file outside what is decoded here), with the reason in *err.
+inline int parse_headers(const uint8_t* b, size_t n, Frame& fr, Huff* huff, size_t* scan_start, std::string* err) {
     if (!b || n < 4 || b[0] != 0xFF || b[1] != 0xD8) return fail(err, kErrArg, "not a JPEG file (no SOI)");
-    Huff* huff = new Huff[8];  // [class * 4 + id]
-    struct Del { Huff* p; ~Del() { delete[] p; } } del{huff};
     uint16_t qt[4][64];
     bool qt_set[4] = {false, false, false, false};
     bool have_sof = false, jfif = false, adobe = false;
@@ -400,8 +399,15 @@ inline int decode_file(const uint8_t* b, size_t n, Frame& fr, bool keep_coef, st
     // a block takes two bits at the very least (a DC code and an end-of-block code): a header that promises more blocks
     // than the rest of the file can hold is refused before any buffer is sized by it
     if (fr.n_blocks > (n - i) * 4) return fail(err, kErrArg, "truncated: the entropy data cannot hold the frame's blocks");
+    *scan_start = i;
+    return kOk;
+}
+
+// The scan walk of decode_file over the entropy-coded bytes from scan_start on, with the frame and tables of
+// parse_headers.  keep_coef: fill fr.coef; otherwise the data is walked and checked all the same.
+inline int decode_scan(const uint8_t* b, size_t n, size_t scan_start, Frame& fr, const Huff* huff, bool keep_coef, std::string* err) {
     if (keep_coef) fr.coef.assign(fr.n_blocks * 64, 0);
-    BitReader br{b, i, n};
+    BitReader br{b, scan_start, n};
     int32_t pred[3] = {0, 0, 0};
     size_t mcu = 0;
     int rst = 0;
@@ -450,6 +456,15 @@ inline int decode_file(const uint8_t* b, size_t n, Frame& fr, bool keep_coef, st
     return fail(err, kErrArg, "truncated: no EOI behind the scan");
 }
 
+// Parses the file and decodes its one scan.  keep_coef: fill fr.coef; otherwise the entropy data is walked and checked
+// all the same, without the coefficient buffer (hpmvs_jpeg_info).  -> kOk, kErrArg or kErrUnsupported, reason in *err.
+inline int decode_file(const uint8_t* b, size_t n, Frame& fr, bool keep_coef, std::string* err) {
+    std::vector<Huff> huff(8);
+    size_t scan_start = 0;
+    const int rc = parse_headers(b, n, fr, huff.data(), &scan_start, err);
+    return rc != kOk ? rc : decode_scan(b, n, scan_start, fr, huff.data(), keep_coef, err);
+}
+
 // plane layout of a frame: offsets 256-byte aligned; -> bytes of the buffer
 inline size_t make_planes(const Frame& fr, Planes* P) {
     P->W = fr.W; P->H = fr.H; P->ncomp = fr.ncomp;
@@ -465,6 +480,275 @@ inline size_t make_planes(const Frame& fr, Planes* P) {
         total += ((size_t)fr.c[c].bx * fr.c[c].by * 64 + 255) & ~(size_t)255;
     }
     return total;
+}
+
+// ------------------------------------------------------------------------------------------------ parallel entropy decoding
+// The scan's Huffman data decoded in parallel (kernel_jpeg_entropy.hip; restated in loops by tests/jpeg_entropy_host.cpp):
+// the host removes the byte stuffing and cuts the scan at its restart markers into segments (prescan), every segment is
+// cut into subsequences of S bits, and every subsequence is decoded by decode_subseq from an entry state -- first from a
+// guess, then from its predecessor's exit until no exit changes (Huffman codes resynchronise after a wrong start).  A
+// chain that a check accepts is the sequential decode of decode_scan, symbol for symbol.
+constexpr int kSubseqBits = 512;      // the shipped subsequence size
+constexpr int kSubsPerGroup = 64;     // subsequences that synchronise inside one workgroup (one wavefront)
+// synchronisation rounds before the decode is left to the host: four times what the slowest fixture file needs at the
+// shipped size (185); at another size (the test hook) as many rounds more as it has subsequences more
+constexpr int kSyncRoundCap = 740;
+HPMVS_JPG_FN int sync_round_cap(uint32_t subseq_bits) { return (int)((uint64_t)kSyncRoundCap * kSubseqBits / subseq_bits); }
+constexpr uint32_t kStateErr = 1u << 31;
+
+struct Segment {
+    uint32_t first_byte;  // in the unstuffed bytes
+    uint32_t bits;
+    uint32_t first_mcu, n_mcus;
+    uint32_t first_sub, n_subs;  // filled by plan_subsequences
+};
+
+// where a decoder stands: p bits into the segment, in block blk of the MCU (bk >> 8), at coefficient k (bk & 63; 0: the DC
+// code comes next).  kStateErr in an exit's bk: the decode that gave it met an invalid code or k > 63.
+struct SubState {
+    uint32_t p, bk;
+};
+HPMVS_JPG_FN bool same_state(SubState a, SubState b) { return a.p == b.p && a.bk == b.bk; }
+// the entry a subsequence takes from its predecessor's exit
+HPMVS_JPG_FN SubState handed_on(SubState exit) {
+    exit.bk &= ~kStateErr;
+    return exit;
+}
+
+// what a subsequence adds to its segment: blocks completed and, per component, the sum of its DC differences (mod 2^32)
+struct SubCount {
+    uint32_t nblk, dc[3];
+};
+
+struct ScanInfo {
+    int32_t ncomp, bpm;  // blocks per MCU
+    int32_t mcus_x, n_mcus;
+    int32_t h[3], v[3], bx[3];
+    uint32_t off[3];  // first coefficient of the component
+    uint8_t blk_comp[8], blk_dx[8], blk_dy[8];
+};
+
+// 32 bits of the segment from bit p on; bits past the segment's end read as 0.  d: the segment's first byte, with at least
+// 8 readable bytes behind its last
+HPMVS_JPG_FN uint32_t peek32(const uint8_t* d, uint32_t bits, uint32_t p) {
+    const uint8_t* s = d + (p >> 3);
+    const uint64_t w = (uint64_t)s[0] << 32 | (uint64_t)s[1] << 24 | (uint64_t)s[2] << 16 | (uint64_t)s[3] << 8 | (uint64_t)s[4];
+    const uint32_t v = (uint32_t)(w >> (8 - (p & 7)));
+    const uint32_t avail = bits - p;
+    return avail >= 32 ? v : avail == 0 ? 0u : v & ~(0xffffffffu >> avail);
+}
+
+// the code at the head of v (32 bits, left aligned) -> length << 8 | symbol, 0: no code (huff_decode's two steps)
+HPMVS_JPG_FN uint32_t huff_lookup(const Huff& h, uint32_t v) {
+    const uint32_t e = h.lut[v >> 23];
+    if (e >> 8) return e;
+    for (int l = 10; l <= 16; l++) {
+        const int32_t code = (int32_t)(v >> (32 - l));
+        if (h.maxcode[l] >= 0 && code >= h.mincode[l] && code <= h.maxcode[l])
+            return (uint32_t)l << 8 | h.vals[h.valptr[l] + code - h.mincode[l]];
+    }
+    return 0;
+}
+
+// receive_extend on the n bits (1 <= n <= 15) at the head of v
+HPMVS_JPG_FN int32_t extend_bits(uint32_t v, int n) {
+    const int32_t x = (int32_t)(v >> (32 - n));
+    return x < (1 << (n - 1)) ? x - (1 << n) + 1 : x;
+}
+
+// Decodes the symbols of one segment that start in front of bit `end` (the subsequence's last bit + 1, at most the
+// segment's length `bits`), from the entry state `in`.  tabs: per component the DC and the AC table ([2 c], [2 c + 1]).
+// Every iteration consumes at least one bit or ends the loop: a symbol that the segment's remaining bits cannot hold is
+// left unread (the padding behind the last block).  An invalid code with 16 bits in sight or k > 63 marks the exit with
+// kStateErr, and the decoder goes on behind it (one bit on, or into the next block): a guess that stopped at its first
+// error could never meet the true decode again, and every later subsequence would wait for a hand-over one by one.  The
+// mark says that THIS decode of the subsequence met an error; it is not handed on (handed_on), and a chain is accepted
+// only if none of its members carries it.  Exit state and counts are a function of the entry state and the bits alone.
+// coef != nullptr: coefficients are stored as decode_scan stores them; the block in progress at entry is the segment's
+// block number first_blk, blocks from seg_blocks on are dropped, and dc[] holds the predictions at entry.
+HPMVS_JPG_FN SubState decode_subseq(const uint8_t* d, uint32_t bits, uint32_t end, const Huff* tabs, const ScanInfo& si,
+                                    const uint8_t* zigzag, SubState in, SubCount* cnt, int16_t* coef, uint32_t first_blk,
+                                    uint32_t seg_first_mcu, uint32_t seg_blocks, const uint32_t* dc_in) {
+    uint32_t p = in.p, nblk = 0;
+    uint32_t dc[3] = {0, 0, 0};
+    if (dc_in) { dc[0] = dc_in[0]; dc[1] = dc_in[1]; dc[2] = dc_in[2]; }
+    if (cnt) { cnt->nblk = 0; cnt->dc[0] = cnt->dc[1] = cnt->dc[2] = 0; }
+    int blk = (int)(in.bk >> 8), k = (int)(in.bk & 63);
+    bool err = false;
+    int16_t* out = nullptr;  // the block in progress, where it is stored
+    bool out_known = false;
+    while (p < end) {
+        const int c = si.blk_comp[blk];
+        if (coef && !out_known) {
+            const uint32_t g = first_blk + nblk;
+            out = nullptr;
+            if (g < seg_blocks) {
+                const uint32_t mcu = seg_first_mcu + g / (uint32_t)si.bpm;
+                if (mcu < (uint32_t)si.n_mcus) {
+                    const uint32_t my = mcu / (uint32_t)si.mcus_x, mx = mcu - my * (uint32_t)si.mcus_x;
+                    out = coef + si.off[c] + ((size_t)(my * si.v[c] + si.blk_dy[blk]) * si.bx[c] + (mx * si.h[c] + si.blk_dx[blk])) * 64;
+                }
+            }
+            out_known = true;
+        }
+        const uint32_t v = peek32(d, bits, p);
+        const uint32_t avail = bits - p;
+        const uint32_t e = huff_lookup(tabs[2 * c + (k != 0)], v);
+        const uint32_t len = e >> 8;
+        if (len == 0) {
+            if (avail < 16) break;
+            err = true;  // no code: one bit on
+            p++;
+            continue;
+        }
+        const int sym = (int)(e & 255);
+        const int sz = k == 0 ? sym : (sym & 15);  // (DC symbols are at most 15: parse_headers)
+        if (len + (uint32_t)sz > avail) break;
+        const uint32_t vv = sz ? peek32(d, bits, p + len) : 0u;
+        bool done = false;
+        if (k == 0) {
+            const int32_t diff = sz ? extend_bits(vv, sz) : 0;
+            dc[c] += (uint32_t)diff;
+            if (out) out[0] = (int16_t)(int32_t)dc[c];
+            k = 1;
+        } else {
+            const int r = sym >> 4;
+            if (sz == 0) {
+                if (r != 15) done = true;
+                else k += 16;
+            } else {
+                k += r;
+                if (k > 63) err = true;  // the block ends here
+                else if (out) out[zigzag[k]] = (int16_t)extend_bits(vv, sz);
+                k++;
+            }
+            if (k >= 64) done = true;
+        }
+        p += len + (uint32_t)sz;
+        if (done) {
+            k = 0;
+            nblk++;
+            blk = blk + 1 == si.bpm ? 0 : blk + 1;
+            out_known = false;
+        }
+    }
+    if (cnt) {
+        cnt->nblk = nblk;
+        for (int c = 0; c < 3; c++) cnt->dc[c] = dc[c] - (dc_in ? dc_in[c] : 0u);
+    }
+    SubState o;
+    o.p = p;
+    o.bk = (err ? kStateErr : 0u) | (uint32_t)blk << 8 | (uint32_t)k;
+    return o;
+}
+
+// the guess a subsequence starts from: its first bit, block 0, the DC code next (for a segment's first one, the truth)
+HPMVS_JPG_FN SubState guess_state(uint32_t index_in_segment, uint32_t subseq_bits) {
+    SubState s;
+    s.p = index_in_segment * subseq_bits;
+    s.bk = 0;
+    return s;
+}
+
+// What the check asks of a segment whose chain is consistent: no error, the last block just completed, exactly the
+// segment's blocks, and fewer than 8 unread bits unless it is the scan's last segment (decode_scan leaves those unread
+// too, but finds a restart marker only right behind the byte it stopped in).
+HPMVS_JPG_FN bool segment_ok(const Segment& g, SubState last_exit, uint32_t blocks, int bpm, bool last_segment) {
+    if (last_exit.bk != 0 || last_exit.p > g.bits) return false;
+    if (blocks != g.n_mcus * (uint32_t)bpm) return false;
+    return last_segment || g.bits - last_exit.p < 8;
+}
+
+// (plain C++ from here on)
+struct Prescan {
+    std::vector<uint8_t> bytes;  // the scan without its stuffing and markers, 16 zero bytes behind
+    std::vector<Segment> segs;
+    size_t n_subs = 0;
+};
+
+inline ScanInfo make_scan_info(const Frame& fr) {
+    ScanInfo si;
+    memset(&si, 0, sizeof(si));
+    si.ncomp = fr.ncomp;
+    si.mcus_x = fr.mcus_x;
+    si.n_mcus = fr.mcus_x * fr.mcus_y;
+    int b = 0;
+    for (int c = 0; c < fr.ncomp; c++) {
+        si.h[c] = fr.c[c].h; si.v[c] = fr.c[c].v; si.bx[c] = fr.c[c].bx;
+        si.off[c] = (uint32_t)fr.c[c].off;
+        for (int by = 0; by < fr.c[c].v; by++)
+            for (int bx = 0; bx < fr.c[c].h; bx++, b++) {
+                si.blk_comp[b] = (uint8_t)c; si.blk_dx[b] = (uint8_t)bx; si.blk_dy[b] = (uint8_t)by;
+            }
+    }
+    si.bpm = b;
+    return si;
+}
+
+// per component the DC and AC table the scan names, in the order decode_subseq indexes them
+inline void scan_tables(const Frame& fr, const Huff* huff, Huff* tabs6) {
+    for (int c = 0; c < 3; c++) {
+        const int cc = c < fr.ncomp ? c : 0;
+        tabs6[2 * c] = huff[fr.c[cc].td];
+        tabs6[2 * c + 1] = huff[4 + fr.c[cc].ta];
+    }
+}
+
+// Walks the scan's bytes once: drops the 00 of every FF 00, cuts at the RSTn markers the frame's restart interval
+// expects (numbered 0, 1, .. mod 8) and stops at the first other marker, behind which EOI must come before any other
+// scan.  false: something the parallel decode does not take on (FF FF fill, a restart marker too few, misnumbered or
+// without a restart interval, no end marker, no EOI, 512 MiB of scan) -- decode_scan then decides what the file is.
+inline bool prescan(const uint8_t* b, size_t n, size_t scan_start, const Frame& fr, Prescan& ps) {
+    const size_t total_mcus = (size_t)fr.mcus_x * fr.mcus_y;
+    const size_t interval = fr.restart ? (size_t)fr.restart : total_mcus;
+    const size_t want = (total_mcus + interval - 1) / interval;  // segments
+    if (n - scan_start >= ((size_t)1 << 29) || want >= ((size_t)1 << 28)) return false;
+    ps.bytes.clear();
+    ps.bytes.reserve(n - scan_start + 16);
+    ps.segs.clear();
+    size_t seg_first = 0, p = scan_start, end_marker = n;
+    for (;;) {
+        if (p >= n) return false;  // no marker ends the scan
+        const uint8_t v = b[p];
+        if (v != 0xFF) { ps.bytes.push_back(v); p++; continue; }
+        if (p + 1 >= n) return false;
+        const uint8_t m = b[p + 1];
+        if (m == 0) { ps.bytes.push_back(0xFF); p += 2; continue; }
+        if (m == 0xFF) return false;
+        const bool rst = m >= 0xD0 && m <= 0xD7;
+        const bool expected = rst && ps.segs.size() + 1 < want;  // (any marker ends the last segment, as it stops decode_scan)
+        if (expected && m != 0xD0 + (ps.segs.size() & 7)) return false;
+        Segment g;
+        g.first_byte = (uint32_t)seg_first;
+        g.bits = (uint32_t)((ps.bytes.size() - seg_first) * 8);
+        g.first_mcu = (uint32_t)(ps.segs.size() * interval);
+        g.n_mcus = (uint32_t)(total_mcus - g.first_mcu < interval ? total_mcus - g.first_mcu : interval);
+        g.first_sub = g.n_subs = 0;
+        ps.segs.push_back(g);
+        seg_first = ps.bytes.size();
+        if (!expected) { end_marker = p; break; }
+        p += 2;
+    }
+    if (ps.segs.size() != want) return false;
+    ps.bytes.insert(ps.bytes.end(), 16, 0);
+    for (size_t q = end_marker; q + 1 < n; q++) {  // decode_scan's search behind the scan
+        if (b[q] != 0xFF) continue;
+        if (b[q + 1] == 0xD9) return true;
+        if (b[q + 1] == 0xDA) return false;
+    }
+    return false;
+}
+
+// cuts every segment into subsequences of subseq_bits (one at least) -> their number
+inline size_t plan_subsequences(Prescan& ps, uint32_t subseq_bits) {
+    size_t n = 0;
+    for (Segment& g : ps.segs) {
+        g.first_sub = (uint32_t)n;
+        g.n_subs = g.bits ? (g.bits + subseq_bits - 1) / subseq_bits : 1;
+        n += g.n_subs;
+    }
+    ps.n_subs = n;
+    return n;
 }
 
 }  // namespace jpg

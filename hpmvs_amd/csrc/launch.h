@@ -288,6 +288,30 @@ void launch_jpeg_idct(const uint16_t* q, const int16_t* coef, const JpegBlocks& 
 // planes -> interleaved u8 RGB [H][W][3]: exactly W x H pixels are written
 void launch_jpeg_rgb(const uint8_t* planes, const jpg::Planes& P, uint8_t* rgb, hipStream_t st);
 
+// the scan's Huffman data decoded in parallel (kernel_jpeg_entropy.hip, jpeg.hpp: decode_subseq; include/hpmvs_amd.h:
+// hpmvs_jpeg_decode_ex).  bytes: the prescan's unstuffed bytes (16 zero bytes behind), segs / sub_seg: its segments and every
+// subsequence's segment, tabs: six jpg::Huff (per component DC, AC) and the 64 zigzag bytes.  Working arrays, one element per
+// subsequence: entry, exit, cnt, incl; per workgroup of the sync kernel (kSubsPerGroup subsequences): grp_exit [2][n_groups];
+// per 256 subsequences: grp [n_scan_groups].  flags: [0] a pass's slowest workgroup in rounds, [1] the round budget ran out,
+// [2] the check refused the chain.
+struct JpegEntropy {
+    const uint8_t* bytes;
+    const jpg::Segment* segs;
+    const uint32_t* sub_seg;
+    const uint32_t* tabs;
+    jpg::ScanInfo si;
+    uint32_t subseq_bits, n_subs, n_segs, n_groups, n_scan_groups;
+    jpg::SubState *entry, *exit, *grp_exit;
+    uint4 *cnt, *incl, *grp;
+    uint32_t* flags;
+};
+// one synchronisation pass (pass 0 decodes from the guesses first); budget: rounds a workgroup may still take
+void launch_jpeg_entropy_sync(const JpegEntropy& A, int pass, int budget, hipStream_t st);
+// sums, check and write; coef: the zero-filled dense coefficients (JpegBlocks' layout), written only if the check accepts.
+// ev (diagnostics, nullable): five events recorded in front of, between and behind the four kernels; -> the first event
+// call's error, if any (launch errors: hipGetLastError, as for every launcher here)
+hipError_t launch_jpeg_entropy_finish(const JpegEntropy& A, int16_t* coef, hipStream_t st, hipEvent_t* ev = nullptr);
+
 // refined-patch records of the multi-GPU exchange (include/hpmvs_amd.h: hpmvs_record, 192 bytes)
 void launch_pack_records(const DevBatch& b, void* records, hipStream_t st);
 void launch_unpack_records(const void* records, int n, const DevBatch& b, hipStream_t st);

@@ -217,12 +217,53 @@ int hpmvs_jpeg_decode(int device, const uint8_t *bytes, size_t n, uint8_t *rgb, 
 /* diagnostics (tools/jpeg_scale.py): hpmvs_jpeg_decode to a device buffer, with the time of its stages in ms[4]: host parse
  * and entropy decode (wall clock, this thread), coefficient upload, IDCT kernel, RGB kernel (HIP events) */
 int hpmvs_jpeg_decode_timed(int device, const uint8_t *bytes, size_t n, uint8_t *rgb_device, size_t cap, float *ms);
+/* diagnostics (tools/jpeg_entropy_scale.py): the same with the scan decoded on the device and no fallback (HPMVS_ERR_STATE
+ * as hpmvs_jpeg_decode_ex with _DEVICE), stages in ms[12]: [0] host prescan (wall clock); by HIP events [1] uploads of the
+ * scan and its tables with the fills, [2] jpeg_entropy_sync_kernel summed over its passes, [3] the passes with the read-backs
+ * between them, [4] jpeg_entropy_scan_local_kernel, [5] _scan_groups, [6] _check, [7] _write, [8] quantiser upload, [9] IDCT
+ * kernel, [10] RGB kernel; [11] the synchronisation rounds taken */
+/* diagnostics: what decoded the scan in the calling thread's last successful JPEG decode through any entry above --
+ * *used HPMVS_JPEG_ENTROPY_HOST or _DEVICE, *rounds (nullable) the device's synchronisation rounds.  It shows what
+ * hpmvs_jpeg_decode and hpmvs_scene_set_view_jpeg, which report nothing, made of HPMVS_JPEG_ENTROPY and of the _AUTO
+ * threshold.  HPMVS_ERR_STATE before the thread's first such decode. */
+int hpmvs_jpeg_last_decode(int *used, int *rounds);
+int hpmvs_jpeg_entropy_timed(int device, const uint8_t *bytes, size_t n, uint8_t *rgb_device, size_t cap, float *ms);
 /* hpmvs_scene_set_view for a view given as JPEG file bytes: level 0 is decoded in HBM (the pixels never visit the host),
  * undistorted there when k1 != 0 (as hpmvs_scene_set_view_distorted does, and with its rules for f and k1, which hold for
  * k1 == 0 too), and the pyramid is built from it.  Width and height are the file's (hpmvs_jpeg_info).  Calls for different
  * views of one scene are as independent of each other as those of hpmvs_scene_set_view; nothing is kept between calls. */
 int hpmvs_scene_set_view_jpeg(hpmvs_scene *s, int view, const uint8_t *bytes, size_t n, const hpmvs_camera *cam, float f,
                               float k1);
+/* Where the scan's Huffman data is decoded.  _HOST: the bit-serial walk on the calling thread, as hpmvs_jpeg_info does it.
+ * _DEVICE: on the GPU (kernel_jpeg_entropy.hip): the host removes the byte stuffing and finds the restart markers, the scan's
+ * bytes go up instead of the coefficients, and subsequences of the scan are decoded in parallel until each starts where the
+ * one before it ended; a check kernel accepts that chain only if it is the sequential decode and one the host walk accepts.
+ * An accepted chain gives the host walk's coefficients bit for bit.  Anything else -- a chain the check refuses, more
+ * synchronisation rounds than the cap, FF FF fill bytes in the scan, restart markers or an end of scan that the prescan does
+ * not vouch for, working buffers the device cannot allocate -- is left to the host walk, whose code, message and pixels are then the call's: no refusal, message or pixel
+ * depends on this choice.  _AUTO: the device for scans of HPMVS_JPEG_AUTO_MIN_SCAN_BYTES and more, the host below.
+ * hpmvs_jpeg_decode and hpmvs_scene_set_view_jpeg are the _ex entries with what the environment variable
+ * HPMVS_JPEG_ENTROPY=host|device|auto names (read once per process; unset or anything else: auto); its `device` still leaves
+ * to the host walk what the device does not take.
+ * The _ex entries called with _DEVICE themselves do NOT fall back: where the host walk would have to run they return
+ * HPMVS_ERR_STATE with the reason in hpmvs_last_error (a file whose headers are refused keeps its own code).
+ * *used (nullable): HPMVS_JPEG_ENTROPY_HOST or _DEVICE, what decoded the scan.  HPMVS_ERR_ARG for another `entropy` value. */
+enum { HPMVS_JPEG_ENTROPY_AUTO = 0, HPMVS_JPEG_ENTROPY_HOST = 1, HPMVS_JPEG_ENTROPY_DEVICE = 2 };
+#define HPMVS_JPEG_AUTO_MIN_SCAN_BYTES 445155 /* measured: profiles/jpeg_entropy_scale.json, DESIGN.md 3.13 */
+int hpmvs_jpeg_decode_ex(int device, const uint8_t *bytes, size_t n, uint8_t *rgb, size_t cap, int rgb_on_device, int entropy,
+                         int *used);
+int hpmvs_scene_set_view_jpeg_ex(hpmvs_scene *s, int view, const uint8_t *bytes, size_t n, const hpmvs_camera *cam, float f,
+                                 float k1, int entropy, int *used);
+/* The dense coefficients behind the entropy decode, to host memory: per component [blocks_y][blocks_x][64] int16 in natural
+ * order, the components one behind the other, blocks padded to whole MCUs (cap: int16 elements available at coef).
+ * subseq_bits: the subsequence size of the device decode, 0 for the shipped one (512), else a multiple of 32 from 64 up --
+ * a test hook that puts subsequence boundaries at every position of a small file.  The cap on synchronisation rounds
+ * shrinks as the size grows (740 * 512 / subseq_bits, rounded down): above 378 880 bits it is 0, and only a scan whose
+ * segments are one subsequence each is decoded on the device.  *rounds (nullable): synchronisation
+ * rounds the device decode took (0 on the host).  HPMVS_ERR_ARG before any write for a bad entropy or subseq_bits value
+ * and a short cap; _DEVICE as above. */
+int hpmvs_jpeg_coefficients(int device, const uint8_t *bytes, size_t n, int entropy, int subseq_bits, int16_t *coef, size_t cap,
+                            int *used, int *rounds);
 
 /* ---- the hot path ------------------------------------------------------------------------- */
 /* Full optimize() for every patch of the batch.  `stream` is a hipStream_t (NULL = default
