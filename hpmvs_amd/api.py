@@ -101,7 +101,7 @@ EXPORTS = [
     "hpmvs_regularize_batch", "hpmvs_filter_batch", "hpmvs_seed_tree_batch", "hpmvs_octree_locate_batch",
     "hpmvs_octree_insert_batch", "hpmvs_octree_route_batch", "hpmvs_octree_partition", "hpmvs_extend_tree_batch",
     "hpmvs_extend_forest_batch", "hpmvs_process_forest_batch", "hpmvs_border_forest_batch",
-    "hpmvs_level_conflicts_batch", "hpmvs_conflicts_from_footprints",
+    "hpmvs_level_conflicts_batch", "hpmvs_conflicts_from_footprints", "hpmvs_level_walk_batch", "hpmvs_last_level_walk",
     "hpmvs_scene_center", "hpmvs_init_patches_sphere_batch",
     "hpmvs_jpeg_info", "hpmvs_jpeg_decode", "hpmvs_scene_set_view_jpeg", "hpmvs_jpeg_decode_timed",
     "hpmvs_jpeg_decode_ex", "hpmvs_scene_set_view_jpeg_ex", "hpmvs_jpeg_coefficients", "hpmvs_jpeg_entropy_timed",
@@ -183,6 +183,9 @@ def lib():
     L.hpmvs_conflicts_from_footprints.argtypes = [C.c_int] * 5 + [C.c_void_p] * 6 + [C.c_void_p, C.c_void_p, C.c_size_t,
                                                   C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                                   C.c_int, C.c_void_p]
+    L.hpmvs_level_walk_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(PatchBatch)] + [C.c_void_p] * 4 + [C.c_float, C.c_int] + \
+        [C.c_void_p] * 4 + [C.POINTER(C.c_int32), C.c_int, C.c_void_p]
+    L.hpmvs_last_level_walk.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3
     L.hpmvs_depth_gates_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_float, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int, C.c_void_p]
     L.hpmvs_depth_ops_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_void_p, C.c_int, C.c_void_p]
@@ -677,6 +680,39 @@ def conflicts_from_footprints(n_images, writes, frees, attached, view_block, n_l
     return _conflicts(lambda fo, fa, cf, ao, aa, ca, nf, na: lib().hpmvs_conflicts_from_footprints(
         int(device), n, M, V, int(n_levels), ni.ctypes.data, wr.ctypes.data, fr.ctypes.data, at.ctypes.data, vb.ctypes.data, evp,
         fo, fa, cf, ao, aa, ca, nf, na, 0, None), n)
+
+
+WALK_EVENT, WALK_REFINED, WALK_BORDER, WALK_HAS_PRE, WALK_PRE_TAKEN, WALK_POST_TAKEN = 1, 2, 4, 8, 16, 32   # HPMVS_WALK_*
+
+
+def level_walk(scene: Scene, batch: Batch, flags, set, pre_key, post_key, margin=1.0, abs_int=0, options: Options | None = None,
+               stage=None):
+    """The wave walk of one extend level as ONE hpmvs_level_walk_batch (include/hpmvs_amd.h): `batch` holds the
+    level's queue in the reference's order (an event's patch, a candidate's refined patch), flags the WALK_* bits per item, set
+    the tree each candidate's keys belong to (None: one set), pre_key / post_key its leaf before and after refinement.  stage:
+    the items' preset stages (default batch.stage).  The scene's depth maps receive the accepted candidates and the events'
+    subtractions.  Returns (stage, counts [n, 3], accepted [n] uint8, wave [n] (the 1-based wave that decided the item), n_waves)."""
+    o = options or default_options()
+    n = batch.n
+    b = batch.c_struct()
+    fl = np.ascontiguousarray(flags, dtype=np.uint8).reshape(n)
+    st = None if set is None else np.ascontiguousarray(set, dtype=np.int32).reshape(n)
+    pre = np.ascontiguousarray(pre_key, dtype=np.uint64).reshape(n)
+    post = np.ascontiguousarray(post_key, dtype=np.uint64).reshape(n)
+    stage = np.array(batch.stage if stage is None else stage, dtype=np.int32).reshape(n)
+    counts = np.full((n, 3), -1, np.int32); accepted = np.zeros(n, np.uint8); wave = np.zeros(n, np.int32)
+    n_waves = C.c_int32(0)
+    _chk(lib().hpmvs_level_walk_batch(scene.h, C.byref(o), C.byref(b), fl.ctypes.data, None if st is None else st.ctypes.data,
+                                      pre.ctypes.data, post.ctypes.data, float(margin), int(abs_int), stage.ctypes.data,
+                                      counts.ctypes.data, accepted.ctypes.data, wave.ctypes.data, C.byref(n_waves), 0, None))
+    return stage, counts, accepted, wave, int(n_waves.value)
+
+
+def last_level_walk(scene: Scene):
+    """(rounds, most rounds in one wave, in-order passes) of the last level_walk on this scene."""
+    r, m, f = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _chk(lib().hpmvs_last_level_walk(scene.h, C.byref(r), C.byref(m), C.byref(f)))
+    return int(r.value), int(m.value), int(f.value)
 
 
 def build_pyramid(img: np.ndarray, device: int = 0) -> np.ndarray:

@@ -91,6 +91,7 @@ struct hpmvs_scene {
     struct StageEntry { hipStream_t st = nullptr; char* dev = nullptr; char* host = nullptr; std::mutex mu; };
     static constexpr int kStageEntries = 8;
     mutable int32_t* last_ws = nullptr;   // the workspace of the last refinement launch (hpmvs_last_wide_patches)
+    mutable std::atomic<int32_t> last_walk[3] = {};   // hpmvs_last_level_walk: rounds, most rounds in a wave, in-order passes
     static constexpr int kStageCapPatches = 4096;
     mutable StageEntry stage[kStageEntries];
     mutable std::atomic<unsigned> stage_next{0};
@@ -3176,6 +3177,223 @@ int hpmvs_level_conflicts_batch(const hpmvs_scene* s, const hpmvs_patch_batch* b
     launch_depth_footprints(dev_scene(s), s->ddepth, D, wr, fr, at, vb, st);
     HIPCHK(hipGetLastError());
     return conflicts_call(c, who, F, on_device, dfo, flow_adj, cap_flow, dao, anti_adj, cap_anti, n_flow, n_anti, st);
+}
+
+// The wave walk of one extend level, entirely on the device (kernel_level_walk.hip, level_walk.hpp): the graph by
+// the device code of hpmvs_level_conflicts_batch, the key records, then per wave the gates over the pending refined candidates,
+// resolve rounds, and ONE ordered depth update.  The host reads a count per wave and per round and decides nothing but when to stop.
+static constexpr int kWalkFewDecided = 8;      // a round that decided fewer items, with at most kWalkFinishBudget left, is followed by
+static constexpr int kWalkFinishBudget = 128;  // an in-order pass of one wavefront that decides them all: the end of a chain
+int hpmvs_level_walk_batch(hpmvs_scene* s, const hpmvs_options* o, const hpmvs_patch_batch* items, const uint8_t* flags, const int32_t* set,
+                           const uint64_t* pre_key, const uint64_t* post_key, float margin, int abs_int, int32_t* stage, int32_t* counts,
+                           uint8_t* accepted, int32_t* wave, int32_t* n_waves, int on_device, void* stream) {
+    const std::string who = "level_walk_batch";
+    if (!s || !o || !items || !n_waves) return fail(HPMVS_ERR_ARG, who + ": null scene / options / batch / n_waves");
+    if (items->n < 0 || items->max_images < 1 || items->max_images > HPMVS_MAX_IMAGES) return fail(HPMVS_ERR_ARG, who + ": bad n/max_images");
+    if (items->n > 0 && (!items->center || !items->normal || !items->scale || !items->n_images || !items->images))
+        return fail(HPMVS_ERR_ARG, who + ": batch input arrays missing");
+    if (items->n > 0 && (!flags || !pre_key || !post_key || !stage || !counts || !accepted || !wave))
+        return fail(HPMVS_ERR_ARG, who + ": flags / pre_key / post_key / stage / counts / accepted / wave missing");
+    if (o->MIN_IMAGES_PER_PATCH < 1) return fail(HPMVS_ERR_ARG, who + ": MIN_IMAGES_PER_PATCH must be >= 1");
+    int n_levels = 1;
+    for (int v = 0; v < s->n_views; v++) n_levels = std::max(n_levels, (int)s->hviews[v].n_levels);
+    {   // whatever hpmvs_level_conflicts_batch refuses (the graph is over at most n nodes)
+        uint32_t off = 0, total = 0;
+        const int rc = conflicts_check(who, items->n, items->max_images, s->n_views, n_levels, &off, nullptr, 0, &off, nullptr, 0, &total, &total);
+        if (rc) return rc;
+    }
+    if (!s->committed || !s->depth_pool || !s->ddepth) return fail(HPMVS_ERR_STATE, who + ": call hpmvs_scene_depth_reset first");
+    if (s->depth_floats >= ((size_t)1 << 32)) return fail(HPMVS_ERR_STATE, who + ": the scene's depth maps hold 2^32 cells or more");
+    *n_waves = 0;
+    for (auto& w : s->last_walk) w = 0;
+    if (items->n == 0) return HPMVS_OK;
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    Call c(s, on_device, st);
+    const int n = items->n, M = items->max_images, V = s->n_views;
+    const size_t N = (size_t)n;
+    const DevBatch D = c.batch(items, Call::kRead);
+    const uint8_t* dflags = c.in(flags, N);
+    const int32_t* dset = c.in(set, N);
+    const unsigned long long *dpre = c.in((const unsigned long long*)pre_key, N), *dpost = c.in((const unsigned long long*)post_key, N);
+    // outputs: nothing of the caller's is written before walk_init_kernel, so no zero fill and no copy back on a refusal
+    int32_t* dstage = c.arr(stage, N, Call::kCopyIn | Call::kCopyBack);
+    int32_t* dcounts = c.arr(counts, 3 * N, Call::kCopyBack);
+    uint8_t* daccepted = c.arr(accepted, N, Call::kCopyBack);
+    int32_t* dwave = c.arr(wave, N, Call::kCopyBack);
+    // the call's own arrays, one block: sizes known from n (a node batch has at most n rows)
+    size_t need = 0;
+    auto room = [&need](size_t bytes) { const size_t at = need; need += reg_align(bytes); return at; };
+    const size_t a_ctl = room(64), a_state = room(N), a_ok = room(N), a_sub = room(N), a_nev = room(N), a_mark = room(4 * N), a_scan = room(4 * N),
+                 a_node = room(4 * N), a_item = room(4 * N), a_slot = room(4 * N), a_rows = room(4 * N), a_gv = room(4 * N), a_gb = room(4 * N),
+                 a_gf = room(4 * N), a_fpre = room(4 * N), a_fpost = room(4 * N), a_foff = room(4 * (N + 1)), a_aoff = room(4 * (N + 1)),
+                 a_k0 = room(16 * N), a_k1 = room(16 * N), a_key = room(16 * N), a_v0 = room(8 * N), a_v1 = room(8 * N), a_val = room(8 * N),
+                 a_s0 = room(8 * N), a_set = room(8 * N), a_p0 = room(8 * N), a_perm = room(8 * N), a_bc = room(16 * N), a_bn = room(16 * N),
+                 a_bs = room(4 * N), a_bi = room(4 * N), a_bm = room(4 * N * (size_t)M);
+    char* block = (char*)c.scratch(need);
+    if ((rc = c.begin())) return rc;
+    if (!block) return c.error() ? c.error() : fail(HPMVS_ERR_HIP, who + ": out of device memory");
+    unsigned int* ctl = (unsigned int*)(block + a_ctl);
+    uint8_t *state = (uint8_t*)(block + a_state), *ok = (uint8_t*)(block + a_ok), *sub = (uint8_t*)(block + a_sub), *node_event = (uint8_t*)(block + a_nev);
+    uint32_t *mark = (uint32_t*)(block + a_mark), *scan = (uint32_t*)(block + a_scan);
+    int32_t *node_of = (int32_t*)(block + a_node), *item_of = (int32_t*)(block + a_item), *slot_of = (int32_t*)(block + a_slot), *rows = (int32_t*)(block + a_rows);
+    uint32_t *flow_off = (uint32_t*)(block + a_foff), *anti_off = (uint32_t*)(block + a_aoff);
+    DevBatch B;   // the compact batch: the nodes for the graph, then each wave's pending refined candidates for the gates
+    memset(&B, 0, sizeof(B));
+    B.max_images = M;
+    B.center = (float*)(block + a_bc); B.normal = (float*)(block + a_bn); B.scale = (float*)(block + a_bs);
+    B.n_images = (int32_t*)(block + a_bi); B.images = (int32_t*)(block + a_bm);
+    auto temp_of = [&c](size_t bytes) { return c.scratch(bytes ? bytes : 16); };
+#define WALK_PRIM(call_with_temp)                                                                        \
+    do {                                                                                                 \
+        void* temp = nullptr; size_t temp_bytes = 0;                                                     \
+        if ((call_with_temp) != 0) return fail(HPMVS_ERR_HIP, who + ": rocPRIM size query failed");      \
+        if (!(temp = temp_of(temp_bytes))) return c.error();                                             \
+        if ((call_with_temp) != 0) return fail(HPMVS_ERR_HIP, who + ": rocPRIM call failed");            \
+    } while (0)
+
+    // 1. the flags, before anything is written
+    HIPCHK(hipMemsetAsync(ctl, 0, 64, st));
+    launch_walk_check(n, dflags, dset, ctl + 8, st);
+    unsigned int bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, ctl + 8, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (bad) return fail(HPMVS_ERR_ARG, who + ": " + std::to_string(bad) + " items with a flag byte that cannot occur (an event that is refined or border, an unknown bit) or a negative set");
+    // 2. the nodes in queue order and the graph over them
+    launch_walk_mark(n, dflags, mark, st);
+    WALK_PRIM(walk_scan(temp, &temp_bytes, mark, scan, n, st));
+    launch_walk_nodes(n, dflags, mark, scan, node_of, item_of, node_event, sub, ctl + 9, st);
+    unsigned int n_nodes = 0;
+    HIPCHK(hipMemcpyAsync(&n_nodes, ctl + 9, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (n_nodes > (unsigned int)n) return fail(HPMVS_ERR_HIP, who + ": node count");
+    uint32_t *flow_adj = nullptr, *anti_adj = nullptr;
+    if (n_nodes) {
+        B.n = (int)n_nodes;
+        launch_walk_gather(D, item_of, (int)n_nodes, B, st);
+        int32_t* fp = (int32_t*)c.scratch(4 * (size_t)n_nodes * (11 * (size_t)M + 3 * (size_t)V));
+        if (!fp) return c.error();
+        conflicts::Footprints F;
+        F.n = (int)n_nodes; F.M = M; F.V = V; F.n_levels = n_levels; F.n_images = B.n_images; F.is_event = node_event;
+        int32_t *wr = fp, *fr = wr + (size_t)n_nodes * M * 4, *at = fr + (size_t)n_nodes * M * 4, *vb = at + (size_t)n_nodes * M * 3;
+        F.wr = wr; F.fr = fr; F.at = at; F.vb = vb;
+        launch_depth_footprints(dev_scene(s), s->ddepth, B, wr, fr, at, vb, st);
+        HIPCHK(hipGetLastError());
+        const unsigned long long* pairs = nullptr;
+        uint32_t nf = 0, na = 0;
+        const int grc = launch_conflicts(F, [&c](size_t bytes) { return c.scratch(bytes); }, flow_off, anti_off, &pairs, &nf, &na, st);
+        if (grc == kConflictsMemory) return c.error() ? c.error() : fail(HPMVS_ERR_HIP, who + ": out of device memory");
+        if (grc == kConflictsTooMany)
+            return fail(HPMVS_ERR_STATE, who + ": more than 2^30 conflicting (reader, writer) pairs before duplicates are dropped");
+        if (grc != kConflictsOk) return fail(HPMVS_ERR_HIP, who + ": " + hipGetErrorString(hipGetLastError()));
+        flow_adj = (uint32_t*)c.scratch(4 * ((size_t)nf + 1)); anti_adj = (uint32_t*)c.scratch(4 * ((size_t)na + 1));
+        if (!flow_adj || !anti_adj) return c.error();
+        launch_conflicts_adjacency(pairs, nf, na, flow_adj, anti_adj, st);
+        HIPCHK(hipGetLastError());
+    }
+    // 3. the key records, sorted by (set, key, item): two stable sorts
+    unsigned long long *k0 = (unsigned long long*)(block + a_k0), *k1 = (unsigned long long*)(block + a_k1), *rec_key = (unsigned long long*)(block + a_key);
+    uint32_t *v0 = (uint32_t*)(block + a_v0), *v1 = (uint32_t*)(block + a_v1), *rec_val = (uint32_t*)(block + a_val);
+    uint32_t *s0 = (uint32_t*)(block + a_s0), *rec_set = (uint32_t*)(block + a_set), *p0 = (uint32_t*)(block + a_p0), *perm = (uint32_t*)(block + a_perm);
+    launch_walk_records(n, dflags, dpre, dpost, k0, v0, st);
+    WALK_PRIM(walk_sort_keys64(temp, &temp_bytes, k0, k1, v0, v1, 2 * n, st));
+    launch_walk_record_sets(n, dflags, dset, v1, s0, p0, st);
+    WALK_PRIM(walk_sort_keys32(temp, &temp_bytes, s0, rec_set, p0, perm, 2 * n, st));
+    launch_walk_permute(n, perm, k1, v1, rec_key, rec_val, st);
+    level_walk::Level L;
+    L.n = n; L.min_images = o->MIN_IMAGES_PER_PATCH; L.flags = dflags; L.set = dset; L.pre = dpre; L.post = dpost;
+    L.node_of = node_of; L.item_of = item_of; L.flow_off = flow_off; L.flow_adj = flow_adj; L.anti_off = anti_off; L.anti_adj = anti_adj;
+    L.n_rec = 2u * (unsigned int)n; L.rec_set = rec_set; L.rec_key = rec_key; L.rec_val = rec_val;
+    L.first_pre = (uint32_t*)(block + a_fpre); L.first_post = (uint32_t*)(block + a_fpost);
+    launch_walk_first(L, (uint32_t*)(block + a_fpre), (uint32_t*)(block + a_fpost), st);
+    // 4. the waves.  From here on the outputs and the maps are written.
+    launch_walk_init(n, state, ok, dcounts, daccepted, dwave, st);
+    HIPCHK(hipGetLastError());
+    WalkArrays A;
+    A.state = state; A.ok = ok; A.slot_of = slot_of; A.gv = (int32_t*)(block + a_gv); A.gb = (int32_t*)(block + a_gb); A.gf = (int32_t*)(block + a_gf);
+    A.n_images = D.n_images; A.stage = dstage; A.counts = dcounts; A.wave = dwave; A.accepted = daccepted;
+    DevBatch Dok = D;   // the level's batch with this wave's accepted / applied items as its ok mask: rows in queue order
+    Dok.ok = ok;
+    const DevScene sc = dev_scene(s);
+    unsigned long long *op_keys = nullptr, *op_sorted = nullptr;
+    void* op_temp = nullptr;
+    size_t op_temp_bytes = 0;
+    int waves = 0, rounds_all = 0, rounds_most = 0, finishes = 0;
+    for (int w = 1;; w++) {
+        HIPCHK(hipMemsetAsync(ctl, 0, 32, st));
+        launch_walk_begin(n, dflags, state, ok, rows, slot_of, ctl, st);
+        unsigned int head[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(head, ctl, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const unsigned int pending = head[0], gated = head[1];
+        if (!pending) break;
+        if (w > n || pending > (unsigned int)n || gated > pending) return fail(HPMVS_ERR_STATE, who + ": the waves do not end (a bug: the first pending item of a wave always decides)");
+        waves = w;
+        if (gated) {
+            B.n = (int)gated;
+            launch_walk_gather(D, rows, (int)gated, B, st);
+            launch_depth_gates(sc, s->ddepth, B, margin, abs_int, A.gv, A.gb, A.gf, st);
+        }
+        unsigned int tail[3] = {0, 0, 0};   // ctl[2 .. 4]
+        int rounds = 0;
+        for (unsigned int decided = 0; decided < pending;) {
+            launch_walk_round(L, A, w, ctl, st);
+            HIPCHK(hipMemcpyAsync(tail, ctl + 2, 12, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            rounds++;
+            if (tail[0] <= decided || tail[0] > pending) return fail(HPMVS_ERR_STATE, who + ": a round decided nothing (a bug: the first undecided item always decides)");
+            const bool few = tail[0] - decided < (unsigned int)kWalkFewDecided;
+            decided = tail[0];
+            if (few && decided < pending && pending - decided <= (unsigned int)kWalkFinishBudget) {   // the end of a chain: one wavefront takes the rest in order
+                launch_walk_finish(L, A, w, kWalkFinishBudget, ctl, st);
+                HIPCHK(hipMemcpyAsync(tail, ctl + 2, 12, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
+                finishes++;
+                if (tail[0] <= decided || tail[0] > pending) return fail(HPMVS_ERR_STATE, who + ": the in-order pass decided nothing (a bug)");
+                decided = tail[0];
+            }
+        }
+        HIPCHK(hipGetLastError());
+        rounds_all += rounds; rounds_most = std::max(rounds_most, rounds);
+        if (tail[1] && !tail[2]) launch_set_depths(sc, s->ddepth, Dok, st);   // additions only: a minimum per cell, any order
+        else if (tail[1]) {
+            const size_t cap = N * (size_t)M;
+            if (!op_keys) {
+                op_keys = (unsigned long long*)c.scratch(8 * cap); op_sorted = (unsigned long long*)c.scratch(8 * cap);
+                if (!op_keys || !op_sorted) return c.error();
+            }
+            HIPCHK(hipMemsetAsync(ctl + 10, 0, 4, st));
+            launch_depth_ops_keys(sc, s->ddepth, s->depth_pool, Dok, op_keys, ctl + 10, st);
+            unsigned int count = 0;
+            HIPCHK(hipMemcpyAsync(&count, ctl + 10, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            if (count > cap) return fail(HPMVS_ERR_HIP, who + ": depth-op key count");
+            if (count) {
+                size_t bytes = 0;
+                if (depth_ops_sort(nullptr, &bytes, op_keys, op_sorted, count, st) != 0) return fail(HPMVS_ERR_HIP, who + ": rocPRIM size query failed");
+                if (bytes > op_temp_bytes || !op_temp) {
+                    if (!(op_temp = temp_of(bytes))) return c.error();
+                    op_temp_bytes = bytes;
+                }
+                if (depth_ops_sort(op_temp, &bytes, op_keys, op_sorted, count, st) != 0) return fail(HPMVS_ERR_HIP, who + ": rocPRIM sort failed");
+                launch_depth_ops_apply(sc, s->ddepth, s->depth_pool, Dok, sub, op_sorted, count, st);
+            }
+        }
+        HIPCHK(hipGetLastError());
+    }
+#undef WALK_PRIM
+    *n_waves = waves;
+    s->last_walk[0] = rounds_all; s->last_walk[1] = rounds_most; s->last_walk[2] = finishes;
+    return c.finish();   // (waits in both forms: the scratch is freed on return)
+}
+// rounds of the last hpmvs_level_walk_batch on this scene, the most in one wave, and its in-order passes
+int hpmvs_last_level_walk(const hpmvs_scene* s, int32_t* rounds, int32_t* most_rounds, int32_t* in_order_passes) {
+    if (!s) return fail(HPMVS_ERR_ARG, "last_level_walk: null scene");
+    if (rounds) *rounds = s->last_walk[0];
+    if (most_rounds) *most_rounds = s->last_walk[1];
+    if (in_order_passes) *in_order_passes = s->last_walk[2];
+    return HPMVS_OK;
 }
 
 // how many patches of the last refinement launch outgrew the batch kernel's 64-id rows and were redone by the wide kernel

@@ -5,6 +5,7 @@
 #include <functional>
 
 #include "conflicts.hpp"
+#include "level_walk.hpp"
 #include "dev_types.h"
 #include "jpeg.hpp"
 #include "octree.hpp"
@@ -247,6 +248,39 @@ int launch_conflicts(const conflicts::Footprints& F, const std::function<void*(s
                      const unsigned long long** pairs_out, uint32_t* n_flow, uint32_t* n_anti, hipStream_t st);
 void launch_conflicts_adjacency(const unsigned long long* pairs, uint32_t n_flow, uint32_t n_anti, uint32_t* flow_adj, uint32_t* anti_adj,
                                 hipStream_t st);
+
+// an extend level's wave walk (kernel_level_walk.hip, level_walk.hpp, include/hpmvs_amd.h: hpmvs_level_walk_batch).  The entry point
+// strings these together with the graph, gate and depth-op launches above; every launch is a kernel of its own on `st`.  walk_scan
+// and the two sorts follow depth_ops_sort: temp == nullptr reports the temporary bytes; != 0: the rocPRIM call failed.
+// ctl: [0] pending items, [1] the refined candidates among them, [2] decided in this wave, [3] its ops, [4] the subtractions among them.
+struct WalkArrays {
+    uint8_t *state, *ok;
+    int32_t *slot_of, *gv, *gb, *gf;
+    const int32_t* n_images;
+    int32_t *stage, *counts, *wave;
+    uint8_t* accepted;
+};
+void launch_walk_check(int n, const uint8_t* flags, const int32_t* set, unsigned int* bad, hipStream_t st);
+int walk_scan(void* temp, size_t* temp_bytes, const uint32_t* in, uint32_t* out, int n, hipStream_t st);
+void launch_walk_mark(int n, const uint8_t* flags, uint32_t* mark, hipStream_t st);
+void launch_walk_nodes(int n, const uint8_t* flags, const uint32_t* mark, const uint32_t* scan, int32_t* node_of, int32_t* item_of,
+                       uint8_t* node_event, uint8_t* subtract, unsigned int* n_nodes, hipStream_t st);
+void launch_walk_gather(const DevBatch& src, const int32_t* rows, int count, const DevBatch& dst, hipStream_t st);
+int walk_sort_keys64(void* temp, size_t* temp_bytes, const unsigned long long* key_in, unsigned long long* key, const uint32_t* val_in,
+                     uint32_t* val, int count, hipStream_t st);
+int walk_sort_keys32(void* temp, size_t* temp_bytes, const uint32_t* key_in, uint32_t* key, const uint32_t* val_in, uint32_t* val, int count,
+                     hipStream_t st);
+void launch_walk_records(int n, const uint8_t* flags, const unsigned long long* pre, const unsigned long long* post, unsigned long long* key,
+                         uint32_t* val, hipStream_t st);
+void launch_walk_record_sets(int n, const uint8_t* flags, const int32_t* set, const uint32_t* val, uint32_t* rec_set, uint32_t* pos,
+                             hipStream_t st);
+void launch_walk_permute(int n, const uint32_t* perm, const unsigned long long* key_in, const uint32_t* val_in, unsigned long long* key,
+                         uint32_t* val, hipStream_t st);
+void launch_walk_first(const level_walk::Level& L, uint32_t* first_pre, uint32_t* first_post, hipStream_t st);
+void launch_walk_init(int n, uint8_t* state, uint8_t* ok, int32_t* counts, uint8_t* accepted, int32_t* wave, hipStream_t st);
+void launch_walk_begin(int n, const uint8_t* flags, uint8_t* state, uint8_t* ok, int32_t* rows, int32_t* slot_of, unsigned int* ctl, hipStream_t st);
+void launch_walk_round(const level_walk::Level& L, const WalkArrays& A, int w, unsigned int* ctl, hipStream_t st);
+void launch_walk_finish(const level_walk::Level& L, const WalkArrays& A, int w, int budget, unsigned int* ctl, hipStream_t st);
 
 // the split into subtrees (kernel_octree_partition.hip, include/hpmvs_amd.h: hpmvs_octree_partition).  launch_octree_partition
 // reads the table launch_octree_build made and enqueues the leaf kernel, the sort, the one-wavefront loop and the assignment on

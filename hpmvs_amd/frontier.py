@@ -37,6 +37,9 @@ without events.
   candidate (asserted against the oracle's `orc_extend_round` on BASELINE configs[0] and on a 12-view scene; with events
   against the sequential filter / extend loop, tests/test_gpu_filter_level.py).  tests/test_cpu_frontier_walk.py
   drives `_walk` without a device against the sequential loop of a toy model.
+  Every level call takes device_walk=True: the queue then goes to ONE hpmvs_level_walk_batch, which runs the waves on the device
+  by the same rule stated over earlier neighbours (hpmvs_amd/csrc/level_walk.hpp), and `_walk` is not
+  used.  `_walk` stays the readable statement of the rule and the default.
 
 The octree itself stays with the scheduler (out of scope): `occupied` is the caller's set of cell keys,
 `cell_key` the caller's map from a point to its leaf (default: the uniform grid of leaf width `width`).
@@ -249,11 +252,63 @@ def _walk(queue, pre_key, post_key, refined, n_images, reads, writes, ev_cells, 
     return accepted, waves, deferred_log
 
 
-def _level(scene, parents, width, occupied, margin, abs_int, o, keys, n_levels, sequential=True, events=None, event_cell=()):
+def _walk_key(k):
+    """A leaf key of the walk as hpmvs_level_walk_batch takes it: (set or None, 64-bit key).  The grid's and a tree's keys are
+    integers, a forest's (tree, key) pairs; REFUSED is key 0 of whatever set."""
+    return (int(k[0]), int(k[1])) if isinstance(k, tuple) else (None, int(k))
+
+
+def _device_walk(scene, out, events, n_ev, M, queue, pre_key, post_key, skip, refined, border, occupied, margin, abs_int, o):
+    """The walk of `queue` as ONE hpmvs_level_walk_batch: the queue's items become the rows of one batch with
+    their flag bytes, sets and keys -- no graph, no token set and no count reaches the host -- and the call's arrays fill the
+    LevelResult `_walk` would have filled.  `occupied` grows by the accepted candidates' leaves."""
+    N = out.n
+    n = len(queue)
+    flags, sets = np.zeros(n, np.uint8), np.zeros(n, np.int32)
+    pre, post = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+    rows = np.zeros(n, np.int64)
+    for i, (kind, t) in enumerate(queue):
+        if kind == "e":
+            flags[i], rows[i] = api.WALK_EVENT, N + t
+            continue
+        rows[i] = t
+        f, s = 0, None
+        pk = pre_key[t]
+        if not (isinstance(pk, tuple) and pk[0] == "outside"):     # (an outside candidate is never pre-gated)
+            s, pre[i] = _walk_key(pk)
+            f |= api.WALK_HAS_PRE | (api.WALK_PRE_TAKEN if pk in occupied else 0)
+        if refined[t]:
+            f |= api.WALK_REFINED
+            if border is not None and border[t]:
+                f |= api.WALK_BORDER
+            else:
+                s2, post[i] = _walk_key(post_key[t])
+                s = s if s2 is None else s2
+                f |= api.WALK_POST_TAKEN if post_key[t] in occupied else 0
+        flags[i], sets[i] = f, 0 if s is None else s
+    both = _concat([_rows(out, np.arange(N), M)] + ([_rows(events, np.arange(n_ev), M)] if n_ev else []))
+    stage = np.where(skip != 0, 20, out.stage).astype(np.int32)
+    counts = np.full((N, 3), -1, np.int32)
+    cand = np.array([kind == "c" for kind, _ in queue], bool)
+    st, cnt, acc, wave, waves = api.level_walk(scene, _rows(both, rows), flags, sets, pre, post, margin, abs_int, o,
+                                               stage=np.where(cand, stage[np.minimum(rows, N - 1)], 0) if n else None)
+    stage[rows[cand]] = st[cand]
+    counts[rows[cand]] = cnt[cand]
+    accepted = sorted(int(t) for t in rows[cand & (acc != 0)])
+    for t in accepted:
+        occupied.add(post_key[t])
+    deferred_log = [int((wave > w + 1).sum()) for w in range(waves)]
+    return LevelResult(out, stage, counts, accepted, waves, deferred_log, [t for kind, t in queue if kind == "c" and stage[t] == 27],
+                       {t: post_key[t] for t in accepted} if border is not None else {})
+
+
+def _level(scene, parents, width, occupied, margin, abs_int, o, keys, n_levels, sequential=True, events=None, event_cell=(), walk="host"):
     """CellProcessor::extend over `parents` with the subtraction events `events` (a Batch, or None): event j comes before the
     candidates of parent event_cell[j] (non-decreasing).  The candidate steps, the queue, ONE hpmvs_level_conflicts_batch over the
     queue's events and refined candidates, and the walk with the device behind its two callables.  `n_levels` is not used: the
-    call takes the pyramid levels from the scene's cameras, as _pyramid_levels does."""
+    call takes the pyramid levels from the scene's cameras, as _pyramid_levels does.
+    walk = "device": the candidate steps and the queue as before, then ONE hpmvs_level_walk_batch in place of the graph call, the
+    token sets and `_walk` (_device_walk); the LevelResult is the same."""
     out, pre_key, post_key, skip, refined, border = _candidates(scene, parents, width, keys, o)
     N = 6 * parents.n
     rc = np.nonzero(refined)[0]
@@ -267,6 +322,12 @@ def _level(scene, parents, width, occupied, margin, abs_int, o, keys, n_levels, 
             queue.append(("e", j))
             j += 1
         queue.extend(("c", t) for t in range(6 * i, 6 * i + 6) if not skip[t])
+    if walk == "device":
+        if not sequential:
+            raise ValueError("the device walk is the sequential walk: sequential = False has no device form")
+        return _device_walk(scene, out, events, n_ev, M, queue, pre_key, post_key, skip, refined, border, occupied, margin, abs_int, o)
+    if walk != "host":
+        raise ValueError(f"walk must be 'host' or 'device', not {walk!r}")
     # The level's conflict graph from ONE hpmvs_level_conflicts_batch over the nodes in queue order (the events and the refined
     # candidates): no footprint and no cell key reaches the host.  _walk only ever intersects one node's reads /
     # writes with other nodes' writes / reads, so every conflicting pair gets ONE token, in both sets it is a member of: ("rw",
@@ -324,16 +385,22 @@ def _level(scene, parents, width, occupied, margin, abs_int, o, keys, n_levels, 
                        {t: post_key[t] for t in accepted} if border is not None else {})
 
 
+def _walk_mode(device_walk) -> str:
+    return "device" if device_walk else "host"
+
+
 def extend_level(scene: api.Scene, parents: api.Batch, width: float, occupied: set, margin: float = 1.0, abs_int: int = 0,
-                 options=None, n_levels: int = 6, key=cell_key, sequential: bool = True) -> LevelResult:
+                 options=None, n_levels: int = 6, key=cell_key, sequential: bool = True, device_walk: bool = False) -> LevelResult:
     """CellProcessor::extend over `parents` (the leaves of one priority level, in the scheduler's order): the walk of the module
     docstring without events.  `occupied` is updated in place; the scene's depth maps receive the accepted candidates.
     sequential = False gives round 3's plain frontier round (every count read from the maps as they are when the level starts):
     one wave, not the reference's result when candidates of a level interact through the maps.
     `n_levels` is kept for existing callers and ignored: the pyramid levels a read can be on are the scene's cameras' (at most
-    HPMVS_MAX_LEVELS, ValueError beyond), so no value given here can hide a read from the walk."""
+    HPMVS_MAX_LEVELS, ValueError beyond), so no value given here can hide a read from the walk.
+    device_walk = True (here and in the other level calls): the waves run inside ONE hpmvs_level_walk_batch instead of `_walk` on
+    the host; the result is the same, field for field."""
     return _level(scene, parents, width, occupied, margin, abs_int, options or api.default_options(), _GridKeys(key, width, occupied),
-                  _pyramid_levels(scene, "extend_level"), sequential)
+                  _pyramid_levels(scene, "extend_level"), sequential, walk=_walk_mode(device_walk))
 
 
 @dataclass
@@ -578,7 +645,7 @@ def filter_level(scene: api.Scene, patches: api.Batch, cell_start, options=None)
 
 
 def filter_extend_level(scene: api.Scene, patches: api.Batch, cell_start, width: float, occupied: set, expanded=None,
-                        margin: float = 1.0, abs_int: int = 0, options=None, key=cell_key):
+                        margin: float = 1.0, abs_int: int = 0, options=None, key=cell_key, device_walk: bool = False):
     """processCell's first visit of a level's unexpanded leaves (reference CellProcessor.cpp:369-392), in queue order: filter
     cell i (:377-378), then CellProcessor::extend on its kept patch.  Returns (FilterResult, LevelResult); the LevelResult is laid
     out as extend_level's, the kept patches being the parents.
@@ -591,10 +658,10 @@ def filter_extend_level(scene: api.Scene, patches: api.Batch, cell_start, width:
     `expanded`: expanded_ per row (default 0).  ValueError before any map update for a cell with no winner, an empty cell or a
     kept patch that is already expanded (processCell does not extend it, :380)."""
     return _filter_extend(scene, patches, cell_start, width, _GridKeys(key, width, occupied), occupied, expanded, margin, abs_int,
-                          options, "filter_extend_level")
+                          options, "filter_extend_level", device_walk)
 
 
-def _filter_extend(scene, patches, cell_start, width, keys, occupied, expanded, margin, abs_int, options, who):
+def _filter_extend(scene, patches, cell_start, width, keys, occupied, expanded, margin, abs_int, options, who, device_walk=False):
     n_levels = _pyramid_levels(scene, who)
     cs = _cell_offsets(patches, cell_start)
     exp = np.zeros(patches.n, np.uint8) if expanded is None else np.ascontiguousarray(expanded).astype(np.uint8).reshape(patches.n)
@@ -606,7 +673,7 @@ def _filter_extend(scene, patches, cell_start, width, keys, occupied, expanded, 
     losers = np.nonzero(F.removed)[0]
     cell_of = np.repeat(np.arange(len(cs) - 1), np.diff(cs))
     L = _level(scene, _rows(patches, F.keep), width, occupied, margin, abs_int, options or api.default_options(), keys, n_levels,
-               events=_rows(patches, losers), event_cell=cell_of[losers])
+               events=_rows(patches, losers), event_cell=cell_of[losers], walk=_walk_mode(device_walk))
     return F, L
 
 
@@ -878,7 +945,8 @@ def _insert_accepted(tree: Octree, L: LevelResult, rows):
 
 
 def extend_level_tree(scene: api.Scene, parents: api.Batch, width: float, tree: Octree, margin: float = 1.0, abs_int: int = 0,
-                      options=None, sequential: bool = True, events=None, event_cell=(), rows=None) -> LevelResult:
+                      options=None, sequential: bool = True, events=None, event_cell=(), rows=None,
+                      device_walk: bool = False) -> LevelResult:
     """extend_level against the scheduler's real octree (or a subtree of it): CellProcessor::extend over `parents`, the leaves
     of ONE node level (all of width `width`), in the scheduler's order.  The walk is extend_level's; the candidates and their keys come
     from ONE hpmvs_extend_tree_batch (_TreeKeys).  Stage codes as extend_level's, where 20 is the pre-gate (a nonempty leaf of any
@@ -889,18 +957,18 @@ def extend_level_tree(scene: api.Scene, parents: api.Batch, width: float, tree: 
     ("extend", candidate) tuple).  events / event_cell: subtraction events as in filter_extend_level."""
     keys = _TreeKeys(scene, tree, width)
     L = _level(scene, parents, width, {REFUSED}, margin, abs_int, options or api.default_options(), keys,
-               _pyramid_levels(scene, "extend_level_tree"), sequential, events, event_cell)
+               _pyramid_levels(scene, "extend_level_tree"), sequential, events, event_cell, _walk_mode(device_walk))
     _insert_accepted(tree, L, rows)
     return L
 
 
 def filter_extend_level_tree(scene: api.Scene, patches: api.Batch, cell_start, width: float, tree: Octree, expanded=None,
-                             margin: float = 1.0, abs_int: int = 0, options=None, rows=None):
+                             margin: float = 1.0, abs_int: int = 0, options=None, rows=None, device_walk: bool = False):
     """filter_extend_level against the real octree: the same walk with extend_level_tree's keys, the filters' losers as events.
     Returns (FilterResult, LevelResult)."""
     keys = _TreeKeys(scene, tree, width)
     F, L = _filter_extend(scene, patches, cell_start, width, keys, {REFUSED}, expanded, margin, abs_int, options,
-                          "filter_extend_level_tree")
+                          "filter_extend_level_tree", device_walk)
     _insert_accepted(tree, L, rows)
     return F, L
 
@@ -966,7 +1034,7 @@ def _insert_accepted_forest(trees, keys: _ForestKeys, L: LevelResult, rows):
 
 
 def extend_level_forest(scene: api.Scene, parents: api.Batch, parent_tree, width: float, trees, margin: float = 1.0,
-                        abs_int: int = 0, options=None, sequential: bool = True, rows=None) -> LevelResult:
+                        abs_int: int = 0, options=None, sequential: bool = True, rows=None, device_walk: bool = False) -> LevelResult:
     """extend_level_tree for ALL subtrees of a partition in one pass: `parents` are the trees' level queues one after the other
     (parent_tree non-decreasing, ValueError otherwise), `trees` a list of Octree such as Partition.trees.  The candidates of
     every tree come from ONE hpmvs_extend_forest_batch (_ForestKeys) and go through ONE walk, whose result over the concatenated
@@ -979,13 +1047,13 @@ def extend_level_forest(scene: api.Scene, parents: api.Batch, parent_tree, width
     if len(keys.parent_tree) != parents.n:
         raise ValueError("extend_level_forest: parent_tree needs one entry per parent")
     L = _level(scene, parents, width, {REFUSED}, margin, abs_int, options or api.default_options(), keys,
-               _pyramid_levels(scene, "extend_level_forest"), sequential)
+               _pyramid_levels(scene, "extend_level_forest"), sequential, walk=_walk_mode(device_walk))
     _insert_accepted_forest(keys.trees, keys, L, rows)
     return L
 
 
 def filter_extend_level_forest(scene: api.Scene, patches: api.Batch, cell_start, cell_tree, width: float, trees, expanded=None,
-                               margin: float = 1.0, abs_int: int = 0, options=None, rows=None):
+                               margin: float = 1.0, abs_int: int = 0, options=None, rows=None, device_walk: bool = False):
     """filter_extend_level_tree for all subtrees in one pass: cell c (rows cell_start[c] .. cell_start[c + 1] - 1 of `patches`)
     is a leaf of trees[cell_tree[c]], cell_tree non-decreasing.  The same walk with extend_level_forest's keys, the filters'
     losers as events.  Returns (FilterResult, LevelResult)."""
@@ -993,7 +1061,7 @@ def filter_extend_level_forest(scene: api.Scene, patches: api.Batch, cell_start,
     if len(keys.parent_tree) != len(np.asarray(cell_start).reshape(-1)) - 1:
         raise ValueError("filter_extend_level_forest: cell_tree needs one entry per cell")
     F, L = _filter_extend(scene, patches, cell_start, width, keys, {REFUSED}, expanded, margin, abs_int, options,
-                          "filter_extend_level_forest")
+                          "filter_extend_level_forest", device_walk)
     _insert_accepted_forest(keys.trees, keys, L, rows)
     return F, L
 

@@ -1337,6 +1337,26 @@ bool Scene::levelConflicts(const Patch3d* const* patches, size_t n, const uint8_
     return device_conflict_graph(*this, patches, n, isEvent, graph.flowOff, graph.flowAdj, graph.antiOff, graph.antiAdj) == 0;
 }
 
+int Scene::levelWalk(const Patch3d* const* items, size_t n, const HpmvsOptions& options, const uint8_t* flags, const int32_t* set,
+                     const uint64_t* preKey, const uint64_t* postKey, float margin, bool absInt, LevelWalk& out) const {
+    hpmvs_scene* dev = deviceScene();
+    if (!dev || out.stage.size() != n) return -1;
+    out.counts.assign(3 * n, -1); out.accepted.assign(n, 0); out.wave.assign(n, 0); out.waves = 0;
+    if (n == 0) return 0;
+    HostBatch hb(items, n);
+    hpmvs_options o;
+    o.MAXLEVEL = options.MAXLEVEL; o.MINLEVEL = options.MINLEVEL; o.MAX_ANGLE = options.MAX_ANGLE; o.MIN_ANGLE = options.MIN_ANGLE;
+    o.MAX_IMAGES_PER_PATCH = options.MAX_IMAGES_PER_PATCH; o.MIN_IMAGES_PER_PATCH = options.MIN_IMAGES_PER_PATCH;
+    o.NCC_ALPHA_1 = options.NCC_ALPHA_1; o.NCC_ALPHA_2 = options.NCC_ALPHA_2;
+    int32_t waves = 0;
+    const int rc = hpmvs_level_walk_batch(dev, &o, &hb.b, flags, set, preKey, postKey, margin, absInt ? 1 : 0, out.stage.data(), out.counts.data(),
+                                          out.accepted.data(), out.wave.data(), &waves, 0, nullptr);
+    if (rc == HPMVS_ERR_STATE) return 1;   // (nothing was written to the maps: the caller walks on the host)
+    if (rc != HPMVS_OK) { std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl; return -1; }
+    out.waves = waves;
+    return 0;
+}
+
 // ---------------------------------------------------------------- PatchOptimizer
 PatchOptimizer::PatchOptimizer(const mo3d::HpmvsOptions& options, const mo3d::Scene* scene)
     : options_p(&options), scene_p(scene) {}
@@ -1975,6 +1995,13 @@ static bool graph_on_device() {
     return on;
 }
 
+// HPMVS_DEVICE_WALK=1: walk_level hands the waves of a level to ONE hpmvs_level_walk_batch instead of walking them
+// here; the result is the same bytes (tests/test_gpu_cpp_level_walk.py).  A lab switch: the default is the host walk.
+static bool walk_on_device() {
+    static const bool on = [] { const char* d = getenv("HPMVS_DEVICE_WALK"); return d && d[0] == '1'; }();
+    return on;
+}
+
 // The deepest pyramid of the scene's cameras: the levels getFullDepth walks, so the levels a read can be on (-1: more than the gates support)
 static int pyramid_levels(const Scene* scene, const char* who) {
     int nLevels = 1;
@@ -2062,25 +2089,70 @@ static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, 
     // and no footprint reaches the host; build_conflict_graph / add_event_edges below are the same graph from the
     // footprints on the host -- the default (graph_on_device), and the fallback when the device refuses the level's size.  The
     // walk only asks whether a list holds a node of this wave, so the order inside a list does not matter.
+    // With walk_on_device() the waves run inside ONE hpmvs_level_walk_batch: the queue goes down as flag bytes, sets
+    // and keys, and neither a graph nor a count comes back.  When the device refuses the level (HPMVS_ERR_STATE: nothing written) the
+    // host walk below runs as always.
+    bool walked = false;
+    double t_device_walk = 0.0;
+    if (sequential && walk_on_device()) {
+        const double w0 = level_now();
+        const size_t m = pending.size();
+        std::vector<const Patch3d*> items(m);
+        std::vector<uint8_t> flags(m, 0);
+        std::vector<int32_t> sets(m, 0);
+        std::vector<uint64_t> pre(m, 0), post(m, 0);
+        Scene::LevelWalk W;
+        W.stage.assign(m, 1);
+        for (size_t i = 0; i < m; i++) {
+            const size_t t = pending[i];
+            if (t >= T) { items[i] = nodes[t - T]; flags[i] = HPMVS_WALK_EVENT; W.stage[i] = 0; continue; }
+            items[i] = &R.candidates[t];
+            sets[i] = (int32_t)setOf(t);
+            uint8_t f = 0;
+            if (preIn[t]) { f |= HPMVS_WALK_HAS_PRE; pre[i] = preKey[t]; if (occ(t).count(preKey[t])) f |= HPMVS_WALK_PRE_TAKEN; }
+            if (refined[t]) {
+                f |= HPMVS_WALK_REFINED;
+                if (border[t]) f |= HPMVS_WALK_BORDER;
+                else { post[i] = postKey[t]; if (occ(t).count(postKey[t])) f |= HPMVS_WALK_POST_TAKEN; }
+            }
+            flags[i] = f;
+        }
+        const int rc = scene->levelWalk(items.data(), m, *options, flags.data(), forest ? sets.data() : nullptr, pre.data(), post.data(), margin,
+                                        absInt, W);
+        if (rc < 0) return false;
+        if (rc == 0) {
+            walked = true;
+            R.waves = W.waves;
+            for (size_t i = 0; i < m; i++) {
+                const size_t t = pending[i];
+                if (t >= T) continue;
+                R.stage[t] = W.stage[i];
+                for (int k = 0; k < 3; k++) R.counts[3 * t + k] = W.counts[3 * i + k];
+                if (W.accepted[i]) { R.accepted.push_back(t); occ(t).insert(postKey[t]); }
+            }
+            pending.clear();
+        }
+        t_device_walk = level_now() - w0;
+    }
     ConflictGraph G;
     bool haveGraph = false;
-    if (sequential && !nodes.empty() && graph_on_device()) {   // (the plain frontier round decides everything in one wave)
+    if (!walked && sequential && !nodes.empty() && graph_on_device()) {   // (the plain frontier round decides everything in one wave)
         const int rc = device_conflict_graph(*scene, nodes.data(), nodes.size(), nEvents ? isEvent.data() : nullptr, G.flow_off, G.flow_adj,
                                              G.anti_off, G.anti_adj);
         if (rc < 0) return false;
         haveGraph = rc == 0;
     }
     RawFootprints F;   // (only the host build reads footprints: none are fetched for the device graph or for the one-wave round)
-    if (!haveGraph && sequential && !raw_footprints(*scene, nodes.data(), nodes.size(), F)) return false;
-    const double t_fp = haveGraph ? t_ref : level_now();   // (on the device the two steps are one call: it is timed as the graph)
-    if (!haveGraph && sequential && F.n > 0) {
+    if (!walked && !haveGraph && sequential && !raw_footprints(*scene, nodes.data(), nodes.size(), F)) return false;
+    const double t_fp = (haveGraph || walked) ? t_ref : level_now();   // (on the device the two steps are one call: it is timed as the graph)
+    if (!walked && !haveGraph && sequential && F.n > 0) {
         int maxW = 1, maxH = 1;
         for (const Image& im : scene->images_) { maxW = std::max(maxW, im.getWidth()); maxH = std::max(maxH, im.getHeight()); }
         if (nEvents) clear_event_reads(F, isEvent);
         build_conflict_graph(F, nLevels, maxW, maxH, G);
         if (nEvents) add_event_edges(F, isEvent, G);
     }
-    const double t_graph = level_now();
+    const double t_graph = walked ? t_fp : level_now();   // (the device walk made its graph inside the call: timed under "walk")
     const int MIN = options->MIN_IMAGES_PER_PATCH;
     // open[i] == w: node i was accepted, applied or deferred in wave w -- its writes are not in the maps this wave's counts were read
     // from (`dirty`); defer_w[i] == w: it was deferred in wave w -- nobody may overwrite what it reads, no addition may overtake its
@@ -2096,7 +2168,7 @@ static bool walk_level(const char* who, PatchOptimizer& po, const Scene* scene, 
         for (uint32_t q = G.anti_off[i]; q < G.anti_off[i + 1]; q++) if (defer_w[G.anti_adj[q]] == wave) return true;
         return false;
     };
-    double t_gates = 0.0, t_walk = 0.0, t_set = 0.0;
+    double t_gates = 0.0, t_walk = walked ? t_device_walk : 0.0, t_set = 0.0;   // (the device walk: "walk" carries the whole call)
     while (!pending.empty()) {
         R.waves++;
         double w0 = level_now();

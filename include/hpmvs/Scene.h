@@ -225,6 +225,18 @@ public:
         std::vector<uint32_t> flowOff, flowAdj, antiOff, antiAdj;
     };
     bool levelConflicts(const Patch3d* const* patches, size_t n, const uint8_t* isEvent, LevelGraph& graph) const;
+    // The wave walk of one extend level as ONE batched GPU call (hpmvs_level_walk_batch, include/hpmvs_amd.h):
+    // items are the level's queue in the reference's order (an event's patch, a candidate's patch), flags the HPMVS_WALK_* bits,
+    // set (nullptr: one set) the tree each candidate's keys belong to, preKey / postKey its leaf before and after refinement.
+    // out.stage must hold the n preset stages.  Returns 0, 1 when the device refuses the level (HPMVS_ERR_STATE: no map was
+    // written, walk on the host), -1 for any other failure (reported).  PatchOptimizer's levels use it with HPMVS_DEVICE_WALK=1.
+    struct LevelWalk {
+        std::vector<int32_t> stage, counts, wave;   // [n] in / out, [n][3], [n] the 1-based wave that decided the item
+        std::vector<uint8_t> accepted;              // [n]
+        int waves = 0;
+    };
+    int levelWalk(const Patch3d* const* items, size_t n, const HpmvsOptions& options, const uint8_t* flags, const int32_t* set,
+                  const uint64_t* preKey, const uint64_t* postKey, float margin, bool absInt, LevelWalk& out) const;
     // The scheduler's octree as CellProcessor::extend consults it (CellProcessor.cpp:122-125, 147-154), for a list of points as
     // ONE batched GPU call (hpmvs_octree_locate_batch): root->at(p), getRoot()->contains(p) and the leaf
     // DynOctTree::addConditional(p, addWidth) would put p in.  OctreeIndex names the tree by path keys (sentinel bit, 3 bits per

@@ -415,6 +415,45 @@ int hpmvs_conflicts_from_footprints(int device, int n, int max_images, int n_vie
                                     const uint8_t *is_event, uint32_t *flow_off, uint32_t *flow_adj, size_t cap_flow,
                                     uint32_t *anti_off, uint32_t *anti_adj, size_t cap_anti, uint32_t *n_flow, uint32_t *n_anti,
                                     int on_device, void *stream);
+/* The WAVE WALK of one extend level -- what strings the candidates, the graph, the gates and the ordered depth update into the
+ * result of CellProcessor::extend run over the level's leaves one after the other -- as ONE call, entirely on the device
+ * (hpmvs_amd/csrc/level_walk.hpp states the rule and has the host restatement; INTEGRATION.md has the recipe).
+ * `items`: the level's queue, n rows in the reference's order -- a subtraction event's patch (the patches CellProcessor::filter
+ * removed from a cell, right before that cell's candidates), a candidate's refined patch; the rows of candidates that were not
+ * refined are not read.  flags[i]: HPMVS_WALK_EVENT, or for a candidate any of HPMVS_WALK_REFINED (it was refined: stage 0 of the
+ * candidate call, and not skipped), _BORDER (refined and outside its tree's root), _HAS_PRE (pre_key[i] is a leaf: the pre_inside of
+ * the candidate calls; the grid always), _PRE_TAKEN / _POST_TAKEN (that leaf is nonempty, or refused, when the level starts).
+ * set[i] (NULL: one set): the tree the keys of candidate i belong to -- keys are equal only within one set; >= 0.  pre_key /
+ * post_key: the leaf of the candidate before and after refinement (post_key is read for a refined candidate that is not border).
+ * stage (in / out): preset to each candidate's refinement result, an accepted candidate's becomes 0, a rejected one's 20 (its
+ * leaf was taken), 23 / 24 / 25 (depthTests / viewBlockTest / pixelFreeTests), 26 (the refined patch's leaf was taken) or 27
+ * (border: every gate passed, handed to the scheduler); an event's is not written.  counts [n][3]: the three counts at decision
+ * time, -1 where never counted.  accepted[i]: 1 for an accepted candidate, whose depths are in the maps on return, as the
+ * subtractions of every event are.  wave[i]: the wave (1-based) that decided item i; *n_waves (a HOST word in both forms): their
+ * number -- the items still deferred after wave w are those with wave[i] > w.
+ * Inside: the conflict graph over the events and the refined candidates by the device code of hpmvs_level_conflicts_batch; the
+ * candidates' key records, sorted once; then per wave the gates over the pending refined candidates against the maps as they stand,
+ * resolve ROUNDS -- an item decides once no earlier item it shares a map cell or a leaf key with, and that can still change its
+ * outcome, is undecided; the last few of a wave are decided by one wavefront in order -- and one ordered depth update (the kernels of
+ * hpmvs_set_depths_batch when the wave holds additions only, else those of hpmvs_depth_ops_batch).  Rounds and waves are kernel
+ * launches; the host reads a count after each and takes no decision.
+ * HPMVS_ERR_ARG before any output byte or map cell is written: null arrays, max_images outside 1 .. HPMVS_MAX_IMAGES, a flag byte
+ * that cannot occur (an event that is refined or border, a bit that is none of the above), a negative set, and whatever
+ * hpmvs_level_conflicts_batch refuses.  HPMVS_ERR_STATE before any map write: a scene without depth maps (or with 2^32 cells or
+ * more), the graph's 2^30-pair refusal -- the caller then walks on the host.  n == 0, only events and only unrefined candidates are
+ * valid.  Host-synchronous in both pointer forms.  hpmvs_last_level_walk: the rounds of the last call on this scene, the most
+ * rounds of one wave and the in-order passes (any may be NULL). */
+#define HPMVS_WALK_EVENT 1
+#define HPMVS_WALK_REFINED 2
+#define HPMVS_WALK_BORDER 4
+#define HPMVS_WALK_HAS_PRE 8
+#define HPMVS_WALK_PRE_TAKEN 16
+#define HPMVS_WALK_POST_TAKEN 32
+int hpmvs_level_walk_batch(hpmvs_scene *s, const hpmvs_options *o, const hpmvs_patch_batch *items, const uint8_t *flags,
+                           const int32_t *set, const uint64_t *pre_key, const uint64_t *post_key, float margin, int abs_int,
+                           int32_t *stage, int32_t *counts, uint8_t *accepted, int32_t *wave, int32_t *n_waves, int on_device,
+                           void *stream);
+int hpmvs_last_level_walk(const hpmvs_scene *s, int32_t *rounds, int32_t *most_rounds, int32_t *in_order_passes);
 
 /* ---- CellProcessor::regularize for a priority level (src/hpmvs/CellProcessor.cpp:309-367, processCell :369-420) ----------------
  * The octree stays the scheduler's.  For each call it passes a VERSIONED snapshot of the nonempty leaves: a leaf is part of the

@@ -146,14 +146,18 @@ class DeviceForm:
         return b"".join(v.cpu().numpy().tobytes() for v in list(self.out.values()) + list(self.keys.values()))
 
 
-def cpp_levels(scene, F):
-    """(c): tests/native/bench_extend_level_forest on the same parents; -> its JSON line and the HPMVS_LEVEL_TIMES lines."""
+def cpp_build():
+    """tests/native/bench_extend_level_forest, built here -> its path"""
     exe = os.path.join(ROOT, "tests", "native", "bench_extend_level_forest")
     inc, lib = os.path.join(ROOT, "include"), os.path.join(ROOT, "hpmvs_amd")
     subprocess.run(["g++", "-O2", "-std=c++14", "-I" + inc, exe + ".cpp", "-o", exe, "-L" + lib, "-lhpmvs_host", "-lhpmvs_amd",
                     "-Wl,-rpath," + lib], check=True)
+    return exe
+
+
+def cpp_dump(scene, F, dump):
+    """The scene, the parents and the forest as bench_extend_level_forest reads them."""
     P = F.P
-    dump = os.path.join(os.environ.get("TMPDIR", "/tmp"), "extend_forest_scene.bin")
     with open(dump, "wb") as f:
         f.write(struct.pack("i", scene.n_views))
         for v in scene.views:
@@ -171,10 +175,11 @@ def cpp_levels(scene, F):
         for k in range(F.n_trees):
             bk, lk = F.keys_of(k)
             f.write(F.roots[k].tobytes() + struct.pack("i", len(bk)) + bk.tobytes() + struct.pack("i", len(lk)) + lk.tobytes())
-    try:
-        r = subprocess.run([exe, dump], capture_output=True, text=True, env=dict(os.environ, HPMVS_LEVEL_TIMES="1"))
-    finally:
-        os.remove(dump)
+
+
+def cpp_run(exe, dump):
+    """One run of bench_extend_level_forest on a dump, with the environment as it stands -> its JSON line and the HPMVS_LEVEL_TIMES lines."""
+    r = subprocess.run([exe, dump], capture_output=True, text=True, env=dict(os.environ, HPMVS_LEVEL_TIMES="1"))
     if r.returncode != 0:
         raise SystemExit(f"bench_extend_level_forest failed: {r.stdout}\n{r.stderr}")
     rec = json.loads(r.stdout.strip().splitlines()[-1])
@@ -186,6 +191,17 @@ def cpp_levels(scene, F):
     rec["level_times"] = {"extendLevelForest": [l for l in lines if l.startswith("extendLevelForest ")][-1:],
                           "extendLevelTree_largest": sorted(loop, key=lambda l: -int(l.split()[1]))[:3], "extendLevelTree_lines": len(loop)}
     return rec
+
+
+def cpp_levels(scene, F):
+    """(c): tests/native/bench_extend_level_forest on the same parents; -> its JSON line and the HPMVS_LEVEL_TIMES lines."""
+    exe = cpp_build()
+    dump = os.path.join(os.environ.get("TMPDIR", "/tmp"), "extend_forest_scene.bin")
+    cpp_dump(scene, F, dump)
+    try:
+        return cpp_run(exe, dump)
+    finally:
+        os.remove(dump)
 
 
 def main(argv):
