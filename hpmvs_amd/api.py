@@ -106,6 +106,7 @@ EXPORTS = [
     "hpmvs_jpeg_info", "hpmvs_jpeg_decode", "hpmvs_scene_set_view_jpeg", "hpmvs_jpeg_decode_timed",
     "hpmvs_jpeg_decode_ex", "hpmvs_scene_set_view_jpeg_ex", "hpmvs_jpeg_coefficients", "hpmvs_jpeg_entropy_timed",
     "hpmvs_jpeg_last_decode",
+    "hpmvs_jpeg_encode_bound", "hpmvs_jpeg_encode", "hpmvs_jpeg_encode_timed", "hpmvs_scene_get_level_jpeg",
 ]
 JPEG_ENTROPY = {"auto": 0, "host": 1, "device": 2}   # HPMVS_JPEG_ENTROPY_AUTO / _HOST / _DEVICE
 
@@ -151,6 +152,12 @@ def lib():
                                           C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.hpmvs_jpeg_last_decode.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.hpmvs_jpeg_entropy_timed.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_float)]
+    L.hpmvs_jpeg_encode_bound.restype = C.c_size_t
+    L.hpmvs_jpeg_encode_bound.argtypes = [C.c_int, C.c_int]
+    L.hpmvs_jpeg_encode.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
+    L.hpmvs_jpeg_encode_timed.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                          C.POINTER(C.c_float)]
+    L.hpmvs_scene_get_level_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.hpmvs_optimize_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(PatchBatch), C.c_int, C.c_void_p]
     L.hpmvs_init_patches_batch.argtypes = [C.c_void_p, C.POINTER(Options), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.POINTER(PatchBatch), C.c_int, C.c_void_p]
@@ -341,6 +348,31 @@ def jpeg_coefficients(data, entropy: str = "auto", subseq_bits: int = 0, device:
     return out, "device" if used.value == 2 else "host", rounds.value
 
 
+def jpeg_encode_bound(width: int, height: int) -> int:
+    """Upper bound in bytes of jpeg_encode's file for a width x height image, at any quality."""
+    return int(lib().hpmvs_jpeg_encode_bound(int(width), int(height)))
+
+
+def jpeg_encode(rgb, quality: int = 100, device: int = 0) -> bytes:
+    """uint8 [H, W, 3] pixels (a numpy array, or a torch tensor on the device, which is read in place) -> the baseline JPEG file
+    libjpeg writes for them with its defaults at `quality` (YCbCr 4:2:0, the standard Huffman tables), byte for byte; colour
+    conversion, DCT, Huffman coding and byte stuffing run on the GPU.  Raises for a quality outside 1 .. 100 or a side above
+    65535 (HPMVS_ERR_ARG = -2) and for a side under 8 pixels (HPMVS_ERR_UNSUPPORTED = -5)."""
+    if isinstance(rgb, np.ndarray):
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+        ptr, on_device = rgb.ctypes.data, 0
+    else:
+        rgb = rgb.contiguous()
+        ptr, on_device = rgb.data_ptr(), 1
+    if rgb.ndim != 3 or rgb.shape[2] != 3 or (on_device and rgb.dtype != torch.uint8):
+        raise HpmvsError("jpeg_encode: pixels must be uint8 [H, W, 3]")
+    h, w = int(rgb.shape[0]), int(rgb.shape[1])
+    out = np.empty(max(1, jpeg_encode_bound(w, h)), dtype=np.uint8)
+    n = C.c_size_t(0)
+    _chk(lib().hpmvs_jpeg_encode(device, ptr, w, h, int(quality), out.ctypes.data, out.nbytes, C.byref(n), on_device))
+    return out[:n.value].tobytes()
+
+
 class Scene:
     """HBM-resident scene: Scene::addCameras + extractCoVisiblilty state the path reads
     (reference include/hpmvs/Scene.h:69-71)."""
@@ -409,6 +441,15 @@ class Scene:
         out = np.empty((h.value, w.value, 3), dtype=np.uint8)
         _chk(lib().hpmvs_scene_get_level(self.h, view, level, out.ctypes.data, out.nbytes, C.byref(w), C.byref(h)))
         return out
+
+    def level_jpeg(self, view: int, level: int = 0, quality: int = 100) -> bytes:
+        """The level as the baseline JPEG file jpeg_encode writes for its pixels, encoded where it lies in HBM (level 0 of a view
+        with k1 != 0: the undistorted pixels)."""
+        n = C.c_size_t(0)
+        _chk(lib().hpmvs_scene_get_level_jpeg(self.h, view, level, int(quality), None, 0, C.byref(n)))
+        out = np.empty(n.value, dtype=np.uint8)
+        _chk(lib().hpmvs_scene_get_level_jpeg(self.h, view, level, int(quality), out.ctypes.data, out.nbytes, C.byref(n)))
+        return out[:n.value].tobytes()
 
     def last_staging(self):
         """(bytes copied through device buffers, bytes used in place) of the last host-pointer optimize_batch call."""

@@ -816,6 +816,142 @@ int hpmvs_jpeg_entropy_timed(int device, const uint8_t* bytes, size_t n, uint8_t
     return jpeg_frame_to_device(jd, rgb_device, ms + 7);
 }
 
+// ---- baseline JPEG encode (jpeg_enc.hpp, kernel_jpeg_encode.hip): everything between the pixels and the stuffed entropy data
+// runs on the device; the host puts the header in front and EOI behind
+static int jpeg_enc_fail(int code, const std::string& msg) { return fail(code == jpge::kErrUnsupported ? HPMVS_ERR_UNSUPPORTED : HPMVS_ERR_ARG, msg); }
+
+size_t hpmvs_jpeg_encode_bound(int width, int height) {
+    if (width < 1 || height < 1 || width > jpge::kMaxSide || height > jpge::kMaxSide) return 0;
+    return jpge::encode_bound(width, height);
+}
+
+// d_rgb: interleaved u8 [H][W][3] on the current device -> the whole file at the host address `out`, on the null stream.  *n is
+// the file's length, also when cap is too small (HPMVS_ERR_ARG; nothing is written to `out` then).  The two working buffers
+// live for this call only.  The first is sized from the image: tables, coefficients, the blocks' lengths and offsets.  The
+// second is sized from the stream's length once the scan has given it, which jpeg_enc.hpp's bound (208 bytes per block,
+// every byte stuffed) limits: the stream, its chunks' counts and offsets, and the stuffed bytes at twice the stream's length.
+// ms (diagnostics, nullable): by HIP events [0] the first buffer and the tables' upload, [1] coefficient kernel, [2] lengths and their scan
+// with the total's read-back, [3] the second buffer and its fills, [4] write kernel, [5] 0xFF counts and their scan with the
+// total's read-back, [6] stuff kernel, [7] the bytes' copy to the host.
+static int jpeg_encode_device(const uint8_t* d_rgb, int W, int H, int quality, uint8_t* out, size_t cap, size_t* n, float* ms = nullptr) {
+    const jpge::Geom g = jpge::make_geom(W, H);
+    jpge::EncTables T;
+    jpge::make_tables(quality, &T);
+    const size_t nb = g.n_blocks;
+    uint8_t *work = nullptr, *work2 = nullptr;
+    struct Free { uint8_t*& a; uint8_t*& b; ~Free() { if (a) hipFree(a); if (b) hipFree(b); } } free_on_exit{work, work2};
+    hipEvent_t ev[9] = {};
+    struct Events { hipEvent_t* e; ~Events() { for (int k = 0; k < 9; k++) if (e[k]) hipEventDestroy(e[k]); } } events{ev};
+    if (ms)
+        for (int k = 0; k < 9; k++) HIPCHK(hipEventCreate(&ev[k]));
+    auto mark = [&](int k) { return ms ? hipEventRecord(ev[k], nullptr) : hipSuccess; };
+    size_t scan_bytes = 0;
+    HIPCHK((hipError_t)jpeg_enc_scan(nullptr, &scan_bytes, nullptr, nullptr, nb + 1, nullptr));
+    size_t total = 0;
+    auto take = [&total](size_t nbytes) { const size_t at = total; total += reg_align(nbytes); return at; };
+    const size_t o_tabs = take(sizeof(T)), o_coef = take(nb * 64 * sizeof(int16_t)), o_lens = take((nb + 1) * 8), o_offs = take((nb + 1) * 8),
+                 o_temp = take(scan_bytes);
+    HIPCHK(mark(0));
+    HIPCHK(hipMalloc((void**)&work, total));
+    const jpge::EncTables* d_tabs = (const jpge::EncTables*)(work + o_tabs);
+    int16_t* d_coef = (int16_t*)(work + o_coef);
+    unsigned long long *d_lens = (unsigned long long*)(work + o_lens), *d_offs = (unsigned long long*)(work + o_offs);
+    HIPCHK(hipMemcpy(work + o_tabs, &T, sizeof(T), hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(d_lens + nb, 0, 8, nullptr));
+    HIPCHK(mark(1));
+    launch_jpeg_enc_coef(d_rgb, g, d_tabs, d_coef, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(mark(2));
+    launch_jpeg_enc_lengths(d_coef, g.n_blocks, d_tabs, d_lens, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK((hipError_t)jpeg_enc_scan(work + o_temp, &scan_bytes, d_lens, d_offs, nb + 1, nullptr));
+    unsigned long long bits = 0;
+    HIPCHK(hipMemcpy(&bits, d_offs + nb, 8, hipMemcpyDeviceToHost));
+    HIPCHK(mark(3));
+    if (bits == 0 || bits > (unsigned long long)nb * jpge::kBlockBoundBytes * 8) return fail(HPMVS_ERR_HIP, "jpeg_encode: the blocks' lengths are none the encoder produces");
+    const unsigned long long n_bytes = (bits + 7) / 8, n_chunks = (n_bytes + 63) / 64;
+    size_t scan2_bytes = 0;
+    HIPCHK((hipError_t)jpeg_enc_scan(nullptr, &scan2_bytes, nullptr, nullptr, (size_t)n_chunks + 1, nullptr));
+    total = 0;
+    const size_t o_stream = take((size_t)n_chunks * 64), o_cnt = take(((size_t)n_chunks + 1) * 8), o_moved = take(((size_t)n_chunks + 1) * 8),
+                 o_temp2 = take(scan2_bytes), o_out = take((size_t)n_bytes * 2);
+    HIPCHK(hipMalloc((void**)&work2, total));
+    unsigned long long *d_cnt = (unsigned long long*)(work2 + o_cnt), *d_moved = (unsigned long long*)(work2 + o_moved);
+    HIPCHK(hipMemsetAsync(work2 + o_stream, 0, (size_t)n_chunks * 64, nullptr));
+    HIPCHK(hipMemsetAsync(d_cnt + n_chunks, 0, 8, nullptr));
+    HIPCHK(mark(4));
+    launch_jpeg_enc_write(d_coef, g.n_blocks, d_tabs, d_offs, (uint32_t*)(work2 + o_stream), nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(mark(5));
+    launch_jpeg_enc_ff(work2 + o_stream, n_chunks, d_cnt, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK((hipError_t)jpeg_enc_scan(work2 + o_temp2, &scan2_bytes, d_cnt, d_moved, (size_t)n_chunks + 1, nullptr));
+    unsigned long long n_ff = 0;
+    HIPCHK(hipMemcpy(&n_ff, d_moved + n_chunks, 8, hipMemcpyDeviceToHost));
+    HIPCHK(mark(6));
+    if (n_ff > n_bytes) return fail(HPMVS_ERR_HIP, "jpeg_encode: more stuffed bytes than bytes");
+    const size_t n_data = (size_t)(n_bytes + n_ff);
+    *n = jpge::kHeaderBytes + n_data + 2;
+    if (cap < *n) return fail(HPMVS_ERR_ARG, "jpeg_encode: output buffer too small (" + std::to_string(*n) + " bytes needed)");
+    launch_jpeg_enc_stuff(work2 + o_stream, n_chunks, n_bytes, d_moved, work2 + o_out, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(mark(7));
+    HIPCHK(hipMemcpy(out + jpge::kHeaderBytes, work2 + o_out, n_data, hipMemcpyDeviceToHost));
+    HIPCHK(mark(8));
+    jpge::write_header(W, H, quality, out);
+    out[jpge::kHeaderBytes + n_data] = 0xFF;
+    out[jpge::kHeaderBytes + n_data + 1] = 0xD9;
+    if (ms) {
+        HIPCHK(hipEventSynchronize(ev[8]));
+        for (int k = 0; k < 8; k++) HIPCHK(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+    }
+    return HPMVS_OK;
+}
+
+static int jpeg_encode_impl(int device, const uint8_t* rgb, int width, int height, int quality, uint8_t* out, size_t cap, size_t* n,
+                            int rgb_on_device, float* ms) {
+    if (!rgb || !out || !n) return fail(HPMVS_ERR_ARG, "jpeg_encode: null argument");
+    std::string err;
+    const int rc = jpge::check_args(width, height, quality, &err);
+    if (rc != jpge::kOk) return jpeg_enc_fail(rc, err);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(HPMVS_ERR_NODEVICE, "no HIP device visible");
+    if (device < 0 || device >= ndev) return fail(HPMVS_ERR_ARG, "jpeg_encode: bad device index");
+    HIPCHK(hipSetDevice(device));
+    if (rgb_on_device) return jpeg_encode_device(rgb, width, height, quality, out, cap, n, ms);
+    const size_t nb = (size_t)3 * width * height;
+    uint8_t* d_rgb = nullptr;
+    struct Free { uint8_t*& a; ~Free() { if (a) hipFree(a); } } free_on_exit{d_rgb};
+    HIPCHK(hipMalloc((void**)&d_rgb, nb));
+    HIPCHK(hipMemcpy(d_rgb, rgb, nb, hipMemcpyHostToDevice));
+    return jpeg_encode_device(d_rgb, width, height, quality, out, cap, n, ms);
+}
+
+int hpmvs_jpeg_encode(int device, const uint8_t* rgb, int width, int height, int quality, uint8_t* out, size_t cap, size_t* n, int rgb_on_device) {
+    return jpeg_encode_impl(device, rgb, width, height, quality, out, cap, n, rgb_on_device, nullptr);
+}
+
+int hpmvs_jpeg_encode_timed(int device, const uint8_t* rgb_device, int width, int height, int quality, uint8_t* out, size_t cap, size_t* n, float* ms) {
+    if (!ms) return fail(HPMVS_ERR_ARG, "jpeg_encode_timed: null argument");
+    return jpeg_encode_impl(device, rgb_device, width, height, quality, out, cap, n, 1, ms);
+}
+
+int hpmvs_scene_get_level_jpeg(const hpmvs_scene* s, int view, int level, int quality, uint8_t* out, size_t cap, size_t* n) {
+    if (!s || !n) return fail(HPMVS_ERR_ARG, "scene_get_level_jpeg: null argument");
+    if (view < 0 || view >= s->n_views || !s->view_set[view]) return fail(HPMVS_ERR_ARG, "scene_get_level_jpeg: bad view");
+    const DevView& V = s->hviews[view];
+    if (level < 0 || level >= V.n_levels) return fail(HPMVS_ERR_ARG, "scene_get_level_jpeg: bad level");
+    std::string err;
+    const int rc = jpge::check_args(V.w[level], V.h[level], quality, &err);
+    if (rc != jpge::kOk) return jpeg_enc_fail(rc, err);
+    if (!out) {
+        *n = jpge::encode_bound(V.w[level], V.h[level]);
+        return HPMVS_OK;
+    }
+    HIPCHK(hipSetDevice(s->device));
+    return jpeg_encode_device(V.pix[level], V.w[level], V.h[level], quality, out, cap, n);
+}
+
 static int scene_set_view_jpeg_impl(hpmvs_scene* s, int view, const uint8_t* bytes, size_t n, const hpmvs_camera* cam, float f, float k1,
                                     int entropy, bool strict, int* used) {
     if (!s || !bytes || !cam) return fail(HPMVS_ERR_ARG, "scene_set_view_jpeg: null argument");

@@ -8,6 +8,7 @@
 #include "level_walk.hpp"
 #include "dev_types.h"
 #include "jpeg.hpp"
+#include "jpeg_enc.hpp"
 #include "octree.hpp"
 #include "seed_tree.hpp"
 
@@ -345,6 +346,22 @@ void launch_jpeg_entropy_sync(const JpegEntropy& A, int pass, int budget, hipStr
 // ev (diagnostics, nullable): five events recorded in front of, between and behind the four kernels; -> the first event
 // call's error, if any (launch errors: hipGetLastError, as for every launcher here)
 hipError_t launch_jpeg_entropy_finish(const JpegEntropy& A, int16_t* coef, hipStream_t st, hipEvent_t* ev = nullptr);
+
+// baseline JPEG encode of interleaved u8 RGB in HBM (kernel_jpeg_encode.hip, jpeg_enc.hpp, include/hpmvs_amd.h: hpmvs_jpeg_encode).
+// coef: [n_blocks][64] int16 in zigzag order, MCU scan order (Y00 Y01 Y10 Y11 Cb Cr); tabs: device copy of make_tables'.
+void launch_jpeg_enc_coef(const uint8_t* rgb, const jpge::Geom& g, const jpge::EncTables* tabs, int16_t* coef, hipStream_t st);
+// lens: [n_blocks + 1] bits of every block's code; the caller zeroes the last entry
+void launch_jpeg_enc_lengths(const int16_t* coef, uint32_t n_blocks, const jpge::EncTables* tabs, unsigned long long* lens, hipStream_t st);
+// rocPRIM's exclusive sum over n 64-bit entries; temp == nullptr: only reports the temporary bytes it needs.  -> hipError_t
+int jpeg_enc_scan(void* temp, size_t* temp_bytes, const unsigned long long* in, unsigned long long* out, size_t n, hipStream_t st);
+// offs: the scan of lens; stream: zero-filled, ceil(offs[n_blocks] / 8) bytes rounded up to a multiple of 64
+void launch_jpeg_enc_write(const int16_t* coef, uint32_t n_blocks, const jpge::EncTables* tabs, const unsigned long long* offs, uint32_t* stream,
+                           hipStream_t st);
+// cnt: [n_chunks + 1] 0xFF bytes per 64-byte chunk of the stream; the caller zeroes the last entry
+void launch_jpeg_enc_ff(const uint8_t* stream, unsigned long long n_chunks, unsigned long long* cnt, hipStream_t st);
+// moved: the scan of cnt; out: n_bytes + moved[n_chunks] bytes, the stream with a 0x00 behind every 0xFF
+void launch_jpeg_enc_stuff(const uint8_t* stream, unsigned long long n_chunks, unsigned long long n_bytes, const unsigned long long* moved, uint8_t* out,
+                           hipStream_t st);
 
 // refined-patch records of the multi-GPU exchange (include/hpmvs_amd.h: hpmvs_record, 192 bytes)
 void launch_pack_records(const DevBatch& b, void* records, hipStream_t st);

@@ -11,6 +11,7 @@
 #include <iomanip>
 #include <iostream>
 #include <strings.h>
+#include <sys/stat.h>
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -238,6 +239,19 @@ const std::vector<uint8_t>& Image::pixels() const {
     }
     return rgb_;
 }
+bool Image::saveJpeg(const char* path, int quality) const {
+    const std::vector<uint8_t>& px = pixels();
+    if (px.empty()) { std::cerr << "hpmvs: saveJpeg: the image holds no pixels" << std::endl; return false; }
+    std::vector<uint8_t> file(hpmvs_jpeg_encode_bound(width_, height_));
+    size_t n = 0;
+    if (hpmvs_jpeg_encode(0, px.data(), width_, height_, quality, file.data(), file.size(), &n, 0) != HPMVS_OK) {
+        std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl;
+        return false;
+    }
+    std::ofstream out(path, std::ios::binary);
+    out.write((const char*)file.data(), (std::streamsize)n);
+    return out.good();
+}
 void Image::setRawPixels(int width, int height, const uint8_t* rgb) {
     setPixels(width, height, rgb);
     raw_ = true;
@@ -438,6 +452,94 @@ void* Scene::combiner() const {
 Scene::~Scene() {
     if (dev_) hpmvs_scene_destroy(dev_);
     delete (Combiner*)combiner_;
+}
+
+// ---------------------------------------------------------------- Scene::saveAsNVM (reference src/hpmvs/Scene.cpp:646-713)
+// rotation matrix (rows m[0..2]) -> unit quaternion <wxyz>: the standard conversion by the largest of the trace and the
+// diagonal entries, as Eigen::Quaterniond(Matrix3d) does it, normalised behind it
+static void matrix_to_quaternion(const double m[3][3], double q[4]) {
+    double t = m[0][0] + m[1][1] + m[2][2];
+    if (t > 0.0) {
+        t = std::sqrt(t + 1.0);
+        q[0] = 0.5 * t;
+        t = 0.5 / t;
+        q[1] = (m[2][1] - m[1][2]) * t;
+        q[2] = (m[0][2] - m[2][0]) * t;
+        q[3] = (m[1][0] - m[0][1]) * t;
+    } else {
+        int i = 0;
+        if (m[1][1] > m[0][0]) i = 1;
+        if (m[2][2] > m[i][i]) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        t = std::sqrt(m[i][i] - m[j][j] - m[k][k] + 1.0);
+        q[1 + i] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (m[k][j] - m[j][k]) * t;
+        q[1 + j] = (m[j][i] + m[i][j]) * t;
+        q[1 + k] = (m[k][i] + m[i][k]) * t;
+    }
+    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    for (int c = 0; c < 4; c++) q[c] /= n;
+}
+
+static bool make_folder(const std::string& path) {
+    struct stat st;
+    if (stat(path.c_str(), &st) == 0) return S_ISDIR(st.st_mode);
+    return mkdir(path.c_str(), 0777) == 0;
+}
+
+bool Scene::saveAsNVM(const char* folder, const std::vector<Ppatch3d>& patches) const {
+    const std::string root(folder), imgs = root + "/imgs";
+    if (!make_folder(root) || !make_folder(imgs)) { std::cerr << "hpmvs: saveAsNVM: cannot create <" << imgs << ">" << std::endl; return false; }
+    hpmvs_scene* dev = deviceScene();
+    if (!dev) return false;
+    std::vector<NVM_Model> models(1);
+    std::vector<uint8_t> file;
+    for (size_t ii = 0; ii < images_.size(); ii++) {
+        size_t n = 0;
+        if (hpmvs_scene_get_level_jpeg(dev, (int)ii, 0, 100, nullptr, 0, &n) != HPMVS_OK) { std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl; return false; }
+        file.resize(n);
+        if (hpmvs_scene_get_level_jpeg(dev, (int)ii, 0, 100, file.data(), file.size(), &n) != HPMVS_OK) { std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl; return false; }
+        const std::string name = "imgs/" + std::to_string(ii) + ".jpg";
+        std::ofstream out((root + "/" + name).c_str(), std::ios::binary);
+        out.write((const char*)file.data(), (std::streamsize)n);
+        if (!out.good()) { std::cerr << "hpmvs: saveAsNVM: cannot write <" << root << "/" << name << ">" << std::endl; return false; }
+        const Camera& c = cameras_[ii];
+        NVM_Camera cam;
+        cam.filename = name;
+        cam.f = c.kMat_[0](0, 0);
+        for (int k = 0; k < 3; k++) cam.c[k] = (double)c.center_[k] / (double)c.center_[3];
+        cam.r = 0;
+        const Eigen::Vector3f ax[3] = {c.xAxis_.normalized(), c.yAxis_.normalized(), c.zAxis_.normalized()};
+        double m[3][3], q[4];
+        for (int r = 0; r < 3; r++)
+            for (int k = 0; k < 3; k++) m[r][k] = (double)ax[r][k];
+        matrix_to_quaternion(m, q);
+        for (int k = 0; k < 4; k++) cam.rq[k] = q[k];
+        models.back().cameras.push_back(cam);
+    }
+    for (const Ppatch3d& p : patches) {
+        NVM_Point np;
+        for (int k = 0; k < 3; k++) {
+            np.rgb[k] = (double)p->color_[k];
+            np.xyz[k] = (double)p->center_[k] / (double)p->center_[3];
+        }
+        for (int id : p->images_) {
+            if (id < 0 || id >= (int)cameras_.size()) { std::cerr << "hpmvs: saveAsNVM: a patch names image " << id << std::endl; return false; }
+            NVM_Measurement me;
+            me.featIndex = 0;
+            me.imgIndex = id;
+            const Eigen::Vector3f xy = cameras_[id].project(p->center_, 0);
+            me.xy[0] = (double)xy[0];
+            me.xy[1] = (double)xy[1];
+            np.measurements.push_back(me);
+        }
+        models.back().points.push_back(np);
+    }
+    models.emplace_back();
+    const std::string nvm = root + "/project.nvm";
+    NVMReader::saveNVM(nvm.c_str(), models);
+    return std::ifstream(nvm.c_str()).good();
 }
 
 bool Scene::addCameras(const NVM_Model& model, const HpmvsOptions& options) {

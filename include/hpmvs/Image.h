@@ -37,6 +37,10 @@ public:
     int levels() const { return maxLevel_ + 1; }
     // level-0 pixels; of a JPEG image they are decoded on first use (hpmvs_jpeg_decode on device 0; empty when that fails)
     const std::vector<uint8_t>& pixels() const;
+    // the pixels the image holds (pixels()) as the baseline JPEG file the reference's CImg save writes through libjpeg's
+    // defaults, byte for byte (hpmvs_jpeg_encode on device 0: YCbCr 4:2:0, standard Huffman tables; CImg's quality is 100).
+    // False, with the reason on stderr, for an image without pixels, a refused size or quality, or a file that cannot be written.
+    bool saveJpeg(const char* path, int quality = 100) const;
 private:
     mutable std::vector<uint8_t> rgb_;
     std::vector<uint8_t> jpeg_;  // the file, when the view is a JPEG

@@ -280,6 +280,15 @@ public:
     // subtree (nOrphans) are reference behaviour: they stay in the tree, nothing extends them.  False (and
     // hpmvs_last_error) when the keys are no tree, minTrees > HPMVS_MAX_SUBTREES or minSplitLeaves < 1.
     bool octreePartition(const OctreeIndex& tree, int minTrees, OctreePartition& out, int minSplitLeaves = 100) const;
+    // Scene::saveAsNVM (src/hpmvs/Scene.cpp:646-713): the scene as a VisualSFM dataset in the frame the output is expressed in.
+    // <folder>/imgs/<i>.jpg is view i's undistorted level 0, encoded where it lies in HBM (hpmvs_scene_get_level_jpeg at CImg's
+    // quality 100: libjpeg's file byte for byte); <folder>/project.nvm holds per view f = kMat_[0](0,0), the de-homogenised
+    // centre, r = 0 and the quaternion <wxyz> of the matrix whose rows are the normalised axes, and per patch one point with
+    // its colour, its centre and one measurement per attached image at the camera's level-0 projection of the centre; an empty
+    // model follows, as in the reference.  The reference walks its patchTree_; here the patches are handed in, as they are to
+    // writeExtPly.  The quaternion is normalised in double behind the conversion (the reference leaves the float axes' 1e-7).
+    // False, with the reason on stderr, when a folder or file cannot be written or a view cannot be encoded.
+    bool saveAsNVM(const char* folder, const std::vector<Ppatch3d>& patches) const;
     std::map<std::string, int> dict_;
     std::vector<Camera> cameras_;
     std::vector<Image> images_;

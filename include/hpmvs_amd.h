@@ -28,6 +28,8 @@
  *   hpmvs_scene_set_view_distorted  k1 != 0, :50-53), before the pyramid.
  *   hpmvs_jpeg_decode,       <- Image::load's CImg / libjpeg read of the view, src/hpmvs/Image.cpp:46
  *   hpmvs_scene_set_view_jpeg   (thirdLibs/cimg/CImg.h:36920-36934).
+ *   hpmvs_jpeg_encode,       <- the views Scene::saveAsNVM writes, src/hpmvs/Scene.cpp:646-713, through CImg's save_jpeg
+ *   hpmvs_scene_get_level_jpeg  and libjpeg at quality 100 (thirdLibs/cimg/CImg.h:40748-40838).
  *   hpmvs_init_patches_batch <- the seed loop of Scene::initPatches, src/hpmvs/Scene.cpp:112-178.
  *   hpmvs_init_patches_sphere_batch <- the same loop with the scene-centre gate of --only_sphere
  *                               (options.FILTER_SCENE_CENTER), src/hpmvs/Scene.cpp:105-121.
@@ -65,7 +67,7 @@ extern "C" {
 #define HPMVS_ERR_ARG (-2)     /* bad argument */
 #define HPMVS_ERR_STATE (-3)   /* scene not committed / already committed */
 #define HPMVS_ERR_NODEVICE (-4) /* no gfx950 device visible: there is NO CPU fallback */
-#define HPMVS_ERR_UNSUPPORTED (-5) /* a well-formed input of a kind that is not handled (JPEG decoding: see hpmvs_jpeg_decode) */
+#define HPMVS_ERR_UNSUPPORTED (-5) /* a well-formed input of a kind that is not handled (JPEG: see hpmvs_jpeg_decode, hpmvs_jpeg_encode) */
 
 #define HPMVS_MAX_LEVELS 8
 #define HPMVS_MAX_IMAGES 256 /* images attached to one patch (reference: unbounded vector<int>); overflow => stage 100.  Lists of up to
@@ -264,6 +266,39 @@ int hpmvs_scene_set_view_jpeg_ex(hpmvs_scene *s, int view, const uint8_t *bytes,
  * and a short cap; _DEVICE as above. */
 int hpmvs_jpeg_coefficients(int device, const uint8_t *bytes, size_t n, int entropy, int subseq_bits, int16_t *coef, size_t cap,
                             int *used, int *rounds);
+
+/* ---- baseline JPEG files written from pixels in HBM ----------------------------------------- */
+/* Scene::saveAsNVM of the reference writes every undistorted view through CImg's save_jpeg: jpeg_set_defaults, then
+ * jpeg_set_quality(q, TRUE), on RGB rows -- YCbCr 4:2:0, JDCT_ISLOW, the Annex K Huffman tables, no restart markers, no
+ * optimised coding.  These entries write the file libjpeg writes for that, byte for byte (pinned to Pillow over
+ * libjpeg-turbo: tests/golden/g8_jpeg_enc.npz).  Colour conversion, edge replication, downsampling, the forward DCT, the
+ * quantiser, the Huffman coding and the byte stuffing run on the GPU (kernel_jpeg_encode.hip); the host receives the stuffed
+ * entropy data and its length and puts the 623-byte header in front and EOI behind.
+ * HPMVS_ERR_ARG: a NULL pointer, quality outside 1 .. 100, a side above 65535, cap smaller than the file (nothing is
+ *   written to `out`; *n still names the file's length, so a second call can bring the right buffer).
+ * HPMVS_ERR_UNSUPPORTED: a side under 8 pixels -- the lower bound of hpmvs_jpeg_decode, so that everything written here
+ *   can be read back here.  Arguments are checked before the device is looked for (HPMVS_ERR_NODEVICE).
+ * Calls are independent and keep nothing between them; working buffers live for the call only. */
+/* An upper bound of the file for a width x height image at any quality: every block's code at its longest (under 208
+ * bytes), every byte of it stuffed.  Noise at quality 100 gives files larger than the raw pixels.  0 for sides outside
+ * 1 .. 65535. */
+size_t hpmvs_jpeg_encode_bound(int width, int height);
+/* rgb: width x height interleaved u8 RGB, 3*(y*W+x)+c, host memory or (rgb_on_device != 0) device memory on `device`;
+ * out: host memory of cap bytes; *n: the bytes written. */
+int hpmvs_jpeg_encode(int device, const uint8_t *rgb, int width, int height, int quality, uint8_t *out, size_t cap, size_t *n,
+                      int rgb_on_device);
+/* A pyramid level of a scene's view encoded where it lies: no pixel visits the host.  Level 0 of a view with k1 != 0 holds
+ * the undistorted pixels, the frame every patch and camera of the output is expressed in.  out == NULL: *n = the bound for
+ * the level's size and nothing else happens (as hpmvs_scene_get_level reports sizes).  HPMVS_ERR_ARG for a bad view or
+ * level; a level under 8 pixels on a side is HPMVS_ERR_UNSUPPORTED.  Works before and after hpmvs_scene_commit. */
+int hpmvs_scene_get_level_jpeg(const hpmvs_scene *s, int view, int level, int quality, uint8_t *out, size_t cap, size_t *n);
+/* diagnostics (tools/jpeg_encode_scale.py): hpmvs_jpeg_encode of a device buffer with the time of its stages in ms[8], by
+ * HIP events: [0] the first working buffer and the tables' upload, [1] jpeg_enc_coef_kernel, [2] jpeg_enc_length_kernel, the
+ * scan of the lengths and the total's read-back, [3] the second working buffer and its fills, [4] jpeg_enc_write_kernel,
+ * [5] jpeg_enc_ff_kernel, the scan of the counts and the total's read-back, [6] jpeg_enc_stuff_kernel, [7] the entropy
+ * data's copy to the host. */
+int hpmvs_jpeg_encode_timed(int device, const uint8_t *rgb_device, int width, int height, int quality, uint8_t *out, size_t cap,
+                            size_t *n, float *ms);
 
 /* ---- the hot path ------------------------------------------------------------------------- */
 /* Full optimize() for every patch of the batch.  `stream` is a hipStream_t (NULL = default
