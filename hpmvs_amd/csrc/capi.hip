@@ -1,6 +1,6 @@
-// capi.hip -- the C ABI of include/hpmvs_amd.h: scene residency in HBM + batch launches.
-// Host-side only; all arithmetic of the hot path is in the kernels.  There is no CPU fallback:
-// without a HIP device every compute entry point fails with HPMVS_ERR_NODEVICE.
+// capi.hip -- the C ABI of include/hpmvs_amd.h: scene residency in HBM + batch launches (the image entry points, which
+// touch no scene, are capi_image.hip's).  Host-side only; all arithmetic of the hot path is in the kernels.  There is
+// no CPU fallback: without a HIP device every compute entry point fails with HPMVS_ERR_NODEVICE.
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -20,11 +20,13 @@
 #include <vector>
 
 #include "../../include/hpmvs_amd.h"
+#include "capi_common.hpp"
 #include "dev_types.h"
 #include "launch.h"
 #include "octree.hpp"
 
 using namespace hpmvs;
+using namespace hpmvs::capi;
 
 // Each optimize launch gets its own workspace (work-queue counter block + the per-slot image-list rows),
 // handed out round-robin, so that launches issued concurrently from several host threads / streams (the
@@ -34,21 +36,7 @@ static constexpr int kQueueSlots = 16;
 static constexpr size_t kQueueSlotBytes = 1024;
 static constexpr int kServiceMaxPatches = 4;  // host batches up to this size go through the open batch (Service)  // the counter block at the head of a workspace (zeroed per launch)
 
-static size_t reg_align(size_t v) { return (v + 255) & ~(size_t)255; }  // regions of a workspace or a scratch block start at multiples of 256 bytes
-
-static thread_local std::string g_err;
-
-static int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-#define HIPCHK(expr)                                                                                  \
-    do {                                                                                              \
-        hipError_t _e = (expr);                                                                       \
-        if (_e != hipSuccess)                                                                         \
-            return fail(HPMVS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));            \
-    } while (0)
+thread_local std::string hpmvs::capi::g_err;
 
 struct hpmvs_scene {
     int device = 0;
@@ -334,11 +322,8 @@ int hpmvs_scene_center(const hpmvs_camera* cams, int n, double center[3], double
 
 int hpmvs_scene_create(int n_views, int device, hpmvs_scene** out) {
     if (!out || n_views <= 0 || n_views > 65535) return fail(HPMVS_ERR_ARG, "scene_create: bad n_views/out");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(HPMVS_ERR_NODEVICE, "no HIP device visible (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(HPMVS_ERR_ARG, "scene_create: bad device index");
-    HIPCHK(hipSetDevice(device));
+    if (hpmvs_device_count() <= 0) return fail(HPMVS_ERR_NODEVICE, "no HIP device visible (this library has no CPU fallback)");
+    if (const int rc = use_device(device, "scene_create")) return rc;
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     hpmvs_scene* s = new hpmvs_scene();
@@ -357,249 +342,10 @@ int hpmvs_scene_create(int n_views, int device, hpmvs_scene** out) {
     return HPMVS_OK;
 }
 
-// Image::undistort's parameters (reference Image.h:80: float f_, k1_): k1 finite, f finite and positive
-static bool undistort_args_ok(float f, float k1) { return std::isfinite(k1) && std::isfinite(f) && f > 0.0f; }
-
-// ---- baseline JPEG (jpeg.hpp: the host parses; the scan is entropy-decoded by the host walk or, checked, by
-// kernel_jpeg_entropy.hip; kernel_jpeg.hip does the rest)
-static int jpeg_fail(int code, const std::string& msg) { return fail(code == jpg::kErrUnsupported ? HPMVS_ERR_UNSUPPORTED : HPMVS_ERR_ARG, msg); }
-
-constexpr size_t kJpegQBytes = sizeof(uint16_t) * 3 * 64;
-
-// A file behind its entropy decode: the frame, and its coefficients either in fr.coef (the host walked the scan) or at
-// d_coef + kJpegQBytes on the current device (kernel_jpeg_entropy.hip decoded it; d_coef is the call's own and freed with it).
-struct JpegDecoded {
-    jpg::Frame fr;
-    uint8_t* d_coef = nullptr;
-    int used = HPMVS_JPEG_ENTROPY_HOST, rounds = 0;
-    JpegDecoded() = default;
-    JpegDecoded(const JpegDecoded&) = delete;
-    JpegDecoded& operator=(const JpegDecoded&) = delete;
-    ~JpegDecoded() { if (d_coef) hipFree(d_coef); }
-};
-
-// HPMVS_JPEG_ENTROPY=host|device|auto, read once per process
-static int jpeg_entropy_env() {
-    static const int mode = [] {
-        const char* e = getenv("HPMVS_JPEG_ENTROPY");
-        return e && !strcmp(e, "host") ? HPMVS_JPEG_ENTROPY_HOST : e && !strcmp(e, "device") ? HPMVS_JPEG_ENTROPY_DEVICE : HPMVS_JPEG_ENTROPY_AUTO;
-    }();
-    return mode;
-}
-static bool jpeg_entropy_ok(int e) { return e == HPMVS_JPEG_ENTROPY_AUTO || e == HPMVS_JPEG_ENTROPY_HOST || e == HPMVS_JPEG_ENTROPY_DEVICE; }
-
-// The scan decoded on the current device (kernel_jpeg_entropy.hip) into jd.d_coef, on the null stream.  *why stays empty when
-// the check kernel accepted the chain; otherwise it says why the scan is the host walk's, and jd holds no device buffer.
-// Working buffers the device cannot allocate leave the scan to the host walk like any other reason.
-// ms (diagnostics, nullable): [0] prescan (wall clock); by HIP events [1] uploads and fills, [2] jpeg_entropy_sync_kernel, all
-// passes, [3] the passes with their read-backs, [4] _scan_local, [5] _scan_groups, [6] _check, [7] _write kernel.
-static int jpeg_entropy_device(const uint8_t* bytes, size_t n, size_t scan_start, const jpg::Huff* huff, uint32_t subseq_bits,
-                               JpegDecoded& jd, std::string* why, float* ms = nullptr) {
-    const jpg::Frame& fr = jd.fr;
-    jpg::Prescan ps;
-    const auto t0 = std::chrono::steady_clock::now();
-    const bool taken = jpg::prescan(bytes, n, scan_start, fr, ps);
-    if (ms) ms[0] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (!taken) {
-        *why = "jpeg: the scan is not one the device decodes (fill bytes, restart markers or the end of the scan)";
-        return HPMVS_OK;
-    }
-    const size_t n_subs = jpg::plan_subsequences(ps, subseq_bits);
-    if (n_subs >= ((size_t)1 << 30)) { *why = "jpeg: too many subsequences"; return HPMVS_OK; }
-    std::vector<uint32_t> sub_seg(n_subs);
-    for (size_t s = 0; s < ps.segs.size(); s++)
-        for (uint32_t i = 0; i < ps.segs[s].n_subs; i++) sub_seg[ps.segs[s].first_sub + i] = (uint32_t)s;
-    std::vector<uint32_t> tabs((6 * sizeof(jpg::Huff) + 64) / 4);
-    {
-        std::vector<jpg::Huff> six(6);
-        jpg::scan_tables(fr, huff, six.data());
-        memcpy(tabs.data(), six.data(), 6 * sizeof(jpg::Huff));
-        memcpy(tabs.data() + 6 * sizeof(jpg::Huff) / 4, jpg::kZigzag, 64);
-    }
-    JpegEntropy A;
-    A.si = jpg::make_scan_info(fr);
-    A.subseq_bits = subseq_bits;
-    A.n_subs = (uint32_t)n_subs;
-    A.n_segs = (uint32_t)ps.segs.size();
-    A.n_groups = (uint32_t)((n_subs + jpg::kSubsPerGroup - 1) / jpg::kSubsPerGroup);
-    A.n_scan_groups = (uint32_t)((n_subs + 255) / 256);
-    // one working buffer, every array at a 256-byte aligned offset
-    size_t total = 0;
-    auto take = [&total](size_t nbytes) { const size_t at = total; total += (nbytes + 255) & ~(size_t)255; return at; };
-    const size_t o_bytes = take(ps.bytes.size()), o_segs = take(ps.segs.size() * sizeof(jpg::Segment)), o_sub = take(n_subs * 4),
-                 o_tabs = take(tabs.size() * 4), o_entry = take(n_subs * sizeof(jpg::SubState)), o_exit = take(n_subs * sizeof(jpg::SubState)),
-                 o_gexit = take((size_t)2 * A.n_groups * sizeof(jpg::SubState)), o_cnt = take(n_subs * sizeof(uint4)),
-                 o_incl = take(n_subs * sizeof(uint4)), o_grp = take((size_t)A.n_scan_groups * sizeof(uint4)), o_flags = take(16);
-    uint8_t* work = nullptr;
-    struct Free { uint8_t*& a; ~Free() { if (a) hipFree(a); } } free_on_exit{work};
-    const size_t coef_bytes = fr.n_blocks * 64 * sizeof(int16_t);
-    if (hipMalloc((void**)&work, total) != hipSuccess) work = nullptr;
-    if (work && hipMalloc((void**)&jd.d_coef, kJpegQBytes + coef_bytes) != hipSuccess) jd.d_coef = nullptr;
-    if (!work || !jd.d_coef) {   // (free_on_exit releases the working buffer when only the coefficients found no room)
-        (void)hipGetLastError();  // the failed allocation is no error of the call
-        *why = "jpeg: no device memory for the entropy decode's working buffers";
-        return HPMVS_OK;
-    }
-    A.bytes = work + o_bytes;
-    A.segs = (const jpg::Segment*)(work + o_segs);
-    A.sub_seg = (const uint32_t*)(work + o_sub);
-    A.tabs = (const uint32_t*)(work + o_tabs);
-    A.entry = (jpg::SubState*)(work + o_entry);
-    A.exit = (jpg::SubState*)(work + o_exit);
-    A.grp_exit = (jpg::SubState*)(work + o_gexit);
-    A.cnt = (uint4*)(work + o_cnt);
-    A.incl = (uint4*)(work + o_incl);
-    A.grp = (uint4*)(work + o_grp);
-    A.flags = (uint32_t*)(work + o_flags);
-    // events: 0 start, 1 uploaded, 2 passes done, 3 .. 7 around the four kernels of the finish, 8 / 9 around a pass's kernel
-    hipEvent_t ev[10] = {};
-    struct Events { hipEvent_t* e; ~Events() { for (int k = 0; k < 10; k++) if (e[k]) hipEventDestroy(e[k]); } } events{ev};
-    if (ms) {
-        for (int k = 0; k < 10; k++) HIPCHK(hipEventCreate(&ev[k]));
-        HIPCHK(hipEventRecord(ev[0], nullptr));
-        ms[2] = 0.0f;
-    }
-    HIPCHK(hipMemcpy(work + o_bytes, ps.bytes.data(), ps.bytes.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(work + o_segs, ps.segs.data(), ps.segs.size() * sizeof(jpg::Segment), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(work + o_sub, sub_seg.data(), n_subs * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(work + o_tabs, tabs.data(), tabs.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemsetAsync(work + o_gexit, 0, (size_t)2 * A.n_groups * sizeof(jpg::SubState), nullptr));
-    HIPCHK(hipMemsetAsync(work + o_flags, 0, 16, nullptr));
-    HIPCHK(hipMemsetAsync(jd.d_coef + kJpegQBytes, 0, coef_bytes, nullptr));
-    if (ms) HIPCHK(hipEventRecord(ev[1], nullptr));
-    const int cap = jpg::sync_round_cap(subseq_bits);
-    int rounds = 0;
-    bool out_of_rounds = false;
-    for (int pass = 0;; pass++) {  // every pass but the last takes a round at least: at most cap + 2 passes
-        HIPCHK(hipMemsetAsync(A.flags, 0, 8, nullptr));
-        if (ms) HIPCHK(hipEventRecord(ev[8], nullptr));
-        launch_jpeg_entropy_sync(A, pass, cap - rounds, nullptr);
-        HIPCHK(hipGetLastError());
-        if (ms) HIPCHK(hipEventRecord(ev[9], nullptr));
-        uint32_t f[2] = {0, 0};
-        HIPCHK(hipMemcpy(f, A.flags, 8, hipMemcpyDeviceToHost));
-        if (ms) {
-            float t = 0.0f;
-            HIPCHK(hipEventElapsedTime(&t, ev[8], ev[9]));
-            ms[2] += t;
-        }
-        rounds += (int)f[0];
-        if (f[1]) { out_of_rounds = true; break; }
-        if (pass > 0 && f[0] == 0) break;
-    }
-    jd.rounds = rounds;
-    if (ms) HIPCHK(hipEventRecord(ev[2], nullptr));
-    uint32_t refused = 1;
-    if (!out_of_rounds) {
-        HIPCHK(launch_jpeg_entropy_finish(A, (int16_t*)(jd.d_coef + kJpegQBytes), nullptr, ms ? ev + 3 : nullptr));
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpy(&refused, A.flags + 2, 4, hipMemcpyDeviceToHost));
-        if (ms) {
-            HIPCHK(hipEventElapsedTime(&ms[1], ev[0], ev[1]));
-            HIPCHK(hipEventElapsedTime(&ms[3], ev[1], ev[2]));
-            for (int k = 0; k < 4; k++) HIPCHK(hipEventElapsedTime(&ms[4 + k], ev[3 + k], ev[4 + k]));
-        }
-    }
-    if (refused) {
-        *why = out_of_rounds ? "jpeg: the subsequences did not synchronise within " + std::to_string(cap) + " rounds"
-                             : "jpeg: the check refused the chain of subsequences (corrupt entropy data, or data behind the last block)";
-        hipFree(jd.d_coef);
-        jd.d_coef = nullptr;
-        return HPMVS_OK;
-    }
-    jd.used = HPMVS_JPEG_ENTROPY_DEVICE;  // (the quantiser steps in front of the coefficients: jpeg_frame_to_device)
-    return HPMVS_OK;
-}
-
-// hpmvs_jpeg_last_decode: what decoded the scan in this thread's last successful JPEG decode
-static thread_local int t_jpeg_last_used = -1, t_jpeg_last_rounds = 0;
-
-// The scan of a parsed file decoded where `entropy` says, on the current device.  strict: the caller asked for the device
-// itself, so what the device does not take is HPMVS_ERR_STATE instead of the host walk.
-static int jpeg_decode_scan(const uint8_t* bytes, size_t n, size_t scan_start, const jpg::Huff* huff, int entropy, bool strict,
-                            uint32_t subseq_bits, JpegDecoded& jd, float* ms = nullptr) {
-    const bool on_device = entropy == HPMVS_JPEG_ENTROPY_DEVICE ||
-                           (entropy == HPMVS_JPEG_ENTROPY_AUTO && n - scan_start >= (size_t)HPMVS_JPEG_AUTO_MIN_SCAN_BYTES);
-    if (on_device) {
-        std::string why;
-        const int rc = jpeg_entropy_device(bytes, n, scan_start, huff, subseq_bits, jd, &why, ms);
-        if (rc != HPMVS_OK) {
-            if (jd.d_coef) { hipFree(jd.d_coef); jd.d_coef = nullptr; }
-            return rc;
-        }
-        if (why.empty()) {
-            t_jpeg_last_used = jd.used;
-            t_jpeg_last_rounds = jd.rounds;
-            return HPMVS_OK;
-        }
-        if (strict) return fail(HPMVS_ERR_STATE, why);
-    }
-    std::string err;
-    const int rc = jpg::decode_scan(bytes, n, scan_start, jd.fr, huff, true, &err);
-    if (rc != jpg::kOk) return jpeg_fail(rc, err);
-    jd.used = HPMVS_JPEG_ENTROPY_HOST;
-    jd.rounds = 0;
-    t_jpeg_last_used = jd.used;
-    t_jpeg_last_rounds = 0;
-    return HPMVS_OK;
-}
-
-// an argument error found behind the header parse: the file's own refusal, if the scan has one, still comes first
-static int jpeg_arg_error(const uint8_t* bytes, size_t n, size_t scan_start, const jpg::Huff* huff, jpg::Frame& fr, int code,
-                          const std::string& msg) {
-    std::string err;
-    const int rc = jpg::decode_scan(bytes, n, scan_start, fr, huff, false, &err);
-    return rc != jpg::kOk ? jpeg_fail(rc, err) : fail(code, msg);
-}
-
-// Coefficients of a decoded frame -> interleaved RGB at the device address d_rgb (3 W H bytes), on the null stream of the
-// current device; returns after the kernels have run.  The two working buffers (quantiser tables + coefficients, 2 bytes
-// per sample; sample planes, 1 byte per sample) live for this call only: nothing is held between calls, so concurrent
-// calls share nothing and a many-view upload accumulates nothing.
-// ms (diagnostics, nullable): [1] coefficient upload, [2] IDCT kernel, [3] RGB kernel, from HIP events.
-static int jpeg_frame_to_device(const JpegDecoded& jd, uint8_t* d_rgb, float* ms = nullptr) {
-    const jpg::Frame& fr = jd.fr;
-    jpg::Planes P;
-    const size_t plane_bytes = jpg::make_planes(fr, &P);
-    const size_t q_bytes = kJpegQBytes, coef_bytes = fr.n_blocks * 64 * sizeof(int16_t);
-    uint16_t q[3 * 64] = {};
-    for (int c = 0; c < fr.ncomp; c++) memcpy(q + 64 * c, fr.q[c], sizeof(uint16_t) * 64);
-    uint8_t *d_own = nullptr, *d_planes = nullptr;  // (d_own: the coefficient buffer when the host decoded the scan)
-    struct Free { uint8_t*& a; uint8_t*& b; ~Free() { if (a) hipFree(a); if (b) hipFree(b); } } free_on_exit{d_own, d_planes};
-    if (!jd.d_coef) HIPCHK(hipMalloc((void**)&d_own, q_bytes + coef_bytes));
-    uint8_t* const d_coef = jd.d_coef ? jd.d_coef : d_own;
-    HIPCHK(hipMalloc((void**)&d_planes, plane_bytes));
-    hipEvent_t ev[4] = {};
-    struct Events { hipEvent_t* e; ~Events() { for (int k = 0; k < 4; k++) if (e[k]) hipEventDestroy(e[k]); } } events{ev};
-    if (ms) {
-        for (int k = 0; k < 4; k++) HIPCHK(hipEventCreate(&ev[k]));
-        HIPCHK(hipEventRecord(ev[0], nullptr));
-    }
-    HIPCHK(hipMemcpy(d_coef, q, q_bytes, hipMemcpyHostToDevice));
-    if (!jd.d_coef) HIPCHK(hipMemcpy(d_coef + q_bytes, fr.coef.data(), coef_bytes, hipMemcpyHostToDevice));
-    JpegBlocks B;
-    B.n_blocks = (uint32_t)fr.n_blocks;
-    B.first1 = fr.ncomp == 3 ? (uint32_t)(fr.c[1].off / 64) : B.n_blocks;
-    B.first2 = fr.ncomp == 3 ? (uint32_t)(fr.c[2].off / 64) : B.n_blocks;
-    B.bx0 = fr.c[0].bx;
-    B.bx12 = fr.ncomp == 3 ? fr.c[1].bx : fr.c[0].bx;
-    if (ms) HIPCHK(hipEventRecord(ev[1], nullptr));
-    launch_jpeg_idct((const uint16_t*)d_coef, (const int16_t*)(d_coef + q_bytes), B, P, d_planes, nullptr);
-    HIPCHK(hipGetLastError());
-    if (ms) HIPCHK(hipEventRecord(ev[2], nullptr));
-    launch_jpeg_rgb(d_planes, P, d_rgb, nullptr);
-    HIPCHK(hipGetLastError());
-    if (ms) HIPCHK(hipEventRecord(ev[3], nullptr));
-    HIPCHK(hipDeviceSynchronize());
-    if (ms)
-        for (int k = 0; k < 3; k++) HIPCHK(hipEventElapsedTime(&ms[1 + k], ev[k], ev[k + 1]));
-    return HPMVS_OK;
-}
-
 // hpmvs_scene_set_view and, for k1 != 0, hpmvs_scene_set_view_distorted: level 0 is the raw view undistorted on the GPU
 // (jf: hpmvs_scene_set_view_jpeg_ex -- the raw level 0 is decoded on the device from the frame's coefficients; rgb_l0 is unused)
 static int set_view(hpmvs_scene* s, int view, int width, int height, const uint8_t* rgb_l0, int rgb_on_device,
-                    const hpmvs_camera* cam, float f, float k1, const JpegDecoded* jf = nullptr) {
+                    const hpmvs_camera* cam, float f, float k1, const JpegFile* jf = nullptr) {
     if (!s || !cam || (!rgb_l0 && !jf)) return fail(HPMVS_ERR_ARG, "scene_set_view: null argument");
     if (s->committed) return fail(HPMVS_ERR_STATE, "scene_set_view: scene already committed");
     if (view < 0 || view >= s->n_views || width < 2 || height < 2) return fail(HPMVS_ERR_ARG, "scene_set_view: bad view/size");
@@ -623,15 +369,14 @@ static int set_view(hpmvs_scene* s, int view, int width, int height, const uint8
     }
     // the raw view of a distorted one on the device: the caller's buffer, or a copy of the host pixels
     const uint8_t* raw = nullptr;
-    uint8_t* raw_copy = nullptr;
-    struct FreeRaw { uint8_t*& p; ~FreeRaw() { if (p) hipFree(p); } } free_raw{raw_copy};
+    DeviceBuffer raw_copy;
     if (k1 != 0.0f) {
         if (rgb_on_device && !jf) {
             raw = rgb_l0;
         } else {
-            HIPCHK(hipMalloc((void**)&raw_copy, (size_t)width * height * 3));
-            if (!jf) HIPCHK(hipMemcpy(raw_copy, rgb_l0, (size_t)width * height * 3, hipMemcpyHostToDevice));
-            raw = raw_copy;
+            HIPCHK(raw_copy.alloc((size_t)width * height * 3));
+            if (!jf) HIPCHK(hipMemcpy(raw_copy.p, rgb_l0, (size_t)width * height * 3, hipMemcpyHostToDevice));
+            raw = raw_copy.p;
         }
     }
     uint8_t* slab = nullptr;
@@ -653,7 +398,7 @@ static int set_view(hpmvs_scene* s, int view, int width, int height, const uint8
         uint8_t* d = slab + off[l];
         const size_t nb = (size_t)w * h * 3;
         if (l == 0 && jf) {  // decoded straight into level 0, or into the raw copy the undistortion reads
-            const int rc = jpeg_frame_to_device(*jf, raw_copy ? raw_copy : d);
+            const int rc = jpeg_frame_to_device(*jf, raw_copy ? raw_copy.p : d);
             if (rc != HPMVS_OK) return rc;
         }
         if (l == 0 && raw) {
@@ -690,252 +435,6 @@ int hpmvs_scene_set_view_distorted(hpmvs_scene* s, int view, int width, int heig
     return set_view(s, view, width, height, rgb_raw, rgb_on_device, cam, f, k1);
 }
 
-int hpmvs_jpeg_info(const uint8_t* bytes, size_t n, int* width, int* height, int* components, int* h_samp, int* v_samp) {
-    if (!bytes || !width || !height || !components || !h_samp || !v_samp) return fail(HPMVS_ERR_ARG, "jpeg_info: null argument");
-    jpg::Frame fr;
-    std::string err;
-    const int rc = jpg::decode_file(bytes, n, fr, false, &err);
-    if (rc != jpg::kOk) return jpeg_fail(rc, err);
-    *width = fr.W; *height = fr.H; *components = fr.ncomp; *h_samp = fr.hmax; *v_samp = fr.vmax;
-    return HPMVS_OK;
-}
-
-// strict: the caller asked for the device itself (jpeg_decode_scan)
-static int jpeg_decode_impl(int device, const uint8_t* bytes, size_t n, uint8_t* rgb, size_t cap, int rgb_on_device, int entropy, bool strict,
-                            int* used) {
-    if (!bytes || !rgb) return fail(HPMVS_ERR_ARG, "jpeg_decode: null argument");
-    if (!jpeg_entropy_ok(entropy)) return fail(HPMVS_ERR_ARG, "jpeg_decode: bad entropy value");
-    JpegDecoded jd;
-    jpg::Frame& fr = jd.fr;
-    std::vector<jpg::Huff> huff(8);
-    size_t scan_start = 0;
-    std::string err;
-    const int rc = jpg::parse_headers(bytes, n, fr, huff.data(), &scan_start, &err);
-    if (rc != jpg::kOk) return jpeg_fail(rc, err);
-    const size_t nb = (size_t)3 * fr.W * fr.H;
-    int ndev = 0;
-    if (cap < nb) return jpeg_arg_error(bytes, n, scan_start, huff.data(), fr, HPMVS_ERR_ARG, "jpeg_decode: output buffer smaller than 3 * width * height");
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return jpeg_arg_error(bytes, n, scan_start, huff.data(), fr, HPMVS_ERR_NODEVICE, "no HIP device visible");
-    if (device < 0 || device >= ndev) return jpeg_arg_error(bytes, n, scan_start, huff.data(), fr, HPMVS_ERR_ARG, "jpeg_decode: bad device index");
-    HIPCHK(hipSetDevice(device));
-    const int rs = jpeg_decode_scan(bytes, n, scan_start, huff.data(), entropy, strict, jpg::kSubseqBits, jd);
-    if (rs != HPMVS_OK) return rs;
-    if (used) *used = jd.used;
-    if (rgb_on_device) return jpeg_frame_to_device(jd, rgb);
-    uint8_t* d_rgb = nullptr;
-    struct Free { uint8_t*& a; ~Free() { if (a) hipFree(a); } } free_on_exit{d_rgb};
-    HIPCHK(hipMalloc((void**)&d_rgb, nb));
-    const int rd = jpeg_frame_to_device(jd, d_rgb);
-    if (rd != HPMVS_OK) return rd;
-    HIPCHK(hipMemcpy(rgb, d_rgb, nb, hipMemcpyDeviceToHost));
-    return HPMVS_OK;
-}
-
-int hpmvs_jpeg_decode_ex(int device, const uint8_t* bytes, size_t n, uint8_t* rgb, size_t cap, int rgb_on_device, int entropy, int* used) {
-    return jpeg_decode_impl(device, bytes, n, rgb, cap, rgb_on_device, entropy, entropy == HPMVS_JPEG_ENTROPY_DEVICE, used);
-}
-
-// (the environment's choice; its `device` is no request for the device itself and leaves to the host walk what _AUTO would)
-int hpmvs_jpeg_decode(int device, const uint8_t* bytes, size_t n, uint8_t* rgb, size_t cap, int rgb_on_device) {
-    return jpeg_decode_impl(device, bytes, n, rgb, cap, rgb_on_device, jpeg_entropy_env(), false, nullptr);
-}
-
-int hpmvs_jpeg_coefficients(int device, const uint8_t* bytes, size_t n, int entropy, int subseq_bits, int16_t* coef, size_t cap, int* used,
-                            int* rounds) {
-    if (!bytes || !coef) return fail(HPMVS_ERR_ARG, "jpeg_coefficients: null argument");
-    if (!jpeg_entropy_ok(entropy)) return fail(HPMVS_ERR_ARG, "jpeg_coefficients: bad entropy value");
-    if (subseq_bits != 0 && (subseq_bits < 64 || subseq_bits % 32 != 0))
-        return fail(HPMVS_ERR_ARG, "jpeg_coefficients: subseq_bits must be 0 or a multiple of 32 from 64 up");
-    JpegDecoded jd;
-    jpg::Frame& fr = jd.fr;
-    std::vector<jpg::Huff> huff(8);
-    size_t scan_start = 0;
-    std::string err;
-    const int rc = jpg::parse_headers(bytes, n, fr, huff.data(), &scan_start, &err);
-    if (rc != jpg::kOk) return jpeg_fail(rc, err);
-    const size_t nc = fr.n_blocks * 64;
-    if (cap < nc) return fail(HPMVS_ERR_ARG, "jpeg_coefficients: output buffer smaller than the frame's coefficients");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(HPMVS_ERR_NODEVICE, "no HIP device visible");
-    if (device < 0 || device >= ndev) return fail(HPMVS_ERR_ARG, "jpeg_coefficients: bad device index");
-    HIPCHK(hipSetDevice(device));
-    const int rs = jpeg_decode_scan(bytes, n, scan_start, huff.data(), entropy, entropy == HPMVS_JPEG_ENTROPY_DEVICE,
-                                    subseq_bits ? (uint32_t)subseq_bits : (uint32_t)jpg::kSubseqBits, jd);
-    if (rs != HPMVS_OK) return rs;
-    if (jd.d_coef) HIPCHK(hipMemcpy(coef, jd.d_coef + kJpegQBytes, nc * sizeof(int16_t), hipMemcpyDeviceToHost));
-    else memcpy(coef, fr.coef.data(), nc * sizeof(int16_t));
-    if (used) *used = jd.used;
-    if (rounds) *rounds = jd.rounds;
-    return HPMVS_OK;
-}
-
-int hpmvs_jpeg_last_decode(int* used, int* rounds) {
-    if (!used) return fail(HPMVS_ERR_ARG, "jpeg_last_decode: null argument");
-    if (t_jpeg_last_used < 0) return fail(HPMVS_ERR_STATE, "jpeg_last_decode: this thread has decoded no JPEG scan yet");
-    *used = t_jpeg_last_used;
-    if (rounds) *rounds = t_jpeg_last_rounds;
-    return HPMVS_OK;
-}
-
-int hpmvs_jpeg_decode_timed(int device, const uint8_t* bytes, size_t n, uint8_t* rgb_device, size_t cap, float* ms) {
-    if (!bytes || !rgb_device || !ms) return fail(HPMVS_ERR_ARG, "jpeg_decode_timed: null argument");
-    JpegDecoded jd;
-    jpg::Frame& fr = jd.fr;
-    std::string err;
-    const auto t0 = std::chrono::steady_clock::now();
-    const int rc = jpg::decode_file(bytes, n, fr, true, &err);
-    ms[0] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (rc != jpg::kOk) return jpeg_fail(rc, err);
-    if (cap < (size_t)3 * fr.W * fr.H) return fail(HPMVS_ERR_ARG, "jpeg_decode_timed: output buffer smaller than 3 * width * height");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(HPMVS_ERR_NODEVICE, "no HIP device visible");
-    if (device < 0 || device >= ndev) return fail(HPMVS_ERR_ARG, "jpeg_decode_timed: bad device index");
-    HIPCHK(hipSetDevice(device));
-    return jpeg_frame_to_device(jd, rgb_device, ms);
-}
-
-int hpmvs_jpeg_entropy_timed(int device, const uint8_t* bytes, size_t n, uint8_t* rgb_device, size_t cap, float* ms) {
-    if (!bytes || !rgb_device || !ms) return fail(HPMVS_ERR_ARG, "jpeg_entropy_timed: null argument");
-    JpegDecoded jd;
-    jpg::Frame& fr = jd.fr;
-    std::vector<jpg::Huff> huff(8);
-    size_t scan_start = 0;
-    std::string err;
-    const int rc = jpg::parse_headers(bytes, n, fr, huff.data(), &scan_start, &err);
-    if (rc != jpg::kOk) return jpeg_fail(rc, err);
-    if (cap < (size_t)3 * fr.W * fr.H) return fail(HPMVS_ERR_ARG, "jpeg_entropy_timed: output buffer smaller than 3 * width * height");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(HPMVS_ERR_NODEVICE, "no HIP device visible");
-    if (device < 0 || device >= ndev) return fail(HPMVS_ERR_ARG, "jpeg_entropy_timed: bad device index");
-    HIPCHK(hipSetDevice(device));
-    for (int k = 0; k < 12; k++) ms[k] = 0.0f;
-    const int rs = jpeg_decode_scan(bytes, n, scan_start, huff.data(), HPMVS_JPEG_ENTROPY_DEVICE, true, jpg::kSubseqBits, jd, ms);
-    if (rs != HPMVS_OK) return rs;
-    ms[11] = (float)jd.rounds;
-    return jpeg_frame_to_device(jd, rgb_device, ms + 7);
-}
-
-// ---- baseline JPEG encode (jpeg_enc.hpp, kernel_jpeg_encode.hip): everything between the pixels and the stuffed entropy data
-// runs on the device; the host puts the header in front and EOI behind
-static int jpeg_enc_fail(int code, const std::string& msg) { return fail(code == jpge::kErrUnsupported ? HPMVS_ERR_UNSUPPORTED : HPMVS_ERR_ARG, msg); }
-
-size_t hpmvs_jpeg_encode_bound(int width, int height) {
-    if (width < 1 || height < 1 || width > jpge::kMaxSide || height > jpge::kMaxSide) return 0;
-    return jpge::encode_bound(width, height);
-}
-
-// d_rgb: interleaved u8 [H][W][3] on the current device -> the whole file at the host address `out`, on the null stream.  *n is
-// the file's length, also when cap is too small (HPMVS_ERR_ARG; nothing is written to `out` then).  The two working buffers
-// live for this call only.  The first is sized from the image: tables, coefficients, the blocks' lengths and offsets.  The
-// second is sized from the stream's length once the scan has given it, which jpeg_enc.hpp's bound (208 bytes per block,
-// every byte stuffed) limits: the stream, its chunks' counts and offsets, and the stuffed bytes at twice the stream's length.
-// ms (diagnostics, nullable): by HIP events [0] the first buffer and the tables' upload, [1] coefficient kernel, [2] lengths and their scan
-// with the total's read-back, [3] the second buffer and its fills, [4] write kernel, [5] 0xFF counts and their scan with the
-// total's read-back, [6] stuff kernel, [7] the bytes' copy to the host.
-static int jpeg_encode_device(const uint8_t* d_rgb, int W, int H, int quality, uint8_t* out, size_t cap, size_t* n, float* ms = nullptr) {
-    const jpge::Geom g = jpge::make_geom(W, H);
-    jpge::EncTables T;
-    jpge::make_tables(quality, &T);
-    const size_t nb = g.n_blocks;
-    uint8_t *work = nullptr, *work2 = nullptr;
-    struct Free { uint8_t*& a; uint8_t*& b; ~Free() { if (a) hipFree(a); if (b) hipFree(b); } } free_on_exit{work, work2};
-    hipEvent_t ev[9] = {};
-    struct Events { hipEvent_t* e; ~Events() { for (int k = 0; k < 9; k++) if (e[k]) hipEventDestroy(e[k]); } } events{ev};
-    if (ms)
-        for (int k = 0; k < 9; k++) HIPCHK(hipEventCreate(&ev[k]));
-    auto mark = [&](int k) { return ms ? hipEventRecord(ev[k], nullptr) : hipSuccess; };
-    size_t scan_bytes = 0;
-    HIPCHK((hipError_t)jpeg_enc_scan(nullptr, &scan_bytes, nullptr, nullptr, nb + 1, nullptr));
-    size_t total = 0;
-    auto take = [&total](size_t nbytes) { const size_t at = total; total += reg_align(nbytes); return at; };
-    const size_t o_tabs = take(sizeof(T)), o_coef = take(nb * 64 * sizeof(int16_t)), o_lens = take((nb + 1) * 8), o_offs = take((nb + 1) * 8),
-                 o_temp = take(scan_bytes);
-    HIPCHK(mark(0));
-    HIPCHK(hipMalloc((void**)&work, total));
-    const jpge::EncTables* d_tabs = (const jpge::EncTables*)(work + o_tabs);
-    int16_t* d_coef = (int16_t*)(work + o_coef);
-    unsigned long long *d_lens = (unsigned long long*)(work + o_lens), *d_offs = (unsigned long long*)(work + o_offs);
-    HIPCHK(hipMemcpy(work + o_tabs, &T, sizeof(T), hipMemcpyHostToDevice));
-    HIPCHK(hipMemsetAsync(d_lens + nb, 0, 8, nullptr));
-    HIPCHK(mark(1));
-    launch_jpeg_enc_coef(d_rgb, g, d_tabs, d_coef, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(mark(2));
-    launch_jpeg_enc_lengths(d_coef, g.n_blocks, d_tabs, d_lens, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK((hipError_t)jpeg_enc_scan(work + o_temp, &scan_bytes, d_lens, d_offs, nb + 1, nullptr));
-    unsigned long long bits = 0;
-    HIPCHK(hipMemcpy(&bits, d_offs + nb, 8, hipMemcpyDeviceToHost));
-    HIPCHK(mark(3));
-    if (bits == 0 || bits > (unsigned long long)nb * jpge::kBlockBoundBytes * 8) return fail(HPMVS_ERR_HIP, "jpeg_encode: the blocks' lengths are none the encoder produces");
-    const unsigned long long n_bytes = (bits + 7) / 8, n_chunks = (n_bytes + 63) / 64;
-    size_t scan2_bytes = 0;
-    HIPCHK((hipError_t)jpeg_enc_scan(nullptr, &scan2_bytes, nullptr, nullptr, (size_t)n_chunks + 1, nullptr));
-    total = 0;
-    const size_t o_stream = take((size_t)n_chunks * 64), o_cnt = take(((size_t)n_chunks + 1) * 8), o_moved = take(((size_t)n_chunks + 1) * 8),
-                 o_temp2 = take(scan2_bytes), o_out = take((size_t)n_bytes * 2);
-    HIPCHK(hipMalloc((void**)&work2, total));
-    unsigned long long *d_cnt = (unsigned long long*)(work2 + o_cnt), *d_moved = (unsigned long long*)(work2 + o_moved);
-    HIPCHK(hipMemsetAsync(work2 + o_stream, 0, (size_t)n_chunks * 64, nullptr));
-    HIPCHK(hipMemsetAsync(d_cnt + n_chunks, 0, 8, nullptr));
-    HIPCHK(mark(4));
-    launch_jpeg_enc_write(d_coef, g.n_blocks, d_tabs, d_offs, (uint32_t*)(work2 + o_stream), nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(mark(5));
-    launch_jpeg_enc_ff(work2 + o_stream, n_chunks, d_cnt, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK((hipError_t)jpeg_enc_scan(work2 + o_temp2, &scan2_bytes, d_cnt, d_moved, (size_t)n_chunks + 1, nullptr));
-    unsigned long long n_ff = 0;
-    HIPCHK(hipMemcpy(&n_ff, d_moved + n_chunks, 8, hipMemcpyDeviceToHost));
-    HIPCHK(mark(6));
-    if (n_ff > n_bytes) return fail(HPMVS_ERR_HIP, "jpeg_encode: more stuffed bytes than bytes");
-    const size_t n_data = (size_t)(n_bytes + n_ff);
-    *n = jpge::kHeaderBytes + n_data + 2;
-    if (cap < *n) return fail(HPMVS_ERR_ARG, "jpeg_encode: output buffer too small (" + std::to_string(*n) + " bytes needed)");
-    launch_jpeg_enc_stuff(work2 + o_stream, n_chunks, n_bytes, d_moved, work2 + o_out, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(mark(7));
-    HIPCHK(hipMemcpy(out + jpge::kHeaderBytes, work2 + o_out, n_data, hipMemcpyDeviceToHost));
-    HIPCHK(mark(8));
-    jpge::write_header(W, H, quality, out);
-    out[jpge::kHeaderBytes + n_data] = 0xFF;
-    out[jpge::kHeaderBytes + n_data + 1] = 0xD9;
-    if (ms) {
-        HIPCHK(hipEventSynchronize(ev[8]));
-        for (int k = 0; k < 8; k++) HIPCHK(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
-    }
-    return HPMVS_OK;
-}
-
-static int jpeg_encode_impl(int device, const uint8_t* rgb, int width, int height, int quality, uint8_t* out, size_t cap, size_t* n,
-                            int rgb_on_device, float* ms) {
-    if (!rgb || !out || !n) return fail(HPMVS_ERR_ARG, "jpeg_encode: null argument");
-    std::string err;
-    const int rc = jpge::check_args(width, height, quality, &err);
-    if (rc != jpge::kOk) return jpeg_enc_fail(rc, err);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(HPMVS_ERR_NODEVICE, "no HIP device visible");
-    if (device < 0 || device >= ndev) return fail(HPMVS_ERR_ARG, "jpeg_encode: bad device index");
-    HIPCHK(hipSetDevice(device));
-    if (rgb_on_device) return jpeg_encode_device(rgb, width, height, quality, out, cap, n, ms);
-    const size_t nb = (size_t)3 * width * height;
-    uint8_t* d_rgb = nullptr;
-    struct Free { uint8_t*& a; ~Free() { if (a) hipFree(a); } } free_on_exit{d_rgb};
-    HIPCHK(hipMalloc((void**)&d_rgb, nb));
-    HIPCHK(hipMemcpy(d_rgb, rgb, nb, hipMemcpyHostToDevice));
-    return jpeg_encode_device(d_rgb, width, height, quality, out, cap, n, ms);
-}
-
-int hpmvs_jpeg_encode(int device, const uint8_t* rgb, int width, int height, int quality, uint8_t* out, size_t cap, size_t* n, int rgb_on_device) {
-    return jpeg_encode_impl(device, rgb, width, height, quality, out, cap, n, rgb_on_device, nullptr);
-}
-
-int hpmvs_jpeg_encode_timed(int device, const uint8_t* rgb_device, int width, int height, int quality, uint8_t* out, size_t cap, size_t* n, float* ms) {
-    if (!ms) return fail(HPMVS_ERR_ARG, "jpeg_encode_timed: null argument");
-    return jpeg_encode_impl(device, rgb_device, width, height, quality, out, cap, n, 1, ms);
-}
-
 int hpmvs_scene_get_level_jpeg(const hpmvs_scene* s, int view, int level, int quality, uint8_t* out, size_t cap, size_t* n) {
     if (!s || !n) return fail(HPMVS_ERR_ARG, "scene_get_level_jpeg: null argument");
     if (view < 0 || view >= s->n_views || !s->view_set[view]) return fail(HPMVS_ERR_ARG, "scene_get_level_jpeg: bad view");
@@ -959,17 +458,12 @@ static int scene_set_view_jpeg_impl(hpmvs_scene* s, int view, const uint8_t* byt
     if (!jpeg_entropy_ok(entropy)) return fail(HPMVS_ERR_ARG, "scene_set_view_jpeg: bad entropy value");
     if (s->committed) return fail(HPMVS_ERR_STATE, "scene_set_view: scene already committed");
     if (view < 0 || view >= s->n_views) return fail(HPMVS_ERR_ARG, "scene_set_view_jpeg: bad view");
-    JpegDecoded jd;
-    std::vector<jpg::Huff> huff(8);
-    size_t scan_start = 0;
-    std::string err;
-    const int rc = jpg::parse_headers(bytes, n, jd.fr, huff.data(), &scan_start, &err);
-    if (rc != jpg::kOk) return jpeg_fail(rc, err);
+    JpegFile jf;
+    if (const int rc = jpeg_open(bytes, n, jf)) return rc;
     HIPCHK(hipSetDevice(s->device));
-    const int rs = jpeg_decode_scan(bytes, n, scan_start, huff.data(), entropy, strict, jpg::kSubseqBits, jd);
-    if (rs != HPMVS_OK) return rs;
-    if (used) *used = jd.used;
-    return set_view(s, view, jd.fr.W, jd.fr.H, nullptr, 0, cam, f, k1, &jd);
+    if (const int rc = jpeg_decode_scan(jf, entropy, strict)) return rc;
+    if (used) *used = jf.used;
+    return set_view(s, view, jf.fr.W, jf.fr.H, nullptr, 0, cam, f, k1, &jf);
 }
 
 int hpmvs_scene_set_view_jpeg_ex(hpmvs_scene* s, int view, const uint8_t* bytes, size_t n, const hpmvs_camera* cam, float f, float k1,
@@ -1060,76 +554,6 @@ int hpmvs_scene_get_level(const hpmvs_scene* s, int view, int level, uint8_t* ho
 }
 
 size_t hpmvs_scene_bytes(const hpmvs_scene* s) { return s ? s->bytes : 0; }
-
-int hpmvs_build_pyramid(int device, const uint8_t* src, int w, int h, uint8_t* dst, int on_device) {
-    if (!src || !dst || w < 2 || h < 2) return fail(HPMVS_ERR_ARG, "build_pyramid: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(HPMVS_ERR_NODEVICE, "no HIP device visible");
-    HIPCHK(hipSetDevice(device));
-    const size_t nb = (size_t)w * h * 3, nb2 = (size_t)(w / 2) * (h / 2) * 3;
-    if (on_device) {
-        launch_half_resize(src, w, h, dst, nullptr);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipDeviceSynchronize());
-        return HPMVS_OK;
-    }
-    uint8_t *ds = nullptr, *dd = nullptr;
-    struct Free { uint8_t*& a; uint8_t*& b; ~Free() { if (a) hipFree(a); if (b) hipFree(b); } } free_on_exit{ds, dd};
-    HIPCHK(hipMalloc((void**)&ds, nb));
-    HIPCHK(hipMalloc((void**)&dd, nb2 + 16));
-    HIPCHK(hipMemcpy(ds, src, nb, hipMemcpyHostToDevice));
-    launch_half_resize(ds, w, h, dd, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(dst, dd, nb2, hipMemcpyDeviceToHost));
-    return HPMVS_OK;
-}
-
-int hpmvs_undistort(int device, const uint8_t* src, int w, int h, float f, float k1, uint8_t* dst, int on_device) {
-    if (!src || !dst || w < 2 || h < 2) return fail(HPMVS_ERR_ARG, "undistort: bad argument");
-    if (!undistort_args_ok(f, k1)) return fail(HPMVS_ERR_ARG, "undistort: f must be finite and > 0, k1 finite");
-    const size_t nb = (size_t)w * h * 3;
-    if (src < dst + nb && dst < src + nb) return fail(HPMVS_ERR_ARG, "undistort: src and dst overlap");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(HPMVS_ERR_NODEVICE, "no HIP device visible");
-    if (device < 0 || device >= ndev) return fail(HPMVS_ERR_ARG, "undistort: bad device index");
-    HIPCHK(hipSetDevice(device));
-    if (k1 == 0.0f) {  // Image::load undistorts only for k1 != 0 (reference Image.cpp:50-53)
-        HIPCHK(hipMemcpy(dst, src, nb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToHost));
-        return HPMVS_OK;
-    }
-    if (on_device) {
-        launch_undistort(src, w, h, f, k1, dst, nullptr);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipDeviceSynchronize());
-        return HPMVS_OK;
-    }
-    uint8_t *ds = nullptr, *dd = nullptr;
-    struct Free { uint8_t*& a; uint8_t*& b; ~Free() { if (a) hipFree(a); if (b) hipFree(b); } } free_on_exit{ds, dd};
-    HIPCHK(hipMalloc((void**)&ds, nb));
-    HIPCHK(hipMalloc((void**)&dd, nb));
-    HIPCHK(hipMemcpy(ds, src, nb, hipMemcpyHostToDevice));
-    launch_undistort(ds, w, h, f, k1, dd, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(dst, dd, nb, hipMemcpyDeviceToHost));
-    return HPMVS_OK;
-}
-
-int hpmvs_undistort_map(int device, int w, int h, float f, float k1, float* xy) {
-    if (!xy || w < 2 || h < 2) return fail(HPMVS_ERR_ARG, "undistort_map: bad argument");
-    if (!undistort_args_ok(f, k1)) return fail(HPMVS_ERR_ARG, "undistort_map: f must be finite and > 0, k1 finite");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(HPMVS_ERR_NODEVICE, "no HIP device visible");
-    if (device < 0 || device >= ndev) return fail(HPMVS_ERR_ARG, "undistort_map: bad device index");
-    HIPCHK(hipSetDevice(device));
-    const size_t nf = (size_t)w * h * 2;
-    float* dxy = nullptr;
-    struct Free { float*& a; ~Free() { if (a) hipFree(a); } } free_on_exit{dxy};
-    HIPCHK(hipMalloc((void**)&dxy, nf * sizeof(float)));
-    launch_undistort_map(w, h, f, k1, dxy, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(xy, dxy, nf * sizeof(float), hipMemcpyDeviceToHost));
-    return HPMVS_OK;
-}
 
 }  // extern "C"
 
@@ -1507,10 +931,8 @@ extern "C" int hpmvs_selftest_bobyqa(int device, int n, const int32_t* kind, con
     if (n < 0 || (n > 0 && (!kind || !params || !x0 || !lb || !ub || !xfinal || !minf || !result || !nevals || !rescue_calls)))
         return fail(HPMVS_ERR_ARG, "selftest_bobyqa: missing array");
     if (trace && trace_cap < 1) return fail(HPMVS_ERR_ARG, "selftest_bobyqa: trace_cap");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(HPMVS_ERR_NODEVICE, "no HIP device visible");
+    if (const int rc = use_device(device, "selftest_bobyqa")) return rc;
     if (n == 0) return HPMVS_OK;
-    HIPCHK(hipSetDevice(device));
     Call c(nullptr, 0, nullptr);
     const size_t N = (size_t)n;
     const int32_t* dkind = c.in(kind, N);

@@ -1,6 +1,6 @@
 // jpeg.hpp -- baseline JPEG decoding of a view's level 0 (reference Image::load through CImg and libjpeg,
 // src/hpmvs/Image.cpp:46, thirdLibs/cimg/CImg.h:36920-36934, library defaults: JDCT_ISLOW, fancy upsampling, the integer
-// YCbCr conversion), written once for the device kernels (kernel_jpeg.hip), the C ABI (capi.hip) and the host
+// YCbCr conversion), written once for the device kernels (kernel_jpeg.hip), the C ABI (capi_image.hip) and the host
 // restatement the tests compile with g++ (tests/jpeg_host.cpp).
 //
 // The split: the host parses the markers and either decodes the bit-serial entropy data into dense int16 coefficients

@@ -1,7 +1,7 @@
 // jpeg_enc.hpp -- baseline JPEG encoding of a view's level (reference Scene::saveAsNVM through CImg's save_jpeg and
 // libjpeg's defaults, src/hpmvs/Scene.cpp:646-713: jpeg_set_defaults + jpeg_set_quality(q, TRUE) on RGB rows, i.e. YCbCr
 // 4:2:0, JDCT_ISLOW, the Annex K Huffman tables, no restart markers), written once for the device kernels
-// (kernel_jpeg_encode.hip), the C ABI (capi.hip) and the host restatement the tests compile with g++
+// (kernel_jpeg_encode.hip), the C ABI (capi_image.hip) and the host restatement the tests compile with g++
 // (tests/jpeg_enc_host.cpp).  Everything is integer arithmetic; the file it describes equals libjpeg's byte for byte.
 //
 // The split: per MCU (Y00 Y01 Y10 Y11 Cb Cr) colour conversion, edge replication, h2v2 downsampling, the forward DCT and

@@ -174,7 +174,9 @@ int hpmvs_scene_get_level(const hpmvs_scene *s, int view, int level, uint8_t *ho
                           int *w, int *h);
 size_t hpmvs_scene_bytes(const hpmvs_scene *s);
 
-/* stand-alone pyramid kernel: src (w x h, device or host) -> dst (w/2 x h/2) */
+/* stand-alone pyramid kernel: src (w x h, device or host) -> dst (w/2 x h/2).  A `device` that is no index of a visible
+ * device is HPMVS_ERR_ARG "build_pyramid: bad device index", as for every entry that takes one (it used to be
+ * HPMVS_ERR_HIP with the text of the failed hipSetDevice). */
 int hpmvs_build_pyramid(int device, const uint8_t *src, int w, int h, uint8_t *dst, int on_device);
 
 /* ---- radial undistortion (VisualSFM's one-parameter model: NVM camera field r) ------------- */
@@ -901,7 +903,9 @@ int hpmvs_allgather_records(void *nccl_comm, const hpmvs_record *send, size_t co
  * that the device build of the blocks the photometric objective never reaches (rescue_, bobyqa.c:143-742; active
  * bounds; ROUNDOFF_LIMITED) can be compared evaluation by evaluation with the genuine library.  Host arrays:
  * kind[n], params[n][8], x0/lb/ub[n][3] in; xfinal[n][3], minf[n], result[n] (nlopt_result), nevals[n],
- * rescue_calls[n] out; trace[n][trace_cap][4] = (x0, x1, x2, f) of every evaluation (may be NULL). */
+ * rescue_calls[n] out; trace[n][trace_cap][4] = (x0, x1, x2, f) of every evaluation (may be NULL).
+ * A `device` that is no index of a visible device is HPMVS_ERR_ARG "selftest_bobyqa: bad device index", also for n = 0 (it
+ * used to be HPMVS_ERR_HIP with the text of the failed hipSetDevice, and HPMVS_OK for n = 0). */
 int hpmvs_selftest_bobyqa(int device, int n, const int32_t *kind, const double *params, const double *x0,
                           const double *lb, const double *ub, int maxeval, double *xfinal, double *minf,
                           int32_t *result, int32_t *nevals, int32_t *rescue_calls, double *trace, int trace_cap);
