@@ -107,6 +107,7 @@ EXPORTS = [
     "hpmvs_jpeg_decode_ex", "hpmvs_scene_set_view_jpeg_ex", "hpmvs_jpeg_coefficients", "hpmvs_jpeg_entropy_timed",
     "hpmvs_jpeg_last_decode",
     "hpmvs_jpeg_encode_bound", "hpmvs_jpeg_encode", "hpmvs_jpeg_encode_timed", "hpmvs_scene_get_level_jpeg",
+    "hpmvs_depth_colormap", "hpmvs_scene_depth_image", "hpmvs_scene_depth_jpeg",
 ]
 JPEG_ENTROPY = {"auto": 0, "host": 1, "device": 2}   # HPMVS_JPEG_ENTROPY_AUTO / _HOST / _DEVICE
 
@@ -181,6 +182,10 @@ def lib():
     L.hpmvs_scene_depth_set_level.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
     L.hpmvs_scene_depth_get_level.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int),
                                               C.POINTER(C.c_int)]
+    L.hpmvs_depth_colormap.argtypes = [C.c_void_p]
+    L.hpmvs_scene_depth_image.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_int),
+                                          C.POINTER(C.c_int), C.POINTER(C.c_float)]
+    L.hpmvs_scene_depth_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.hpmvs_set_depths_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_int, C.c_void_p]
     L.hpmvs_depth_footprints_batch.argtypes = [C.c_void_p, C.POINTER(PatchBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_int, C.c_void_p]
@@ -451,6 +456,28 @@ class Scene:
         _chk(lib().hpmvs_scene_get_level_jpeg(self.h, view, level, int(quality), out.ctypes.data, out.nbytes, C.byref(n)))
         return out[:n.value].tobytes()
 
+    def depth_image(self, view: int, level=None, with_range: bool = False):
+        """One depth map of the view (level None: the minimum over all levels, Scene::getFullDepth) as the jet-coloured image
+        the reference's Scene::visualizeDepths saves: uint8 [rows, cols, 3], rendered from the maps where they lie in HBM.
+        with_range: -> (image, (m, M)), the least and largest value the normalisation used."""
+        lv = DEPTH_COMBINED if level is None else int(level)
+        w, h = C.c_int(), C.c_int()
+        _chk(lib().hpmvs_scene_depth_image(self.h, view, lv, None, 0, 0, C.byref(w), C.byref(h), None))
+        out = np.empty((h.value, w.value, 3), dtype=np.uint8)
+        rng = (C.c_float * 2)()
+        _chk(lib().hpmvs_scene_depth_image(self.h, view, lv, out.ctypes.data if out.size else None, out.nbytes, 0, C.byref(w), C.byref(h), rng))
+        return (out, (np.float32(rng[0]), np.float32(rng[1]))) if with_range else out
+
+    def depth_jpeg(self, view: int, level=None, quality: int = 100) -> bytes:
+        """depth_image as the baseline JPEG file jpeg_encode writes for it; neither the cells nor the pixels visit the host.
+        Raises for a map under 8 cells on a side (HPMVS_ERR_UNSUPPORTED = -5)."""
+        lv = DEPTH_COMBINED if level is None else int(level)
+        n = C.c_size_t(0)
+        _chk(lib().hpmvs_scene_depth_jpeg(self.h, view, lv, int(quality), None, 0, C.byref(n)))
+        out = np.empty(n.value, dtype=np.uint8)
+        _chk(lib().hpmvs_scene_depth_jpeg(self.h, view, lv, int(quality), out.ctypes.data, out.nbytes, C.byref(n)))
+        return out[:n.value].tobytes()
+
     def last_staging(self):
         """(bytes copied through device buffers, bytes used in place) of the last host-pointer optimize_batch call."""
         a, b = C.c_ulonglong(), C.c_ulonglong()
@@ -635,6 +662,16 @@ def depth_set_level(scene: Scene, view: int, level: int, data):
     m = np.ascontiguousarray(data, dtype=np.float32)
     if m.size:   # (a 0-row level: nothing to copy)
         _chk(lib().hpmvs_scene_depth_set_level(scene.h, view, level, m.ctypes.data, m.shape[1], m.shape[0]))
+
+
+DEPTH_COMBINED = -1   # HPMVS_DEPTH_COMBINED
+
+
+def depth_colormap() -> np.ndarray:
+    """uint8 [256, 3]: the colormap of Scene.depth_image, CImg's jet_LUT256() (host only)."""
+    lut = np.zeros((256, 3), dtype=np.uint8)
+    _chk(lib().hpmvs_depth_colormap(lut.ctypes.data))
+    return lut
 
 
 def set_depths_batch(scene: Scene, batch: Batch):

@@ -1559,6 +1559,17 @@ static int depth_level(const hpmvs_scene* s, int view, int level, const char* wh
     *p = s->hdepth[view].d[level]; *rows = s->hdepth[view].rows[level]; *cols = s->hdepth[view].cols[level];
     return HPMVS_OK;
 }
+}  // extern "C"
+// (capi_common.hpp: the depth-image entries of capi_image.hip)
+int hpmvs::capi::scene_depth_maps(const hpmvs_scene* s, int view, int level, const char* who, SceneDepthMaps* out) {
+    float* p; int r, c, rc;
+    if ((rc = depth_level(s, view, level == HPMVS_DEPTH_COMBINED ? 0 : level, who, &p, &r, &c))) return rc;
+    out->device = s->device;
+    out->n_levels = s->hviews[view].n_levels;
+    out->maps = s->hdepth[view];
+    return HPMVS_OK;
+}
+extern "C" {
 int hpmvs_scene_depth_set_level(hpmvs_scene* s, int view, int level, const float* data, int rows, int cols) {
     float* p; int r, c, rc;
     if ((rc = depth_level(s, view, level, "scene_depth_set_level", &p, &r, &c))) return rc;

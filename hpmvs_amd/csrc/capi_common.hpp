@@ -1,7 +1,8 @@
 // capi_common.hpp -- what the translation units of the C ABI share (capi.hip: the scene and the batch entry points;
 // capi_image.hip: the image entry points): the error string and its macros, the device prologue, one owner for a device
-// buffer, one accumulator for a working buffer's layout, one set of event marks, and the few image functions the scene
-// entries of capi.hip call.  Host-only; no kernel includes it.
+// buffer, one accumulator for a working buffer's layout, one set of event marks, the few image functions the scene
+// entries of capi.hip call, and the accessor through which capi_image.hip reaches a scene's depth maps.  Host-only; no kernel
+// includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "../../include/hpmvs_amd.h"
+#include "dev_types.h"
 #include "jpeg.hpp"
 #include "jpeg_enc.hpp"
 
@@ -113,6 +115,15 @@ int jpeg_frame_to_device(const JpegFile& jf, uint8_t* d_rgb, float* ms = nullptr
 int jpeg_encode_device(const uint8_t* d_rgb, int W, int H, int quality, uint8_t* out, size_t cap, size_t* n, float* ms = nullptr);
 int jpeg_entropy_env();
 bool jpeg_entropy_ok(int e);
+
+// ---- a scene's depth maps (capi.hip, which alone knows hpmvs_scene) as the depth-image entries of capi_image.hip see them ----
+struct SceneDepthMaps {
+    int device = 0, n_levels = 0;
+    DevDepthView maps = {};  // one view's level pointers and shapes
+};
+// level: 0 .. n_levels - 1 or HPMVS_DEPTH_COMBINED.  The codes and messages of the depth-map entries: HPMVS_ERR_STATE
+// "<who>: call hpmvs_scene_depth_reset first", HPMVS_ERR_ARG "<who>: bad view / level".  Touches no device.
+int scene_depth_maps(const hpmvs_scene* s, int view, int level, const char* who, SceneDepthMaps* out);
 
 }  // namespace capi
 }  // namespace hpmvs

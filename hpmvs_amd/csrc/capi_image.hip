@@ -1,6 +1,7 @@
 // capi_image.hip -- the image entry points of include/hpmvs_amd.h: baseline JPEG decode (host walk or device entropy decode)
-// and encode, radial undistortion and the stand-alone pyramid step.  None of them touches a scene; the scene entries of
-// capi.hip that take or give JPEG bytes call the functions capi_common.hpp declares.  Host-side only.
+// and encode, radial undistortion, the stand-alone pyramid step and the depth maps as jet-coloured images.  Only the last
+// reach into a scene, through scene_depth_maps of capi_common.hpp; the scene entries of capi.hip that take or give JPEG bytes
+// call the functions capi_common.hpp declares.  Host-side only.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -11,6 +12,7 @@
 
 #include "../../include/hpmvs_amd.h"
 #include "capi_common.hpp"
+#include "depth_vis.hpp"
 #include "dev_types.h"
 #include "launch.h"
 
@@ -501,6 +503,96 @@ int hpmvs_undistort_map(int device, int w, int h, float f, float k1, float* xy) 
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(xy, dxy.p, nf * sizeof(float), hipMemcpyDeviceToHost));
     return HPMVS_OK;
+}
+
+}  // extern "C"
+
+// ---- depth maps as jet-coloured images (depth_vis.hpp, kernel_depth_vis.hip; reference Scene::visualizeDepths)
+// the image of `level` (or HPMVS_DEPTH_COMBINED): cols x rows of that level, of level 0 for the combined one
+static void depth_image_size(const SceneDepthMaps& dm, int level, int* W, int* H) {
+    const int l = level == HPMVS_DEPTH_COMBINED ? 0 : level;
+    *W = dm.maps.cols[l];
+    *H = dm.maps.rows[l];
+}
+
+// The image at the device address d_rgb (3 W H bytes) on the scene's device, which the caller made current; W, H > 0.  Ordered
+// behind pending map writes as hpmvs_scene_depth_get_level is: the null stream is drained first and the kernels run on it.
+// Returns after they have run.  The working buffer (the float image, the workgroups' minima and maxima, the colormap, m and
+// M) lives for this call only, so concurrent calls share nothing.  The maps are read, never written.
+static int depth_image_device(const SceneDepthMaps& dm, int level, int W, int H, uint8_t* d_rgb, float range[2]) {
+    const size_t n = (size_t)W * H;
+    const unsigned n_part = depth_vis_partials(W, H);
+    uint8_t lut[768];
+    dvis::make_colormap(lut);
+    Layout L;
+    const size_t o_vals = L.take(n * sizeof(float)), o_part = L.take((size_t)2 * n_part * sizeof(float)), o_lut = L.take(sizeof(lut)),
+                 o_range = L.take(2 * sizeof(float));
+    DeviceBuffer work;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(work.alloc(L.total));
+    HIPCHK(hipMemcpy(work.p + o_lut, lut, sizeof(lut), hipMemcpyHostToDevice));
+    launch_depth_vis_gather(dm.maps, dm.n_levels, level == HPMVS_DEPTH_COMBINED ? -1 : level, W, H, (float*)(work.p + o_vals),
+                            (float*)(work.p + o_part), nullptr);
+    HIPCHK(hipGetLastError());
+    launch_depth_vis_colour((const float*)(work.p + o_vals), n, (const float*)(work.p + o_part), n_part, work.p + o_lut, d_rgb,
+                            (float*)(work.p + o_range), nullptr);
+    HIPCHK(hipGetLastError());
+    float mM[2] = {0.0f, 0.0f};
+    HIPCHK(hipMemcpy(mM, work.p + o_range, sizeof(mM), hipMemcpyDeviceToHost));  // (waits for both kernels)
+    if (range) { range[0] = mM[0]; range[1] = mM[1]; }
+    return HPMVS_OK;
+}
+
+extern "C" {
+
+int hpmvs_depth_colormap(uint8_t lut[768]) {
+    if (!lut) return fail(HPMVS_ERR_ARG, "depth_colormap: null argument");
+    dvis::make_colormap(lut);
+    return HPMVS_OK;
+}
+
+int hpmvs_scene_depth_image(const hpmvs_scene* s, int view, int level, uint8_t* rgb, size_t cap, int rgb_on_device, int* width, int* height,
+                            float range[2]) {
+    SceneDepthMaps dm;
+    if (const int rc = scene_depth_maps(s, view, level, "scene_depth_image", &dm)) return rc;
+    int W, H;
+    depth_image_size(dm, level, &W, &H);
+    if (width) *width = W;
+    if (height) *height = H;
+    if (!rgb) return HPMVS_OK;  // size query
+    const size_t nb = (size_t)3 * W * H;
+    if (cap < nb) return fail(HPMVS_ERR_ARG, "scene_depth_image: buffer smaller than 3 * width * height");
+    if (nb == 0) {  // (a level of one pixel has a map without rows)
+        if (range) range[0] = range[1] = 0.0f;
+        return HPMVS_OK;
+    }
+    HIPCHK(hipSetDevice(dm.device));
+    if (rgb_on_device) return depth_image_device(dm, level, W, H, rgb, range);
+    DeviceBuffer d_rgb;
+    HIPCHK(d_rgb.alloc(nb));
+    if (const int rc = depth_image_device(dm, level, W, H, d_rgb.p, range)) return rc;
+    HIPCHK(hipMemcpy(rgb, d_rgb.p, nb, hipMemcpyDeviceToHost));
+    return HPMVS_OK;
+}
+
+int hpmvs_scene_depth_jpeg(const hpmvs_scene* s, int view, int level, int quality, uint8_t* out, size_t cap, size_t* n) {
+    if (!n) return fail(HPMVS_ERR_ARG, "scene_depth_jpeg: null argument");
+    SceneDepthMaps dm;
+    if (const int rc = scene_depth_maps(s, view, level, "scene_depth_jpeg", &dm)) return rc;
+    int W, H;
+    depth_image_size(dm, level, &W, &H);
+    std::string err;
+    const int rc = jpge::check_args(W, H, quality, &err);
+    if (rc != jpge::kOk) return jpeg_enc_fail(rc, err);
+    if (!out) {
+        *n = jpge::encode_bound(W, H);
+        return HPMVS_OK;
+    }
+    HIPCHK(hipSetDevice(dm.device));
+    DeviceBuffer d_rgb;
+    HIPCHK(d_rgb.alloc((size_t)3 * W * H));
+    if (const int rd = depth_image_device(dm, level, W, H, d_rgb.p, nullptr)) return rd;
+    return jpeg_encode_device(d_rgb.p, W, H, quality, out, cap, n);
 }
 
 }  // extern "C"

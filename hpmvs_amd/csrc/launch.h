@@ -97,6 +97,15 @@ int depth_ops_sort(void* temp, size_t* temp_bytes, const unsigned long long* key
 void launch_depth_ops_apply(const DevScene& sc, const DevDepthView* depths, float* pool, const DevBatch& b, const uint8_t* subtract,
                             const unsigned long long* keys, unsigned int count, hipStream_t st);
 
+// a view's depth maps as jet-coloured images (kernel_depth_vis.hip, depth_vis.hpp, include/hpmvs_amd.h: hpmvs_scene_depth_image).
+// level >= 0: that level's map, W x H its cols x rows; level < 0: the combined image over n_levels levels, W x H level 0's.
+// vals: [H][W] float; part: 2 * depth_vis_partials(W, H) floats; lut: dvis::make_colormap's bytes on the device; rgb: [H][W][3];
+// range: 2 floats, m and M as used.
+unsigned depth_vis_partials(int W, int H);
+void launch_depth_vis_gather(const DevDepthView& D, int n_levels, int level, int W, int H, float* vals, float* part, hipStream_t st);
+void launch_depth_vis_colour(const float* vals, size_t n, const float* part, unsigned n_part, const uint8_t* lut, uint8_t* rgb, float* range,
+                             hipStream_t st);
+
 // the cells a batch's gates read and setDepths would write (the scheduler's conflict test; layouts at the kernel)
 void launch_depth_footprints(const DevScene& sc, const DevDepthView* depths, const DevBatch& b, int32_t* wr, int32_t* fr, int32_t* at,
                              int32_t* vb, hipStream_t st);

@@ -8,8 +8,10 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <iomanip>
 #include <iostream>
+#include <sstream>
 #include <strings.h>
 #include <sys/stat.h>
 #include <algorithm>
@@ -540,6 +542,71 @@ bool Scene::saveAsNVM(const char* folder, const std::vector<Ppatch3d>& patches) 
     const std::string nvm = root + "/project.nvm";
     NVMReader::saveNVM(nvm.c_str(), models);
     return std::ifstream(nvm.c_str()).good();
+}
+
+// ---------------------------------------------------------------- Scene::visualizeDepths (reference src/hpmvs/Scene.cpp:434-516)
+bool Scene::visualizeDepths(const char* folder) const {
+    const std::string root(folder);
+    hpmvs_scene* dev = deviceScene();
+    if (!dev || cameras_.empty()) return false;
+    int W0 = 0, H0 = 0;  // (without depth maps nothing is written)
+    if (hpmvs_scene_depth_image(dev, 0, HPMVS_DEPTH_COMBINED, nullptr, 0, 0, &W0, &H0, nullptr) != HPMVS_OK) {
+        std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl;
+        return false;
+    }
+    if (!make_folder(root)) { std::cerr << "hpmvs: visualizeDepths: cannot create <" << root << ">" << std::endl; return false; }
+    std::ostringstream of;
+    of << "<!DOCTYPE html><html><head>";
+    of << "<style>table, th, td {border: 1px solid black;border-collapse: collapse;}";
+    of << "img { height: auto; width: 100%;}";
+    of << "th, td {padding: 5px;text-align: left;}</style>";
+    of << "</head><body>";
+    of << "<h2>Depth Images:</h2>";
+    of << "<table style=\"width:100%\">";
+    const int maxLevel = cameras_[0].getLevels();
+    of << "<tr><th>Color</th><th>Combined</th>";
+    for (int level = 0; level < maxLevel; level++) of << "<th>L" << level << "</th>";
+    of << "</tr>";
+    std::vector<uint8_t> file;
+    bool failed = false;
+    // one table cell: the image W x H as <name>.jpg, encoded by `encode` (out, cap, n) where it lies in HBM, or, under the
+    // encoder's 8 pixels on a side, no file and the text <W>x<H>
+    auto cell = [&](const std::string& name, int W, int H, const std::function<int(uint8_t*, size_t, size_t*)>& encode) {
+        if (W < 8 || H < 8) { of << "<td>" << W << "x" << H << "</td>"; return true; }
+        size_t n = 0;
+        if (encode(nullptr, 0, &n) != HPMVS_OK) return false;
+        file.resize(n);
+        if (encode(file.data(), file.size(), &n) != HPMVS_OK) return false;
+        const std::string filename = name + ".jpg";
+        std::ofstream out((root + "/" + filename).c_str(), std::ios::binary);
+        out.write((const char*)file.data(), (std::streamsize)n);
+        if (!out.good()) { std::cerr << "hpmvs: visualizeDepths: cannot write <" << root << "/" << filename << ">" << std::endl; failed = true; return false; }
+        of << "<td><img src=\"" << filename << "\"/></td>";
+        return true;
+    };
+    for (int i = 0; i < (int)cameras_.size(); i++) {
+        of << "<tr>";
+        int W = 0, H = 0;
+        bool ok = hpmvs_scene_get_level(dev, i, 1, nullptr, 0, &W, &H) == HPMVS_OK &&
+                  cell(std::to_string(i) + "_col", W, H,
+                       [&](uint8_t* o, size_t cap, size_t* n) { return hpmvs_scene_get_level_jpeg(dev, i, 1, 100, o, cap, n); });
+        for (int level = HPMVS_DEPTH_COMBINED; ok && level < maxLevel; level++) {
+            const std::string name = std::to_string(i) + (level == HPMVS_DEPTH_COMBINED ? std::string("_all") : "_" + std::to_string(level));
+            ok = hpmvs_scene_depth_image(dev, i, level, nullptr, 0, 0, &W, &H, nullptr) == HPMVS_OK &&
+                 cell(name, W, H, [&](uint8_t* o, size_t cap, size_t* n) { return hpmvs_scene_depth_jpeg(dev, i, level, 100, o, cap, n); });
+        }
+        if (!ok) {
+            if (!failed) std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl;
+            return false;
+        }
+        of << "</tr>";
+    }
+    of << "</table></body></html>";
+    const std::string html = root + "/overview.html", text = of.str();
+    std::ofstream out(html.c_str(), std::ios::binary);
+    out.write(text.data(), (std::streamsize)text.size());
+    if (!out.good()) { std::cerr << "hpmvs: visualizeDepths: cannot write <" << html << ">" << std::endl; return false; }
+    return true;
 }
 
 bool Scene::addCameras(const NVM_Model& model, const HpmvsOptions& options) {

@@ -289,6 +289,16 @@ public:
     // writeExtPly.  The quaternion is normalised in double behind the conversion (the reference leaves the float axes' 1e-7).
     // False, with the reason on stderr, when a folder or file cannot be written or a view cannot be encoded.
     bool saveAsNVM(const char* folder, const std::vector<Ppatch3d>& patches) const;
+    // Scene::visualizeDepths (src/hpmvs/Scene.cpp:434-516): the depth maps as jet-coloured JPEG files with an overview.html
+    // table around them, the reference's markup and column order.  Per view i: <i>_col.jpg, pyramid level 1's pixels;
+    // <i>_all.jpg, the getFullDepth map over all levels ("Combined"); <i>_<l>.jpg for l < cameras_[0].getLevels(), level l's map.
+    // Every image is normalised, coloured (CImg's normalize(0, 255) and jet_LUT256(), byte for byte) and encoded at quality 100
+    // where the maps lie in HBM (hpmvs_scene_depth_jpeg, hpmvs_scene_get_level_jpeg): no cell and no pixel visits the host.
+    // The one difference: an image under 8 pixels on a side (the encoder's lower bound) has no file, and its table cell holds
+    // the text <cols>x<rows> instead of an <img>.  The folder is created when it is missing.  False when the maps do not exist
+    // (resetDepths), a device call fails (hpmvs_last_error names the reason, also on stderr) or a file cannot be written
+    // (the reason on stderr, as saveAsNVM reports it).
+    bool visualizeDepths(const char* folder) const;
     std::map<std::string, int> dict_;
     std::vector<Camera> cameras_;
     std::vector<Image> images_;

@@ -30,6 +30,8 @@
  *   hpmvs_scene_set_view_jpeg   (thirdLibs/cimg/CImg.h:36920-36934).
  *   hpmvs_jpeg_encode,       <- the views Scene::saveAsNVM writes, src/hpmvs/Scene.cpp:646-713, through CImg's save_jpeg
  *   hpmvs_scene_get_level_jpeg  and libjpeg at quality 100 (thirdLibs/cimg/CImg.h:40748-40838).
+ *   hpmvs_scene_depth_image, <- the images Scene::visualizeDepths saves, src/hpmvs/Scene.cpp:434-516, through CImg's
+ *   hpmvs_scene_depth_jpeg      normalize, map and jet_LUT256 (thirdLibs/cimg/CImg.h:18423-18435, 19034-19078, 19331-19341).
  *   hpmvs_init_patches_batch <- the seed loop of Scene::initPatches, src/hpmvs/Scene.cpp:112-178.
  *   hpmvs_init_patches_sphere_batch <- the same loop with the scene-centre gate of --only_sphere
  *                               (options.FILTER_SCENE_CENTER), src/hpmvs/Scene.cpp:105-121.
@@ -301,6 +303,33 @@ int hpmvs_scene_get_level_jpeg(const hpmvs_scene *s, int view, int level, int qu
  * data's copy to the host. */
 int hpmvs_jpeg_encode_timed(int device, const uint8_t *rgb_device, int width, int height, int quality, uint8_t *out, size_t cap,
                             size_t *n, float *ms);
+
+/* ---- depth maps as jet-coloured images ------------------------------------------------------- */
+/* Scene::visualizeDepths of the reference (src/hpmvs/Scene.cpp:434-516) renders every depth map, and per view the
+ * getFullDepth map over all levels ("Combined"), as an image: a cell equal to MAX_DEPTH becomes 0, CImg's normalize(0, 255)
+ * maps the image's least value m and largest value M to 0 and 255 in float32 (m == M: every pixel 0; m == 0 and M == 255:
+ * left as it is), the truncated result indexes CImg's 256-entry jet_LUT256().  These entries give that image byte for
+ * byte (tests/golden/g9_depth_vis.npz) from the maps where they lie in HBM (hpmvs_scene_depth_reset): no cell and no pixel
+ * visits the host (kernel_depth_vis.hip).  The image of a level is cols wide and rows high, pixel (x, y) the map's element
+ * (y, x): the transpose of the column-major memory order.  The combined image has level 0's size; its pixel (x, y) is the
+ * least cell over the levels at (x >> l, y >> l), up to the first level where that cell lies outside the map.
+ * A cell that is no finite number counts as empty (the reference's result for one is undefined); negative finite cells are
+ * ordinary values.  The maps are only read.  Calls are ordered behind pending map writes as hpmvs_scene_depth_get_level is,
+ * keep nothing between them and may run concurrently.
+ * level: 0 .. n_levels - 1 or HPMVS_DEPTH_COMBINED.  HPMVS_ERR_STATE without depth maps and HPMVS_ERR_ARG for a bad view /
+ * level, as the depth-map entries report them; arguments are checked before the device is touched. */
+#define HPMVS_DEPTH_COMBINED (-1)
+/* host only: the 256 RGB entries of the colormap, entry i at lut[3*i .. 3*i+2] */
+int hpmvs_depth_colormap(uint8_t lut[768]);
+/* rgb: width x height interleaved u8 RGB, 3*(y*W+x)+c, host memory or (rgb_on_device != 0) device memory on the scene's
+ * device, of cap >= 3*W*H bytes (else HPMVS_ERR_ARG); rgb == NULL: a size query, only *width and *height are set (both
+ * nullable).  range (nullable): m and M as used. */
+int hpmvs_scene_depth_image(const hpmvs_scene *s, int view, int level, uint8_t *rgb, size_t cap, int rgb_on_device, int *width,
+                            int *height, float range[2]);
+/* That image as the baseline JPEG file hpmvs_jpeg_encode writes for it, with hpmvs_scene_get_level_jpeg's conventions:
+ * out == NULL: *n = the bound; cap smaller than the file: HPMVS_ERR_ARG, nothing written, *n the length needed; a map under
+ * 8 cells on a side: HPMVS_ERR_UNSUPPORTED. */
+int hpmvs_scene_depth_jpeg(const hpmvs_scene *s, int view, int level, int quality, uint8_t *out, size_t cap, size_t *n);
 
 /* ---- the hot path ------------------------------------------------------------------------- */
 /* Full optimize() for every patch of the batch.  `stream` is a hipStream_t (NULL = default
