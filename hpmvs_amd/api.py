@@ -108,6 +108,7 @@ EXPORTS = [
     "hpmvs_jpeg_last_decode",
     "hpmvs_jpeg_encode_bound", "hpmvs_jpeg_encode", "hpmvs_jpeg_encode_timed", "hpmvs_scene_get_level_jpeg",
     "hpmvs_depth_colormap", "hpmvs_scene_depth_image", "hpmvs_scene_depth_jpeg",
+    "hpmvs_ply_ext_batch", "hpmvs_ply_ext_timed",
 ]
 JPEG_ENTROPY = {"auto": 0, "host": 1, "device": 2}   # HPMVS_JPEG_ENTROPY_AUTO / _HOST / _DEVICE
 
@@ -221,6 +222,10 @@ def lib():
     L.hpmvs_octree_route_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.hpmvs_octree_partition.argtypes = [C.c_void_p, C.POINTER(OctreeIndex), C.c_int, C.c_int, C.POINTER(OctreePartitionInfo)] + \
         [C.c_void_p] * 9 + [C.c_int, C.c_void_p]
+    L.hpmvs_ply_ext_batch.argtypes = [C.c_int, C.POINTER(PatchBatch), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                      C.POINTER(C.c_size_t), C.c_int, C.c_void_p]
+    L.hpmvs_ply_ext_timed.argtypes = [C.c_int, C.POINTER(PatchBatch), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                      C.POINTER(C.c_size_t), C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -1159,3 +1164,43 @@ def octree_partition(scene: Scene, root_center, root_width, branch_key, leaf_key
     r.n_trees, r.n_orphans, r.n_splits, r.stop = info.n_trees, info.n_orphans, info.n_splits, info.stop
     r.histogram[:] = info.histogram[:]
     return r
+
+
+PLY_BINARY, PLY_NORMAL, PLY_SCALE, PLY_VISIBILITY = 1, 2, 4, 8   # HPMVS_PLY_*
+
+
+def ply_flags(binary=False, normal=True, scale=True, visibility=True) -> int:
+    return (PLY_BINARY if binary else 0) | (PLY_NORMAL if normal else 0) | (PLY_SCALE if scale else 0) | \
+        (PLY_VISIBILITY if visibility else 0)
+
+
+def ply_ext(batch: Batch, order=None, binary=False, normal=True, scale=True, visibility=True, device: int = 0) -> np.ndarray:
+    """The file the reference's DynOctTree::toExtPly writes (include/hpmvs/doctree.h:526-622; the defaults are its own, ASCII) for
+    the rows `order` of the batch -- None: all rows in order; a row may be named more than once -- as a uint8 array, header
+    included: float-to-text conversion, the lines' placement and their writing run on the GPU (include/hpmvs_amd.h:
+    hpmvs_ply_ext_batch).  Reads center, normal, scale, color, n_images, images; a batch whose arrays are device tensors is read
+    in place (`order` then is a device tensor too).  Makes a size query first, then the call.  HpmvsError naming the row for an
+    order entry outside the batch or an n_images outside [0, max_images]."""
+    b = batch.c_struct()
+    on_device = int(not isinstance(batch.center, np.ndarray))
+    n_rows = 0
+    if order is not None:
+        if not on_device:
+            order = np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
+        n_rows = int(order.shape[0])
+        if n_rows == 0:   # (a NULL order means every row: an empty one still needs an address)
+            order = np.zeros(1, dtype=np.int32) if not on_device else torch.zeros(1, dtype=torch.int32, device=order.device)
+    flags = ply_flags(binary, normal, scale, visibility)
+    n = C.c_size_t(0)
+    _chk(lib().hpmvs_ply_ext_batch(device, C.byref(b), _ptr(order), n_rows, flags, None, 0, C.byref(n), on_device, None))
+    out = np.empty(n.value, dtype=np.uint8)
+    _chk(lib().hpmvs_ply_ext_batch(device, C.byref(b), _ptr(order), n_rows, flags, out.ctypes.data, out.nbytes, C.byref(n), on_device, None))
+    return out[:n.value]
+
+
+def write_ext_ply(path, batch: Batch, order=None, binary=False, normal=True, scale=True, visibility=True, device: int = 0) -> int:
+    """ply_ext's bytes as the file `path`; returns their number."""
+    data = ply_ext(batch, order, binary, normal, scale, visibility, device)
+    with open(path, "wb") as f:
+        f.write(data.tobytes())
+    return int(data.size)

@@ -24,6 +24,7 @@
 #include "dev_types.h"
 #include "launch.h"
 #include "octree.hpp"
+#include "ply_text.hpp"
 
 using namespace hpmvs;
 using namespace hpmvs::capi;
@@ -948,7 +949,109 @@ extern "C" int hpmvs_selftest_bobyqa(int device, int n, const int32_t* kind, con
     return c.finish();
 }
 
+// ---- the patch cloud as DynOctTree::toExtPly's file (kernel_ply.hip, ply_text.hpp) ---------------------------------------------
+// One implementation under hpmvs_ply_ext_batch and hpmvs_ply_ext_timed (ms != nullptr: host pointers, the null stream, six stage
+// times).  The header is built on the host; the body's lengths, places and bytes on the device; one read of 16 bytes brings back
+// the body's length and the error word.
+static int ply_ext(const char* who, int device, const hpmvs_patch_batch* b, const int32_t* order, int n_rows, int flags, uint8_t* out, size_t cap,
+                   size_t* n, int on_device, hipStream_t st, float* ms) {
+    const std::string w(who);
+    if (!b || !n) return fail(HPMVS_ERR_ARG, w + ": null argument");
+    if (flags & ~ply::kAllFlags) return fail(HPMVS_ERR_ARG, w + ": unknown flag bits");
+    if (!out && cap) return fail(HPMVS_ERR_ARG, w + ": a capacity without an output buffer");
+    if (b->n < 0 || b->max_images < 0) return fail(HPMVS_ERR_ARG, w + ": bad n/max_images");
+    if (order && n_rows < 0) return fail(HPMVS_ERR_ARG, w + ": negative n_rows");
+    const int R = order ? n_rows : b->n;
+    const bool vis = (flags & ply::kVisibility) != 0;
+    if (R > 0 && (!b->center || !b->color || ((flags & ply::kNormal) && !b->normal) || ((flags & ply::kScale) && !b->scale) ||
+                  (vis && (!b->n_images || (b->max_images > 0 && !b->images)))))
+        return fail(HPMVS_ERR_ARG, w + ": batch arrays missing");
+    if (const int rc = use_device(device, who)) return rc;
+    const std::string head = ply::header(R, flags);
+    if (ms) for (int k = 0; k < 6; k++) ms[k] = 0.0f;
+    if (R == 0) {
+        *n = head.size();
+        if (!out) return HPMVS_OK;
+        if (cap < *n) return fail(HPMVS_ERR_ARG, w + ": output buffer too small (" + std::to_string(*n) + " bytes needed)");
+        memcpy(out, head.data(), head.size());
+        return HPMVS_OK;
+    }
+    EventMarks ev(7, ms != nullptr);
+    HIPCHK(ev.created());
+    HIPCHK(ev.mark(0));
+    Call c(nullptr, on_device, st);
+    const size_t N = (size_t)b->n, rows = (size_t)R, n_len = 2 * rows + 1;
+    PlyRows A;
+    memset(&A, 0, sizeof(A));
+    A.n = b->n; A.max_images = b->max_images; A.n_rows = R; A.flags = flags;
+    A.center = c.in(b->center, 4 * N);
+    A.color = c.in(b->color, 3 * N);
+    if (flags & ply::kNormal) A.normal = c.in(b->normal, 4 * N);
+    if (flags & ply::kScale) A.scale = c.in(b->scale, N);
+    if (vis) { A.n_images = c.in(b->n_images, N); A.images = c.in(b->images, N * (size_t)b->max_images); }
+    A.order = order ? c.in(order, rows) : nullptr;
+    size_t scan_bytes = 0;
+    HIPCHK((hipError_t)jpeg_enc_scan(nullptr, &scan_bytes, nullptr, nullptr, n_len, nullptr));
+    Layout L;
+    // (the scan's last entry and the error word lie side by side: one read brings both back)
+    const size_t o_len = L.take(n_len * 8), o_offs = L.take((n_len + 1) * 8), o_temp = L.take(scan_bytes),
+                 o_rec = L.take((flags & ply::kBinary) ? 0 : ply::kRowRecords * rows * sizeof(uint32_t));
+    uint8_t* work = (uint8_t*)c.scratch(L.total);
+    int rc;
+    if ((rc = c.begin(st))) return rc;
+    HIPCHK(ev.mark(1));
+    unsigned long long *d_len = (unsigned long long*)(work + o_len), *d_offs = (unsigned long long*)(work + o_offs);
+    A.len = d_len;
+    A.rec = (uint32_t*)(work + o_rec);
+    A.err = (unsigned int*)(d_offs + n_len);
+    HIPCHK(hipMemsetAsync(d_len + (n_len - 1), 0, 8, st));
+    HIPCHK(hipMemsetAsync(d_offs + n_len, 0xFF, 8, st));
+    launch_ply_len(A, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(ev.mark(2));
+    HIPCHK((hipError_t)jpeg_enc_scan(work + o_temp, &scan_bytes, d_len, d_offs, n_len, st));
+    unsigned long long back[2] = {0ull, 0ull};   // the body's length; the error word in the low half of the second
+    HIPCHK(hipMemcpyAsync(back, d_offs + (n_len - 1), 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(ev.mark(3));
+    const unsigned int err = (unsigned int)(back[1] & 0xFFFFFFFFull);
+    if (err != 0xFFFFFFFFu) {
+        const std::string row = w + ": row " + std::to_string(err >> 1);
+        return fail(HPMVS_ERR_ARG, (err & 1u) ? row + " holds an n_images outside [0, " + std::to_string(b->max_images) + "]"
+                                              : row + " names a patch outside [0, " + std::to_string(b->n) + ")");
+    }
+    const size_t body = (size_t)back[0];
+    *n = head.size() + body;
+    if (!out) return c.finish();
+    if (cap < *n) return fail(HPMVS_ERR_ARG, w + ": output buffer too small (" + std::to_string(*n) + " bytes needed)");
+    uint8_t* d_body = (uint8_t*)c.scratch(body);
+    if ((rc = c.error())) return rc;
+    launch_ply_vertex(A, d_offs, d_body, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(ev.mark(4));
+    launch_ply_list(A, d_offs, d_body, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(ev.mark(5));
+    HIPCHK(hipMemcpyAsync(out + head.size(), d_body, body, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(ev.mark(6));
+    memcpy(out, head.data(), head.size());
+    if (ms) {
+        HIPCHK(ev.sync(6));
+        for (int k = 0; k < 6; k++) HIPCHK(ev.elapsed(k, k + 1, &ms[k]));
+    }
+    return c.finish();
+}
 
+extern "C" int hpmvs_ply_ext_batch(int device, const hpmvs_patch_batch* b, const int32_t* order, int n_rows, int flags, uint8_t* out, size_t cap,
+                                   size_t* n, int on_device, void* stream) {
+    return ply_ext("ply_ext_batch", device, b, order, n_rows, flags, out, cap, n, on_device, (hipStream_t)stream, nullptr);
+}
+extern "C" int hpmvs_ply_ext_timed(int device, const hpmvs_patch_batch* b, const int32_t* order, int n_rows, int flags, uint8_t* out, size_t cap,
+                                   size_t* n, float* ms) {
+    if (!ms) return fail(HPMVS_ERR_ARG, "ply_ext_timed: null argument");
+    return ply_ext("ply_ext_timed", device, b, order, n_rows, flags, out, cap, n, 0, nullptr, ms);
+}
 
 // ---- pooled staging of a small host batch -------------------------------------------------------------------------
 namespace {

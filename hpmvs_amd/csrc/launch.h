@@ -106,6 +106,24 @@ void launch_depth_vis_gather(const DevDepthView& D, int n_levels, int level, int
 void launch_depth_vis_colour(const float* vals, size_t n, const float* part, unsigned n_part, const uint8_t* lut, uint8_t* rgb, float* range,
                              hipStream_t st);
 
+// the patch cloud as DynOctTree::toExtPly's file (kernel_ply.hip, ply_text.hpp, include/hpmvs_amd.h: hpmvs_ply_ext_batch).  Row r of the
+// file is patch order[r] (order == nullptr: patch r).  rec: [10][n_rows] digit records, ASCII only; len: [2 n_rows + 1] the rows'
+// vertex lengths, then their list lengths, then 0 (the caller zeroes the last entry); err: one word, UINT_MAX before -- 2 row + kind
+// of the lowest bad row behind launch_ply_len (kind 0: its order entry is outside [0, n), 1: its n_images outside [0, max_images]).
+// offs: the exclusive scan of len (jpeg_enc_scan), offs[2 n_rows] the body's length; body: the file behind its header.  The two
+// write launches go only behind a clean error word.
+struct PlyRows {
+    int32_t n, max_images, n_rows, flags;   // flags: HPMVS_PLY_*
+    const float *center, *normal, *scale, *color;
+    const int32_t *n_images, *images, *order;
+    uint32_t* rec;
+    unsigned long long* len;
+    unsigned int* err;
+};
+void launch_ply_len(const PlyRows& A, hipStream_t st);
+void launch_ply_vertex(const PlyRows& A, const unsigned long long* offs, uint8_t* body, hipStream_t st);
+void launch_ply_list(const PlyRows& A, const unsigned long long* offs, uint8_t* body, hipStream_t st);
+
 // the cells a batch's gates read and setDepths would write (the scheduler's conflict test; layouts at the kernel)
 void launch_depth_footprints(const DevScene& sc, const DevDepthView* depths, const DevBatch& b, int32_t* wr, int32_t* fr, int32_t* at,
                              int32_t* vb, hipStream_t st);

@@ -1256,3 +1256,22 @@ def partition(scene: api.Scene, tree: Octree, min_trees: int = 100, min_split_le
     lk, rows, _, _ = tree.leaf_table()
     P = api.octree_partition(scene, tree.root_center, tree.root_width, bk, lk, min_trees, min_split_leaves)
     return partition_from_arrays(tree, bk, lk, rows, P)
+
+
+def forest_leaf_order(trees, root_key, orphans=()) -> np.ndarray:
+    """The rows of all subtrees and orphans in the WHOLE tree's Leaf_iterator order, data order within a leaf: the `order` that
+    makes api.ply_ext write the file scene.patchTree_.toExtPly would (reference include/hpmvs/doctree.h:526-622 walks the whole
+    tree, whatever the split into subtrees).  trees[t]: an Octree whose keys are relative to root_key[t], the root's path key
+    in the whole tree (Partition.trees, Partition.root_key); orphans: (whole-tree leaf key, row) pairs of the nonempty leaves in
+    no subtree.  A row is a patch index or a sequence of them (a leaf's data, in order).  Every key is re-based on its root's key
+    and the leaves are sorted by the aligned key Octree.leaf_table sorts by.  Host code."""
+    leaves = [(int(k), row) for k, row in orphans]
+    for sub, root in zip(trees, root_key):
+        for k, row in sub.leaves.items():
+            d = key_depth(k)
+            leaves.append(((int(root) << (3 * d)) | (k ^ (1 << (3 * d))), row))
+    leaves.sort(key=lambda kr: Octree._aligned(kr[0]))
+    out = []
+    for _, row in leaves:
+        out.extend(int(r) for r in np.atleast_1d(row))
+    return np.array(out, dtype=np.int32)

@@ -544,6 +544,41 @@ bool Scene::saveAsNVM(const char* folder, const std::vector<Ppatch3d>& patches) 
     return std::ifstream(nvm.c_str()).good();
 }
 
+// ---------------------------------------------------------------- Scene::toExtPly (reference include/hpmvs/doctree.h:526-622)
+// writeExtPly's file, made on the scene's device by hpmvs_ply_ext_batch: the patches travel as one structure of arrays, the file
+// comes back whole.  The lists keep every id (the row stride is the longest list's length).
+bool Scene::toExtPly(const char* name, const std::vector<Ppatch3d>& patches, bool binary, bool normal, bool scale, bool visibility) const {
+    const size_t n = patches.size();
+    size_t stride = 0;
+    for (const Ppatch3d& p : patches) stride = std::max(stride, p->images_.size());
+    if (n > (size_t)INT_MAX || stride > (size_t)INT_MAX) { std::cerr << "hpmvs: toExtPly: too many patches or ids" << std::endl; return false; }
+    std::vector<float> center(4 * n), nrm(4 * n), scl(n), color(3 * n);
+    std::vector<int32_t> nimg(n), images(n * stride, -1);
+    for (size_t i = 0; i < n; i++) {
+        const Patch3d& p = *patches[i];
+        for (int k = 0; k < 4; k++) { center[4 * i + k] = p.center_[k]; nrm[4 * i + k] = p.normal_[k]; }
+        for (int k = 0; k < 3; k++) color[3 * i + k] = p.color_[k];
+        scl[i] = p.scale_3dx_;
+        nimg[i] = (int32_t)p.images_.size();
+        std::copy(p.images_.begin(), p.images_.end(), images.begin() + (std::ptrdiff_t)(i * stride));
+    }
+    hpmvs_patch_batch b;
+    memset(&b, 0, sizeof(b));
+    b.n = (int32_t)n; b.max_images = (int32_t)stride;
+    b.center = center.data(); b.normal = nrm.data(); b.scale = scl.data(); b.color = color.data(); b.n_images = nimg.data(); b.images = images.data();
+    const int flags = (binary ? HPMVS_PLY_BINARY : 0) | (normal ? HPMVS_PLY_NORMAL : 0) | (scale ? HPMVS_PLY_SCALE : 0) |
+                      (visibility ? HPMVS_PLY_VISIBILITY : 0);
+    size_t bytes = 0;
+    if (hpmvs_ply_ext_batch(device_, &b, nullptr, 0, flags, nullptr, 0, &bytes, 0, nullptr) != HPMVS_OK) { std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl; return false; }
+    std::vector<uint8_t> file(bytes);
+    if (hpmvs_ply_ext_batch(device_, &b, nullptr, 0, flags, file.data(), file.size(), &bytes, 0, nullptr) != HPMVS_OK) { std::cerr << "hpmvs: " << hpmvs_last_error() << std::endl; return false; }
+    std::ofstream out(name, std::ios::binary);
+    out.write((const char*)file.data(), (std::streamsize)bytes);
+    out.close();
+    if (!out.good()) { std::cerr << "hpmvs: toExtPly: cannot write <" << name << ">" << std::endl; return false; }
+    return true;
+}
+
 // ---------------------------------------------------------------- Scene::visualizeDepths (reference src/hpmvs/Scene.cpp:434-516)
 bool Scene::visualizeDepths(const char* folder) const {
     const std::string root(folder);

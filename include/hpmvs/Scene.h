@@ -299,6 +299,16 @@ public:
     // (resetDepths), a device call fails (hpmvs_last_error names the reason, also on stderr) or a file cannot be written
     // (the reason on stderr, as saveAsNVM reports it).
     bool visualizeDepths(const char* folder) const;
+    // scene.patchTree_.toExtPly(name, ...) (include/hpmvs/doctree.h:526-622, the file main writes after every tenth priority and as
+    // patches-final.ply) with the reference's own defaults, ASCII: the header, per patch x y z [nx ny nz] red green blue
+    // [scalar_scale], then per patch its image list.  Float-to-text conversion, the lines' placement and their writing run on the
+    // scene's device (hpmvs_ply_ext_batch); the file equals writeExtPly's (PlyWriter.h) byte for byte for colours in [0, 256).  A
+    // colour outside is clamped to 0 .. 255 and a NaN gives 0: the reference's ASCII path prints (int) color_ there (300, -3),
+    // its binary path and writeExtPly convert with an undefined (unsigned char).  The image lists travel as one dense
+    // patches x longest-list array: one long list widens every row.  The reference walks its patchTree_; here the patches are handed in, as they are to saveAsNVM, in the order they
+    // are to be written.  False, with the reason on stderr as saveAsNVM reports it, when the device call fails or the file cannot be written.
+    bool toExtPly(const char* name, const std::vector<Ppatch3d>& patches, bool binary = false, bool normal = true, bool scale = true,
+                  bool visibility = true) const;
     std::map<std::string, int> dict_;
     std::vector<Camera> cameras_;
     std::vector<Image> images_;

@@ -925,6 +925,35 @@ int hpmvs_pack_records(const hpmvs_patch_batch *b, hpmvs_record *records, void *
 int hpmvs_unpack_records(const hpmvs_record *records, int n, hpmvs_patch_batch *b, void *stream);
 int hpmvs_allgather_records(void *nccl_comm, const hpmvs_record *send, size_t count, hpmvs_record *recv, void *stream);
 
+/* ---- the patch cloud as an extended PLY file (reference DynOctTree::toExtPly, include/hpmvs/doctree.h:526-622) -------------------
+ * The header's lines; then per row x y z [nx ny nz] red green blue [scalar_scale]; then, with VISIBILITY, per row the list
+ * "n id id ...".  ASCII (the reference's default): every field is followed by one space and every line ends " \n"; a float is
+ * what `ostream << float` writes, printf("%.6g") of its exact value, n is written as int and an id as uint32_t (-1 prints
+ * 4294967295).  Binary: per row 3 floats, [3 floats], 3 bytes, [1 float], then per row uint32 n and n uint32 ids, little endian.
+ * A colour is the float truncated towards zero; below 0 it is 0, from 256 up 255, a NaN 0 (there the reference's ASCII path
+ * prints (int) of the float, 300 or -3, and its binary path's (unsigned char) is undefined).
+ * The conversion is integer arithmetic on the float's exact value (hpmvs_amd/csrc/ply_text.hpp) and runs on the device, as do the
+ * placement of the lines (a 64-bit prefix sum: a cloud's text can pass 4 GiB) and their writing; DESIGN.md 3.21. */
+#define HPMVS_PLY_BINARY 1
+#define HPMVS_PLY_NORMAL 2
+#define HPMVS_PLY_SCALE 4
+#define HPMVS_PLY_VISIBILITY 8
+/* The file DynOctTree::toExtPly writes for the rows order[0 .. n_rows-1] of b (order == NULL: rows 0 .. b->n-1, n_rows ignored;
+ * a row may be named more than once), header included.  Reads center, normal, scale, color, n_images, images (those the flags
+ * ask for; max_images may be any row stride >= 0); b's arrays and order are host pointers, or with on_device device pointers on
+ * `device`; out is host memory.  out == NULL: *n = the file's exact length and nothing else is written.  cap smaller than the
+ * file: HPMVS_ERR_ARG, nothing written, *n the length needed.  Zero rows give the header alone.
+ * HPMVS_ERR_ARG before the device is looked for (HPMVS_ERR_NODEVICE): NULL b or n, a negative b->n, max_images or (with order)
+ * n_rows, unknown flag bits, a cap with out == NULL, a missing array.  HPMVS_ERR_ARG with nothing written and the lowest such
+ * row named in hpmvs_last_error: an order entry outside [0, b->n), and with VISIBILITY an n_images outside [0, max_images].
+ * The call waits for its result (out is complete on return) and keeps nothing between calls. */
+int hpmvs_ply_ext_batch(int device, const hpmvs_patch_batch *b, const int32_t *order, int n_rows, int flags,
+                        uint8_t *out, size_t cap, size_t *n, int on_device, void *stream);
+/* diagnostics (tools/ply_ext_scale.py): the same for host pointers with the stage times by HIP events: staging in, ply_len_kernel,
+ * the scan and the total's read-back, ply_vertex_kernel, ply_list_kernel, the copy to the host */
+int hpmvs_ply_ext_timed(int device, const hpmvs_patch_batch *b, const int32_t *order, int n_rows, int flags,
+                        uint8_t *out, size_t cap, size_t *n, float *ms /*[6]*/);
+
 /* ---- diagnostics --------------------------------------------------------------------------------------------------
  * The optimiser that optimize_kernel runs per lane (NLopt 2.4.2 LN_BOBYQA as PatchOptimizer.cpp:348-365 configures
  * it: 3 variables, xtol_rel 1e-7, default initial step), driven ON THE GPU by the analytic objectives of
